@@ -2,7 +2,8 @@
 """MPPI control-step benchmark (BASELINE.json metric: rollout-steps/s, K x H
 state-steps, plus control-step p50 latency).
 
-    python bench.py [--gpus 1] [--steps K] [--warmup W] [--workload arm_c3]
+    python bench.py [--gpus 1] [--steps K] [--warmup W] [--workload arm_c3] [--dump-outputs DIR]
+    python bench.py --full ...        (the plain run plus every other figure, below)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N ...
     python bench.py --gpus N ...      (no launcher: bench.py starts the N ranks itself, as a child)
@@ -23,6 +24,21 @@ Workloads (the same primary workload at every N, so the driver's per-N values fo
 on the GPU (back-to-back steps, one host sync), bracketed by barrier + synchronize on
 both sides and the max over ranks.  The host-inclusive call latency (state H2D, outputs,
 check_reach) is ``latency_p50/p99_ms`` (never ``value``).
+
+A plain run does what ``value`` needs and no more: set-up, the warmup, the timed batches of
+exactly ``--steps`` control steps each (``ms_per_step``: the median batch / steps), the outputs
+if ``--dump-outputs`` is given, the line.  ``--full`` adds every other figure to the line: the
+event-timed kernel loops and the roofline, the batches without the heat-up, the latency legs
+(back to back, 100 Hz, prewarm, drop-in), the secondary workloads, the CPU baseline and the
+re-measured HBM bandwidth; ``--latency-steps``, ``--secondary``, ``--no-cpu-baseline`` and
+``--no-kernel-timing`` trim a ``--full`` run.
+
+``--dump-outputs DIR`` (one GPU) writes what a caller of the timed path (``mppi_run_steps``)
+receives after the last timed step as ``DIR/<name>.npy``: ``out`` (float64) and ``u0``
+(``mppi_read_outputs``), the warm start ``u_prev``, the last rollout's ``costs`` and ``stats``
+(rho, eta, ess per vehicle).  Every batch's ``--warmup`` steps then start from the engine's
+first-step inputs (initial warm start, Philox step counter 0), so the dumped step is step
+``max(1, warmup) + steps`` of a fixed sequence whatever the heat-up ran before it.
 
 Rank 0 prints ONE JSON line on stdout; progress goes to stderr.
 """
@@ -46,6 +62,7 @@ DRONE_TARGET = [1.0, 2.0, 3.4]                                   # drone_mppi.py
 PREWARM_US = 200        # latency_100hz_prewarm's window (mppi_set_prewarm)
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
 C4_K_TOTAL = 65536      # BASELINE configs[3]: whole-body K=65536 H=64 over the node
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all arrays together
 
 WORKLOADS = {
     # configs[2]: Kinova arm MPPI with on-GPU FK chain, K=4096 H=32 (BASELINE metric shape)
@@ -389,7 +406,12 @@ class StepsGivenUp(RuntimeError):
     point: the verdict comes from ShardedEngine.synchronize(), itself a collective."""
 
 
-def run_workload(name, steps_n, warmup, world, dist, lat_steps, timing=True, batches=1, lat_rate_calls=0):
+def run_workload(name, steps_n, warmup, world, dist, lat_steps, timing=True, batches=1, lat_rate_calls=0,
+                 cold=True, dump=False):
+    """One workload's measurements.  ``timing``: the event-timed kernel loops; ``cold``: the batches
+    without the heat-up too; ``lat_steps`` / ``lat_rate_calls``: the latency legs; ``dump``: every
+    batch's warmup starts from the first step's inputs and the last batch's outputs are returned
+    (``outputs``)."""
     import torch
     from quadrotor_manipulator_mppi_amd.distributed import ShardedEngine
     w = dict(WORKLOADS[name])
@@ -419,6 +441,7 @@ def run_workload(name, steps_n, warmup, world, dist, lat_steps, timing=True, bat
         state = make_state(w["model"], se.vehicles.stop)[se.vehicles.start:]
         eng.set_state(state)
         red_dev = "cuda" if dist is not None and dist.get_backend() == "nccl" else "cpu"
+        start = (eng.get_u_prev(), eng.get_step_counter()) if dump else None
 
         def barrier():
             # torch's synchronize first: it covers torch's own streams (idle here: the steps run on
@@ -482,14 +505,32 @@ def run_workload(name, steps_n, warmup, world, dist, lat_steps, timing=True, bat
                 t_step = max(t_step, tim["pair_us"] * 1e-6)
             t_step = reduce_max([t_step], dist, red_dev)[0]
             n_heat = int(min(20000, max(100, np.ceil(heat_ms * 1e-3 / t_step))))
-        bt_cold, _ = timed_batches(lambda: se.run_steps(steps_n), batches, barrier, prime)
-        bt_cold = reduce_max(bt_cold, dist, red_dev)
+        bt_cold = []
+        if cold:
+            bt_cold, _ = timed_batches(lambda: se.run_steps(steps_n), batches, barrier, prime)
+            bt_cold = reduce_max(bt_cold, dist, red_dev)
         heat_prime = prime
         if n_heat:
             heat_prime = (lambda: (se.run_steps(n_heat), se.run_steps(max(1, warmup)))) if prime is not None else \
                 (lambda: se.run_steps(n_heat))
+        if dump:
+            # every batch runs the same steps: after the heat-up (as many steps as its time takes) the warm
+            # start and the step counter of the engine's first step, then the W warmup steps (they also
+            # follow the upload, so the batch still starts on a busy queue), then the timed steps
+            def heat_prime():
+                if n_heat:
+                    se.run_steps(n_heat)
+                eng.set_u_prev(start[0])
+                eng.set_step_counter(start[1])
+                if prime is not None:
+                    prime()
         bt, benq = timed_batches(lambda: se.run_steps(steps_n), batches, barrier, heat_prime)
         bt = reduce_max(bt, dist, red_dev)    # each batch: the slowest rank
+        outputs = None
+        if dump:   # what a caller of run_steps receives after the last timed step (the barrier waited for it)
+            o, u, s = eng.read_outputs()
+            outputs = {"out": o, "u0": u, "u_prev": eng.get_u_prev(), "costs": eng.get_costs(),
+                       "stats": np.array([[x.rho, x.eta, x.ess] for x in s], np.float64)}
         if tim is not None and dist is not None:   # the slowest rank's kernels
             tim["rollout_us_max_over_ranks"], tim["rollout_in_step_us_max_over_ranks"] = reduce_max(
                 [tim["rollout_us"], tim["rollout_in_step_us"]], dist, red_dev)
@@ -531,7 +572,8 @@ def run_workload(name, steps_n, warmup, world, dist, lat_steps, timing=True, bat
                "rccl_nranks": comm[0] if comm else None, "rccl_rank": comm[1] if comm else None,
                "peer_ranks_connected": peer_n, "agree_every": se.agree_every if se.mode == "peer" and world > 1 else None,
                "process_group": ({"backend": dist.get_backend(), "size": dist.get_world_size()} if dist is not None
-                                 else None)}
+                                 else None),
+               "outputs": outputs}
     finally:   # (also when a step is given up or a call raises: the next workload gets a clean device)
         se.engine.close()
     return res
@@ -583,6 +625,24 @@ def measured_hbm(local: int, nbytes: int = 1 << 30, reps: int = 10):
     return out
 
 
+def write_outputs(path: str, arrays: dict) -> dict:
+    """``--dump-outputs``: each array as ``path/<name>.npy`` in its own float type (float64 / float32),
+    DUMP_MAX_BYTES in all; an array over its share of that is written as a fixed sample of its
+    flattened elements (seed 0, ascending positions).  Returns what was written, for the line."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    info = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+        info[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+            info[name]["sampled"] = int(a.size)
+        np.save(os.path.join(path, name + ".npy"), a)
+    return info
+
+
 def auto_batches(steps_n: int) -> int:
     """Timed batches for the median: 7 for short runs (the driver's --steps 20), fewer as
     each batch gets long enough to amortise its brackets."""
@@ -631,7 +691,7 @@ def make_line(workload, r, args, secondary=None, cpu=None, cpu_all=None, measure
                    "basis": "median over the batches; each batch = a GPU heat-up (`heatup_steps_per_batch` back-to-back "
                             "steps, ~15 ms: the clocks' ramp under sustained load, profiles/r04/ramp), `warmup` untimed "
                             "steps, then exactly `steps` control steps bracketed by barrier + synchronize (wall clock), "
-                            "max over ranks; the same batches without the heat-up: ms_per_step_no_heatup"},
+                            "max over ranks; the same batches without the heat-up (--full): ms_per_step_no_heatup"},
         "latency_p50_ms": float(np.median(lat)) if lat.size else None,
         "latency_p99_ms": float(np.percentile(lat, 99)) if lat.size else None,
         "latency_100hz": latency_100hz(r.get("lat100"), lat),
@@ -788,20 +848,30 @@ def main():
     ap.add_argument("--samples", type=int, default=0,
                     help="override the workload's samples per GPU (profiling one launch shape, e.g. the c4 "
                          "rank shape 65536/N on one GPU)")
-    ap.add_argument("--latency-steps", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="every figure beside the headline: kernel times and roofline, batches without the heat-up, "
+                         "latency legs, secondary workloads, CPU baseline, measured HBM bandwidth (default: only "
+                         "set-up, warmup and the timed batches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (out, u0, u_prev, costs, stats) as DIR/<name>.npy; "
+                         "every batch's warmup then starts from the engine's first-step inputs (one GPU)")
+    ap.add_argument("--latency-steps", type=int, default=200, help="calls per latency leg of a --full run; 0: none")
     ap.add_argument("--cpu-budget", type=float, default=2.5, help="seconds of CPU sampling per baseline cell")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="a --full run without the CPU baseline")
     ap.add_argument("--no-kernel-timing", action="store_true",
-                    help="skip the event-timed kernel loops (profiler runs: the trace then holds only the "
-                         "control steps); no roofline in the line")
+                    help="a --full run without the event-timed kernel loops (no roofline in the line, and no "
+                         "secondary workloads)")
     ap.add_argument("--no-numa-bind", action="store_true",
                     help="leave the process's CPU affinity alone (default: bind to the GPU's local CPUs)")
     ap.add_argument("--secondary", default="drone_c2,wholebody_c4,c4_shard_native1,c4_shard_peer1,c4,fleet_c5,"
                                            "fleet_c5_share,quadrotor_c2",
-                    help="extra workloads reported at N=1, comma separated; '' for none")
+                    help="extra workloads a --full run reports at N=1, comma separated; '' for none")
     ap.add_argument("--secondary-multi", default="c4,c4_rccl,fleet_c5",
-                    help="extra workloads reported at N>1 (every rank runs them), comma separated; '' for none")
+                    help="extra workloads a --full run reports at N>1 (every rank runs them), comma separated; "
+                         "'' for none")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        raise SystemExit("bench.py: --dump-outputs writes one GPU's outputs (--gpus 1)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # N ranks from one command: the ranks run as a child (torch.distributed.run), this process
         # relays rank 0's line and exits with the child's code (nothing here has touched the GPU)
@@ -855,20 +925,23 @@ def main():
     if args.samples:
         WORKLOADS[workload] = dict(WORKLOADS[workload], n_samples=args.samples, strong=False)
     batches = args.batches or auto_batches(args.steps)
-    r = run_workload(workload, args.steps, args.warmup, world, dist, args.latency_steps,
-                     timing=not args.no_kernel_timing, batches=batches, lat_rate_calls=args.latency_steps)
+    lat_steps = args.latency_steps if args.full else 0
+    r = run_workload(workload, args.steps, args.warmup, world, dist, lat_steps,
+                     timing=args.full and not args.no_kernel_timing, batches=batches, lat_rate_calls=lat_steps,
+                     cold=args.full, dump=bool(args.dump_outputs))
     r["ranks_per_gpu"] = ranks_per_gpu
-    extra = args.secondary if world == 1 else args.secondary_multi
+    dumped = write_outputs(args.dump_outputs, r["outputs"]) if args.dump_outputs else None
+    extra = (args.secondary if world == 1 else args.secondary_multi) if args.full else ""
     secondary = {}
     if extra and r["tim"] is not None:
         secondary = run_secondaries([s for s in extra.split(",") if s and s != workload], args.steps, world, dist,
                                     ranks_per_gpu)
     dropin = None
-    if world == 1 and workload == "arm_c3" and args.latency_steps:
+    if world == 1 and workload == "arm_c3" and lat_steps:
         dropin = guarded("drop-in latency", lambda: dropin_latency(args.latency_steps))
         log(f"drop-in latency: {dropin}")
     cpu, cpu_all = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cb = guarded("cpu baseline", lambda: cpu_baseline(workload, args.cpu_budget))
         cpu, cpu_all = (cb, None) if isinstance(cb, dict) else cb   # (a dict: its error)
         log(f"cpu baseline: {cpu}")
@@ -881,6 +954,12 @@ def main():
             log(f"measured HBM: {measured}")
         line = make_line(workload, r, args, secondary, cpu, cpu_all, measured)
         line["host_binding"] = binding
+        line["full"] = args.full
+        if dumped is not None:
+            line["outputs"] = {"dir": args.dump_outputs, "arrays": dumped,
+                               "what": f"after timed step {args.steps} of the last batch; every batch's "
+                                       f"{max(1, args.warmup)} warmup steps start from the engine's first-step "
+                                       "inputs (initial warm start, Philox step counter 0)"}
         if dropin is not None:
             line["dropin_latency"] = dropin
         print(json.dumps(line), file=json_out, flush=True)

@@ -2,7 +2,7 @@
 # GPU runs used with gpurun, one subcommand per job:
 #
 #   scripts/gpu.sh tests    <tag> [pytest files]          GPU test suite (default: all -m gpu tests)
-#   scripts/gpu.sh bench    <tag> [bench.py args]         default bench line + the driver's 20-step shape x2
+#   scripts/gpu.sh bench    <tag> [bench.py args]         the --full bench line + the driver's plain 20-step shape x2
 #   scripts/gpu.sh prof     <tag> [workload ...]          rocprofv3 kernel traces of control steps only,
 #                                                         beside the unprofiled line of the same workload
 #   scripts/gpu.sh final    <tag>                         the round's evidence: tests, bench lines, rocprof of
@@ -46,7 +46,7 @@ run_tests() {   # $1 log, rest: files
 }
 
 bench_lines() {   # the default line and the driver's 20-step shape
-  timeout -k 10 400 python bench.py "$@" > $out/bench_default.json 2> $out/bench_default.err \
+  timeout -k 10 400 python bench.py --full "$@" > $out/bench_default.json 2> $out/bench_default.err \
       || fail bench $? $out/bench_default.err
   head -c 700 $out/bench_default.json; echo
   for i in 1 2; do
@@ -58,7 +58,7 @@ bench_lines() {   # the default line and the driver's 20-step shape
 
 prof_steps() {   # $1 workload: rocprofv3 of control steps only (no event-timed loops in the trace)
   local w=$1
-  timeout -k 10 300 python bench.py --workload $w --no-cpu-baseline --secondary "" --latency-steps 0 --steps 500 \
+  timeout -k 10 300 python bench.py --full --workload $w --no-cpu-baseline --secondary "" --latency-steps 0 --steps 500 \
       --warmup 50 > $out/bench_$w.json 2> $out/bench_$w.err || fail "bench $w" $? $out/bench_$w.err
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $out/profsteps_$w -o run -- \
       python3 bench.py --workload $w --no-cpu-baseline --secondary "" --latency-steps 0 --no-kernel-timing \
@@ -82,13 +82,13 @@ peer2() {   # the N>1 bench path through the peer exchange, 2 ranks on this one 
             # only the handle all-gather, the probe's barriers and the timing reductions)
   MPPI_DIST_BACKEND=gloo MPPI_EXCHANGE=peer timeout -k 10 300 python -m torch.distributed.run --nnodes=1 \
       --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 2 --steps 50 --warmup 10 \
-      --latency-steps 20 > $out/bench_peer2.json 2> $out/bench_peer2.err || fail "peer rehearsal" $? $out/bench_peer2.err
+      --full --latency-steps 20 > $out/bench_peer2.json 2> $out/bench_peer2.err || fail "peer rehearsal" $? $out/bench_peer2.err
   python3 -c "import json;d=json.load(open('$out/bench_peer2.json'));m=d['multi_gpu'];c=(d.get('secondary') or {}).get('c4') or {};print('peer2', d['config']['workload'], d['config']['parallelism'], 'step %.2f us'%(d['ms_per_step']*1e3), m['exchange'], m['native_comm_error'], '| c4', c.get('exchange'), ('step %.2f us'%(c.get('ms_per_step', 0)*1e3)) if c else None, '| fleet_c5', {k: f.get(k) for k in ('n_gpus', 'exchange', 'vehicles_per_gpu', 'vehicles_total', 'ms_per_step', 'value')} if (f := (d.get('secondary') or {}).get('fleet_c5')) else None)"
 }
 
 gpus2() {   # the N>1 bench line from ONE plain command: bench.py starts the 2 ranks itself (a child
            # torch.distributed.run; 2 ranks on this one GPU: gloo process group, peer exchange)
-  timeout -k 10 600 python bench.py --gpus 2 --steps 50 --warmup 10 --latency-steps 20 > $out/bench_gpus2.json \
+  timeout -k 10 600 python bench.py --gpus 2 --full --steps 50 --warmup 10 --latency-steps 20 > $out/bench_gpus2.json \
       2> $out/bench_gpus2.err || fail "bench --gpus 2" $? $out/bench_gpus2.err
   python3 -c "import json;d=json.load(open('$out/bench_gpus2.json'));m=d['multi_gpu'];print('gpus2 n_gpus', d['n_gpus'], m['exchange'], 'peer_ranks_connected', m['peer_ranks_connected'], m['process_group'], {k: (v.get('exchange'), v.get('rccl_nranks'), v.get('peer_ranks_connected'), (v.get('native_comm_error') or '')[:60]) for k, v in (d.get('secondary') or {}).items()})"
 }
@@ -104,7 +104,7 @@ final)
   run_tests $out/gpu_tests.log
   bench_lines
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $out/prof_bench -o run -- \
-      python3 bench.py --steps 500 --warmup 50 --no-cpu-baseline --secondary "" --latency-steps 100 \
+      python3 bench.py --full --steps 500 --warmup 50 --no-cpu-baseline --secondary "" --latency-steps 100 \
       > $out/prof_bench.json 2> $out/prof_bench.err || fail "rocprof bench" $? $out/prof_bench.err
   gpus2
   echo "final done" ;;
@@ -134,7 +134,7 @@ pmc)
              "${PMC_EXTRA:-SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES SQ_BUSY_CYCLES}" "FETCH_SIZE" "WRITE_SIZE"; do
     i=$((i+1))
     timeout -s KILL 120 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $out/p$i -o run -- \
-        python3 bench.py --steps 100 --warmup 10 --latency-steps 0 --no-cpu-baseline --secondary "" "$@" \
+        python3 bench.py --full --steps 100 --warmup 10 --latency-steps 0 --no-cpu-baseline --secondary "" "$@" \
         > $out/p$i.json 2> $out/p$i.err || fail "pass $i ($grp)" $? $out/p$i.err
     echo "pass $i ($grp) ok"
   done
@@ -147,7 +147,7 @@ traffic)
     mkdir -p $d
     for c in FETCH_SIZE WRITE_SIZE; do   # the two cannot share a pass
       timeout -s KILL 240 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $d/$c -o run -- \
-          python3 bench.py --workload $w ${k:+--samples $k} --steps 100 --warmup 10 --latency-steps 0 \
+          python3 bench.py --full --workload $w ${k:+--samples $k} --steps 100 --warmup 10 --latency-steps 0 \
           --no-cpu-baseline --secondary "" > $d/$c.json 2> $d/$c.err || fail "$spec $c" $? $d/$c.err
       echo "$spec $c ok"
     done

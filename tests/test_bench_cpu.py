@@ -258,13 +258,21 @@ sys.path.insert(0, TESTS)
 import bench
 from test_bench_cpu import _fake_result
 
-def fake_run(name, steps_n, warmup, world, dist, lat_steps, timing=True, batches=1, lat_rate_calls=0):
+def fake_run(name, steps_n, warmup, world, dist, lat_steps, timing=True, batches=1, lat_rate_calls=0,
+             cold=True, dump=False):
+    CALLS.append((name, lat_steps, timing, lat_rate_calls, cold, dump))
     if name == "drone_c2":
         raise RuntimeError("secondary boom")
     r = _fake_result(1, 0, model="arm", K=4096, H=32)
     r.update(A=7, strong=False, bytes=4096 * 32 * 76 + 4 * 4096, state_f64=True, exchange=None, native=False)
     r["dt"] = float(np.median(r["batches_s"]))
+    if not timing:
+        r["tim"] = None
+    if not lat_steps:
+        r["lat"] = []
     return r
+
+CALLS = []
 
 def boom():
     raise OSError("no host sampling here")
@@ -273,31 +281,85 @@ bench.run_workload = fake_run
 bench.dropin_latency = lambda n: boom()
 bench.cpu_baseline = lambda w, b: boom()
 bench.measured_hbm = lambda local: {"fill_GBps": 5000.0}
-sys.argv = ["bench.py", "--steps", "20", "--warmup", "5", "--no-numa-bind", "--secondary", "drone_c2,wholebody_c4"]
+sys.argv = ["bench.py", "--steps", "20", "--warmup", "5", "--no-numa-bind", "--secondary", "drone_c2,wholebody_c4"] + EXTRA
 bench.main()
+print("CALLS", json.dumps(CALLS), file=sys.stderr)
 """
 
 
-def test_main_prints_one_line_when_parts_fail(tmp_path):
-    """bench.main() at N = 1 with a secondary, the drop-in latency and the CPU baseline all failing
-    (stand-ins for the GPU workloads, run in a child: main() re-points fd 1): still exactly one JSON
-    line on stdout, the failures named in it, the primary's numbers intact."""
+def _run_main_stub(extra):
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
-    code = f"ROOT = {os.path.dirname(here)!r}\nTESTS = {here!r}\n" + _MAIN_STUB
+    code = f"import json\nROOT = {os.path.dirname(here)!r}\nTESTS = {here!r}\nEXTRA = {extra!r}\n" + _MAIN_STUB
     p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300,
                        cwd=os.path.dirname(here))
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout
-    line = json.loads(lines[0])
+    calls = [json.loads(ln[6:]) for ln in p.stderr.splitlines() if ln.startswith("CALLS ")]
+    return json.loads(lines[0]), calls[0]
+
+
+def test_main_prints_one_line_when_parts_fail(tmp_path):
+    """bench.main() --full at N = 1 with a secondary, the drop-in latency and the CPU baseline all
+    failing (stand-ins for the GPU workloads, run in a child: main() re-points fd 1): still exactly
+    one JSON line on stdout, the failures named in it, the primary's numbers intact."""
+    line, calls = _run_main_stub(["--full"])
+    assert calls[0] == ["arm_c3", 200, True, 200, True, False] and len(calls) == 3
+    assert line["full"] is True
     assert line["config"]["workload"] == "arm_c3" and line["value"] > 0
     assert line["secondary"]["drone_c2"] == {"error": "RuntimeError: secondary boom"}
     assert line["secondary"]["wholebody_c4"]["value"] > 0
     assert line["dropin_latency"]["error"].startswith("OSError")
     assert line["cpu_baseline"]["error"].startswith("OSError") and line["cpu_baseline_all"] is None
     assert line["roofline"]["peak_measured"] == {"fill_GBps": 5000.0}
+
+
+def test_plain_main_runs_only_the_headline():
+    """Without --full main() measures the primary workload's timed batches and nothing else: one
+    run_workload call with the kernel loops, the batches without the heat-up and the latency legs
+    off; no secondary, drop-in latency, CPU baseline or HBM fill (the stand-ins would report their
+    errors in the line); the headline fields are built as in a --full line."""
+    line, calls = _run_main_stub([])
+    assert calls == [["arm_c3", 0, False, 0, False, False]]
+    assert line["full"] is False and line["steps"] == 20 and line["warmup"] == 5
+    assert line["unit"] == "rollout-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["value"] == pytest.approx(4096 * 32 / (line["ms_per_step"] * 1e-3))
+    assert line["timing"]["steps_per_batch"] == 20 and len(line["timing"]["ms_per_step_batches"]) == 7
+    for k in ("secondary", "cpu_baseline", "cpu_baseline_all", "roofline", "kernels", "latency_p50_ms",
+              "latency_100hz", "latency_100hz_prewarm"):
+        assert line[k] is None, k
+    assert "dropin_latency" not in line and "outputs" not in line
+    full, _ = _run_main_stub(["--full"])
+    assert line["metric"] == full["metric"] and line["ms_per_step"] == full["ms_per_step"]
+
+
+def test_write_outputs(tmp_path):
+    """--dump-outputs: one .npy per array in float64 / float32, within the size limit in all; an
+    array over its share is a fixed sample (the same elements on every run)."""
+    arrays = {"out": np.arange(14.0).reshape(1, 14), "u0": np.arange(7, dtype=np.float32).reshape(1, 7),
+              "costs": np.arange(5000, dtype=np.float32).reshape(1, 5000)}
+    info = bench.write_outputs(str(tmp_path / "a"), arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == ["costs.npy", "out.npy", "u0.npy"]
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == a.dtype and np.array_equal(got, a)
+        assert info[k] == {"shape": list(a.shape), "dtype": str(a.dtype)}
+    old = bench.DUMP_MAX_BYTES
+    bench.DUMP_MAX_BYTES = 3 * 4000
+    try:
+        info = bench.write_outputs(str(tmp_path / "b"), arrays)
+        again = bench.write_outputs(str(tmp_path / "c"), arrays)
+    finally:
+        bench.DUMP_MAX_BYTES = old
+    got = np.load(tmp_path / "b" / "costs.npy")
+    assert info["costs"]["sampled"] == 1000 and got.shape == (1000,) and got.dtype == np.float32
+    assert np.all(np.diff(got) > 0) and again == info
+    assert np.array_equal(got, np.load(tmp_path / "c" / "costs.npy"))
+    assert "sampled" not in info["out"] and np.array_equal(np.load(tmp_path / "b" / "out.npy"), arrays["out"])
+    total = sum(os.path.getsize(tmp_path / "b" / f) - 128 for f in os.listdir(tmp_path / "b"))
+    assert total <= 3 * 4000
 
 
 _RUN_STUB = r"""
@@ -309,7 +371,7 @@ import bench
 import quadrotor_manipulator_mppi_amd.distributed as D
 
 class Stat:
-    ess = 123.0
+    rho, eta, ess = 1.0, 2.0, 123.0
 
 class FakeEngine:
     def __init__(self, model, K, H, V):
@@ -318,8 +380,13 @@ class FakeEngine:
         self.cfg = types.SimpleNamespace(state_f64=model == "arm", quad_mass=1.0, quad_gravity=9.81)
         self.closed = 0
         self.steps = 0
+        self.resets = []
     def set_target(self, *a, **k): pass
-    def set_u_prev(self, u): pass
+    def set_u_prev(self, u): self.resets.append(("u_prev", self.steps))
+    def get_u_prev(self): return np.zeros((self.V, self.H, self.A), np.float32)
+    def get_step_counter(self): return 0
+    def set_step_counter(self, n): self.resets.append((n, self.steps))
+    def get_costs(self): return np.zeros((self.V, self.K), np.float32)
     def set_state(self, s): assert s.shape[0] == self.V
     def kernel_timing_ex(self, n): return (5.0, 4.0, 9.0)
     def exchange_timing(self, n): return 2.0
@@ -352,6 +419,17 @@ r = bench.run_workload("arm_c3", 20, 5, 1, None, 3, batches=2, lat_rate_calls=2)
 assert r["K"] == 4096 and r["H"] == 32 and len(r["batches_s"]) == 2 and r["ess"] == 123.0, r
 assert r["tim"]["rollout_in_step_us"] == 5.0 and len(r["lat"]) == 3 and len(r["lat100"]) == 2
 assert [e.closed for e in CLOSED] == [1]
+assert r["outputs"] is None and len(r["batches_s_no_heatup"]) == 2 and CLOSED[0].resets == []
+# a plain run that dumps: no kernel loops, no batches without the heat-up, no latency legs; every batch
+# takes the first step's inputs after its heat-up, then runs its 5 warmup and 20 timed steps; the outputs
+# are read after the last batch's last step
+r = bench.run_workload("arm_c3", 20, 5, 1, None, 0, timing=False, batches=2, cold=False, dump=True)
+eng = CLOSED.pop()
+assert r["tim"] is None and r["batches_s_no_heatup"] == [] and len(r["batches_s"]) == 2 and r["lat"] == []
+assert [x[0] for x in eng.resets] == ["u_prev", 0, "u_prev", 0] and eng.steps == eng.resets[-1][1] + 5 + 20
+o = r["outputs"]
+assert sorted(o) == ["costs", "out", "stats", "u0", "u_prev"] and o["stats"].tolist() == [[1.0, 2.0, 123.0]]
+assert o["out"].dtype == np.float64 and o["u_prev"].shape == (1, 32, 7) and o["costs"].shape == (1, 4096)
 FAIL = "wholebody"
 try:
     bench.run_workload("wholebody_c4", 20, 5, 1, None, 0, batches=1)
