@@ -113,7 +113,9 @@ typedef struct {
     uint64_t seed;            /* Philox key                                                     */
     int32_t device;           /* HIP device ordinal                                             */
     int32_t shard_rank;       /* sample sharding: this engine owns global samples               */
-    int32_t shard_count;      /*   [rank*K, (rank+1)*K); partials exchanged by the caller       */
+    int32_t shard_count;      /*   [rank*K, (rank+1)*K); partials exchanged by the caller.      */
+                              /*   shard_count * n_samples <= 2^32: the noise stream counts the  */
+                              /*   global sample in 32 bits (more: MPPI_ERR_INVALID_ARG)         */
     int32_t state_f64;        /* reproduce the reference's fp64 promotion of an fp64 arm state  */
     int32_t store_trajectory; /* write the trajectory buffer (q / p and EE 3x4 per (k,t))       */
     int32_t store_noise;      /* write eps (K,H,A) (debug / parity readback)                    */

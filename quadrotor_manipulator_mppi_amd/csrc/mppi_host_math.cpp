@@ -285,6 +285,12 @@ mppi_status validate(const mppi_config& c) {
     if (!(c.lambda_ > 0.0) || !(c.dt > 0.0)) return fail(MPPI_ERR_INVALID_ARG, "lambda and dt must be > 0");
     if (c.shard_count < 1 || c.shard_rank < 0 || c.shard_rank >= c.shard_count)
         return fail(MPPI_ERR_INVALID_ARG, "shard %d/%d", c.shard_rank, c.shard_count);
+    // the Philox counter word of a sample is its global index as 32 bits (k_rollout's kg): past
+    // 2^32 samples in all, a high shard would redraw a low shard's noise
+    if ((int64_t)c.shard_count * (int64_t)c.n_samples > (int64_t)1 << 32)
+        return fail(MPPI_ERR_INVALID_ARG, "shard_count %d x n_samples %d = %lld samples: the 32-bit sample counter of "
+                    "the noise stream addresses at most 2^32", c.shard_count, c.n_samples,
+                    (long long)c.shard_count * (long long)c.n_samples);
     if (c.vehicle_offset < 0 || c.vehicle_offset + c.n_vehicles > 32768)
         return fail(MPPI_ERR_INVALID_ARG, "vehicle_offset %d: the fleet-wide vehicle index must stay below 32768",
                     c.vehicle_offset);
