@@ -341,7 +341,8 @@ mppi_status mppi_step(mppi_engine* e, const double* state, const float* h_noise,
  * noise, state and warm start resident on the GPU); single-shard engines, shards connected
  * by the peer exchange, or shards with an engine-owned communicator (rollout, PACK,
  * all-reduce, finalize).
- * No host synchronisation: pair with mppi_synchronize / mppi_read_outputs.
+ * No host synchronisation: pair with mppi_synchronize / mppi_read_outputs.  The outputs of a
+ * batch (mppi_read_outputs) are those of its LAST step; its earlier steps need not write any.
  * Single-shard and peer-exchange engines dispatch the steps natively: raw AQL packets on an
  * HSA queue the engine owns, the kernels from the library's code objects, their arguments
  * resident in device memory (MPPI_DISPATCH = auto (default) | aql (required) | hip). */
@@ -357,6 +358,15 @@ mppi_status mppi_run_steps(mppi_engine* e, int32_t n);
  * fails its creation probe: dispatch ids that are not the queue's packet indices, as under a
  * tool that intercepts queues (rocprofv3 --pmc). */
 mppi_status mppi_dispatch_info(mppi_engine* e, char* buf, int32_t len);
+/* Which kernels the last mppi_run_steps and the last mppi_step ran:
+ * "batch: rollout <symbol>, finalize <symbol>, quiet finalize <symbol | none>; call: rollout
+ * <symbol>, finalize <symbol>" ("none" before the first of either), the symbols as the library's
+ * code objects name them.  The outputs of a batch are those of its last step: its earlier steps run
+ * a finalize that updates the warm start and writes nothing else (the quiet finalize) wherever the
+ * library has one for the engine's shape.  An engine created with MPPI_GENERIC_KERNELS=1 in the
+ * environment (tests, A/B) runs the kernels of every shape and the full finalize on every step;
+ * the text then ends in "; MPPI_GENERIC_KERNELS". */
+mppi_status mppi_kernel_info(mppi_engine* e, char* buf, int32_t len);
 
 mppi_status mppi_synchronize(mppi_engine* e);
 

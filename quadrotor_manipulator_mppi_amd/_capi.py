@@ -117,6 +117,7 @@ PROTOTYPES = {
     "mppi_step": (_ST, [_P, _D, _F, _D, _F, C.POINTER(Stats)]),
     "mppi_run_steps": (_ST, [_P, C.c_int32]),
     "mppi_dispatch_info": (_ST, [_P, C.c_char_p, C.c_int32]),
+    "mppi_kernel_info": (_ST, [_P, C.c_char_p, C.c_int32]),
     "mppi_synchronize": (_ST, [_P]),
     "mppi_set_prewarm": (_ST, [_P, C.c_int32]),
     "mppi_get_prewarm": (_ST, [_P, _I32, C.POINTER(C.c_int64)]),

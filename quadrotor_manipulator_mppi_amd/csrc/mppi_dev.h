@@ -129,6 +129,8 @@ struct DevParams {
     // (V, A, ts) words each incremented once per FINAL (FinTail::xovl), and their count per vehicle
     const uint32_t* ovl;
     int32_t ovl_n;
+    int32_t kern;                 // 1: the kernels as before the fixed-block single-group one
+                                  // (MPPI_GENERIC_KERNELS; mppi_rollout.h launch_rollout_x)
 };
 constexpr int kStamps = 16;
 
@@ -234,6 +236,11 @@ struct LaunchDesc {
     alignas(16) unsigned char args[2048];
 };
 
+// FinParams::kern bits (mppi_launch_finalize).  Generic: the kernel of every role with run-time
+// geometry, as before the role kernels (engines created with MPPI_GENERIC_KERNELS=1).  Quiet: this
+// FINAL's outputs are never read (a batch's step before its last): u_prev and nothing else.
+constexpr int32_t kFinKernGeneric = 1, kFinKernQuiet = 2;
+
 // Finalize / pack kernel parameters.
 struct FinParams {
     int32_t model, V, H, A, nq, qoff, state_f64;
@@ -271,6 +278,7 @@ struct FinParams {
     float* wsmooth;          // (V,H,A) readback
     int32_t out_dim;
     int32_t dbg;             // diagnostic phase-skip bits (MPPI_FIN_DEBUG), 0 in production
+    int32_t kern;            // the launcher's kernel choice (kFinKern*), 0 = a role kernel where one applies
     unsigned long long* stamps;   // diagnostic s_memtime stamps (MPPI_STAMPS), else null
     const FinTail* tail;     // device copy of this launch kind's tail parameters
 };

@@ -56,6 +56,16 @@ struct mppi_engine {
     mppi::DevParams batch_p{};
     mppi::FinParams batch_f{};
     mppi::LaunchDesc batch_roll{}, batch_fin{};
+    mppi::LaunchDesc batch_fin_quiet{}; // the quiet FINAL of the batch's steps before its last (the same
+                                        // description as batch_fin where no quiet kernel applies)
+    int generic = 0;                    // MPPI_GENERIC_KERNELS=1 (tests, A/B): the kernels as before the role and
+                                        // fixed-block ones.  Bits: 1 the finalize of every role with run-time
+                                        // geometry, 2 the full FINAL on every step, 4 the rollout of every block
+                                        // size ("finalize", "quiet", "rollout" set one of them; 1 sets all)
+    // the kernels the last batch and the last control call ran (mppi_kernel_info)
+    std::string kern_batch = "none", kern_call = "none";
+    int kern_batch_state = 0;           // kern_batch describes the resident native batch: 1 one step, 2 several
+    bool kern_call_hip = false, kern_call_peer = false;   // kern_call describes the HIP-launched call (as of peer)
     std::vector<double> rec_out;        // a read step's outputs assembled from its tagged records
     std::vector<float> rec_u0, rec_stats;
     std::vector<float> fk_O, fk_ax;     // the joints' origins and unit axes for check_reach's host FK

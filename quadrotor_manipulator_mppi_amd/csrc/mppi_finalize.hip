@@ -83,15 +83,36 @@ constexpr int kMaxRec = 4096;
 // SGPRs (build.py: 14 dwords); the tail's parameters come from the device-resident FinTail
 // (L2-hot across steps), so a FINAL launch of one vehicle reads nothing else of its
 // kernel-argument block.  pk carries the PACK-mode fields and the diagnostic stamps.
-template <int CW, int WIN, int NT>
-__global__ void __launch_bounds__(NT) k_finalize(const float* __restrict__ hdr_base,
-                                                          const float* __restrict__ dat_base,
-                                                          const FinTail* __restrict__ tail,
-                                                          const uint32_t nrec_H, const uint32_t geo,
-                                                          const int32_t hdr_rs, const int32_t d_rs,
-                                                          const int32_t d_as, const int32_t hdr_vs,
-                                                          const int32_t d_vs, const uint32_t seq_arg,
-                                                          const FinParams pk) {
+// Roles (ROLE): the body below is compiled once per role.  kRoleAny is the kernel as it has always
+// been -- one body for FINAL, PACK, READBACK and the peer exchange, the mode read from the tail at
+// run time; k_finalize instantiates it, and every launch the table below does not cover (and every
+// launch of an engine created with MPPI_GENERIC_KERNELS=1) runs it.  The other roles fix the mode at
+// compile time, pin only the tail values their own path reads and contain no other role's code:
+//   kRoleFinal  the step's finalize without the peer exchange
+//   kRoleQuiet  FINAL of a step nobody reads (every step of a native batch but the last): u_prev
+//               and nothing else -- no vehicle constants loaded, no outputs, stats or records
+//   kRolePack   a shard's PACK
+//   kRolePeer   FINAL with the peer exchange (all-or-nothing decision included)
+// READBACK (mppi_get_weighted_noise, off the step's path) stays on kRoleAny.
+enum { kRoleAny = 0, kRoleFinal = 1, kRoleQuiet = 2, kRolePack = 3, kRolePeer = 4 };
+// Geometry (GEO): GeoRt decodes (A, H, tsz, hf, ts) from the packed arguments as before; GeoC fixes
+// them at compile time for the shapes the engine creates (kFinGeo below), so the block map needs no
+// division, the window bounds fold and the first record load issues earlier.
+struct GeoRt { static constexpr bool kStatic = false; static constexpr int A = 0, H = 0, tsz = 0, hf = 0, ts = 0; };
+template <int A_, int H_, int TSZ_, int HF_, int TS_>
+struct GeoC { static constexpr bool kStatic = true; static constexpr int A = A_, H = H_, tsz = TSZ_, hf = HF_, ts = TS_; };
+
+template <int CW, int WIN, int NT, int ROLE, typename GEO>
+__device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, const float* __restrict__ dat_base,
+                                         const FinTail* __restrict__ tail, const uint32_t nrec_H, const uint32_t geo,
+                                         const int32_t hdr_rs, const int32_t d_rs, const int32_t d_as,
+                                         const int32_t hdr_vs, const int32_t d_vs, const uint32_t seq_arg,
+                                         const FinParams& pk) {
+    constexpr bool kAny = ROLE == kRoleAny, kQuiet = ROLE == kRoleQuiet;
+    // what a role's own path reads of the tail (kRoleAny: everything)
+    constexpr bool kOut = kAny || ROLE == kRoleFinal || ROLE == kRolePeer;   // the outputs section
+    constexpr bool kUpd = kOut || kQuiet;                                     // SavGol and the u_prev update
+    constexpr bool kPeer = kAny || ROLE == kRolePeer;                         // the peer exchange
     constexpr int NWV = NT / 64;
     constexpr int ROWS = 64 / CW;          // rows per wave
     constexpr int TR = NWV * ROWS;         // rows per block
@@ -101,9 +122,10 @@ __global__ void __launch_bounds__(NT) k_finalize(const float* __restrict__ hdr_b
     __shared__ float wsg[96];   // wave 0: w over the window + reflected pads (SavGol taps by LDS reads)
     const FinParams& p = pk;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int n = (int)(nrec_H & 0xFFFFu), H = (int)(nrec_H >> 16);
-    const int tsz = (int)(geo & 0xFFu), hf = (int)((geo >> 8) & 0xFFu), ts = (int)((geo >> 16) & 0xFFu);
-    const int A = (int)(geo >> 24);
+    const int n = (int)(nrec_H & 0xFFFFu);
+    const int H = GEO::kStatic ? GEO::H : (int)(nrec_H >> 16);
+    const int tsz = GEO::kStatic ? GEO::tsz : (int)(geo & 0xFFu), hf = GEO::kStatic ? GEO::hf : (int)((geo >> 8) & 0xFFu);
+    const int ts = GEO::kStatic ? GEO::ts : (int)((geo >> 16) & 0xFFu), A = GEO::kStatic ? GEO::A : (int)(geo >> 24);
     // XCD-aware block map: the dispatcher deals blocks round robin over the 8 XCDs (block b
     // on XCD b mod 8).  Dim a lives on XCD a mod X (X = MPPI_FIN_XCDS of them), every slice of
     // it too: the slices read the same record lines (one 128 B line holds 32 t of a row),
@@ -142,7 +164,7 @@ __global__ void __launch_bounds__(NT) k_finalize(const float* __restrict__ hdr_b
     // scalar round trips).  The empty asm makes every value opaque, so it is neither
     // re-loaded later nor sunk to its use.
     float coef = 0.0f, dt = 0.0f, dt2 = 0.0f;
-    int32_t mode = 0, model = 0, qoff = 0, nq = 0, sf64 = 0, odim = 0;
+    int32_t mode = (ROLE == kRolePack) ? 1 : 0, model = 0, qoff = 0, nq = 0, sf64 = 0, odim = 0;
     const uint32_t seq = seq_arg;
     // native control calls (mppi_aql.cpp): the step's sequence number travels with the vehicle
     // constants (VehicleConst::_pad[0], written by the host into the rollout's arguments, handed
@@ -164,45 +186,75 @@ __global__ void __launch_bounds__(NT) k_finalize(const float* __restrict__ hdr_b
     auto pin_tail = [&]() {
         // every load issues first, then two empty asms consume them (one wait): pinned one
         // by one, each load was followed by its own s_waitcnt, ~20 serial round trips
-        coef = T.coef; dt = T.dt; dt2 = T.dt2;
-        mode = T.mode; model = T.model; qoff = T.qoff; nq = T.nq; sf64 = T.state_f64; odim = T.out_dim;
-        wraw = T.wraw; wsmooth = T.wsmooth; u0p = T.u0; stats = T.stats; outp = T.out; flags = T.flags;
-        up = T.u_prev; vcb = T.vc;
-        xpeers = T.xpeers; xlocal = T.xlocal; xn = T.xn; xme = T.xme; xovl = T.xovl; xstall = T.xstall; xdec = T.xdec;
-        if constexpr (WIN > 0) {
+        // (a fixed role pins only what its own path reads; the rest keep their constants above)
+        coef = T.coef;
+        if constexpr (kAny) {
+            dt = T.dt; dt2 = T.dt2;
+            mode = T.mode; model = T.model; qoff = T.qoff; nq = T.nq; sf64 = T.state_f64; odim = T.out_dim;
+            wraw = T.wraw; wsmooth = T.wsmooth; u0p = T.u0; stats = T.stats; outp = T.out; flags = T.flags;
+            up = T.u_prev; vcb = T.vc;
+            xpeers = T.xpeers; xlocal = T.xlocal; xn = T.xn; xme = T.xme; xovl = T.xovl; xstall = T.xstall; xdec = T.xdec;
+        } else {
+            if constexpr (kOut) {
+                dt = T.dt; dt2 = T.dt2;
+                model = T.model; qoff = T.qoff; nq = T.nq; sf64 = T.state_f64; odim = T.out_dim;
+                u0p = T.u0; stats = T.stats; outp = T.out; flags = T.flags; vcb = T.vc;
+            }
+            if constexpr (kUpd) up = T.u_prev;
+            if constexpr (ROLE == kRolePeer) {
+                xpeers = T.xpeers; xlocal = T.xlocal; xn = T.xn; xme = T.xme; xstall = T.xstall; xdec = T.xdec;
+            }
+        }
+        if constexpr (WIN > 0 && kUpd) {
 #pragma unroll
             for (int j = 0; j < WIN; ++j) sg[j] = T.sg[j];
         }
-        asm volatile("" : "+s"(coef), "+s"(dt), "+s"(dt2), "+s"(mode), "+s"(model), "+s"(qoff), "+s"(nq),
-                          "+s"(sf64), "+s"(odim), "+s"(wraw), "+s"(wsmooth), "+s"(u0p), "+s"(stats),
-                          "+s"(outp), "+s"(flags), "+s"(up), "+s"(vcb), "+s"(xpeers), "+s"(xlocal), "+s"(xn),
-                          "+s"(xme), "+s"(xovl), "+s"(xstall), "+s"(xdec));
-        if constexpr (WIN == 9)
+        if constexpr (kAny)
+            asm volatile("" : "+s"(coef), "+s"(dt), "+s"(dt2), "+s"(mode), "+s"(model), "+s"(qoff), "+s"(nq),
+                              "+s"(sf64), "+s"(odim), "+s"(wraw), "+s"(wsmooth), "+s"(u0p), "+s"(stats),
+                              "+s"(outp), "+s"(flags), "+s"(up), "+s"(vcb), "+s"(xpeers), "+s"(xlocal), "+s"(xn),
+                              "+s"(xme), "+s"(xovl), "+s"(xstall), "+s"(xdec));
+        else if constexpr (kOut) {
+            asm volatile("" : "+s"(coef), "+s"(dt), "+s"(dt2), "+s"(model), "+s"(qoff), "+s"(nq), "+s"(sf64),
+                              "+s"(odim), "+s"(u0p), "+s"(stats), "+s"(outp), "+s"(flags), "+s"(up), "+s"(vcb));
+            if constexpr (ROLE == kRolePeer)
+                asm volatile("" : "+s"(xpeers), "+s"(xlocal), "+s"(xn), "+s"(xme), "+s"(xstall), "+s"(xdec));
+        } else if constexpr (kQuiet)
+            asm volatile("" : "+s"(coef), "+s"(up));
+        else
+            asm volatile("" : "+s"(coef));
+        if constexpr (WIN == 9 && kUpd)
             asm volatile("" : "+s"(sg[0]), "+s"(sg[1]), "+s"(sg[2]), "+s"(sg[3]), "+s"(sg[4]), "+s"(sg[5]),
                               "+s"(sg[6]), "+s"(sg[7]), "+s"(sg[8]));
-        else if constexpr (WIN == 5)
+        else if constexpr (WIN == 5 && kUpd)
             asm volatile("" : "+s"(sg[0]), "+s"(sg[1]), "+s"(sg[2]), "+s"(sg[3]), "+s"(sg[4]));
         // then the loads that need those pointers (global address space: a flat load also
         // counts in lgkmcnt, so every later scalar wait would wait for it too)
-        up += (size_t)v * H * A;
-        // (device-scope loads: the previous finalize's u_prev, the rollout's handed-over vc)
-        if (wv == 0 && q < W && g == 0) u_old = ld_dev(up + (w0 + q) * A + a);
-        if (tid == 0 && sl == 0) {
-            const VehicleConst* vcp = vcb + v;
-            x0f = ld_dev(vcp->pos0f + a); v0f = ld_dev(vcp->vel0f + a);
-            x0d = ld_dev(vcp->pos0 + a); v0d = ld_dev(vcp->vel0 + a);
-            if (seq == kSeqFromVc) seqv = ld_dev((const uint32_t*)vcp->_pad);   // (its bits)
+        if constexpr (kUpd) {
+            up += (size_t)v * H * A;
+            // (device-scope loads: the previous finalize's u_prev, the rollout's handed-over vc)
+            if (wv == 0 && q < W && g == 0) u_old = ld_dev(up + (w0 + q) * A + a);
         }
-        if (tid == 0 && xpeers) {   // the exchange's tag: the step's counter and the exchange epoch
-            xstep = ld_dev((const uint32_t*)(vcb + v) + kVcStepWord);
-            xep = ld_dev((const uint32_t*)(vcb + v) + kVcEpochWord);
+        if constexpr (kOut) {
+            if (tid == 0 && sl == 0) {
+                const VehicleConst* vcp = vcb + v;
+                x0f = ld_dev(vcp->pos0f + a); v0f = ld_dev(vcp->vel0f + a);
+                x0d = ld_dev(vcp->pos0 + a); v0d = ld_dev(vcp->vel0 + a);
+                if (seq == kSeqFromVc) seqv = ld_dev((const uint32_t*)vcp->_pad);   // (its bits)
+            }
         }
-        // every rank's region address, one per lane, loaded here so it lands during the record fold:
-        // loaded per rank inside the store loop, each pointer load's wait also waited for the
-        // previous rank's system-scope stores to complete (vmcnt counts stores): G - 1 serial
-        // remote-store completions before the poll could even start
-        if (wv == 0 && xpeers)
-            xpl = ((const __attribute__((address_space(1))) unsigned long long*)xpeers)[lane < xn ? lane : 0];
+        if constexpr (kPeer) {
+            if (tid == 0 && xpeers) {   // the exchange's tag: the step's counter and the exchange epoch
+                xstep = ld_dev((const uint32_t*)(vcb + v) + kVcStepWord);
+                xep = ld_dev((const uint32_t*)(vcb + v) + kVcEpochWord);
+            }
+            // every rank's region address, one per lane, loaded here so it lands during the record fold:
+            // loaded per rank inside the store loop, each pointer load's wait also waited for the
+            // previous rank's system-scope stores to complete (vmcnt counts stores): G - 1 serial
+            // remote-store completions before the poll could even start
+            if (wv == 0 && xpeers)
+                xpl = ((const __attribute__((address_space(1))) unsigned long long*)xpeers)[lane < xn ? lane : 0];
+        }
     };
     // running softmin per lane.  The header terms (rho, eta, eta2, nan) are the same for every
     // column of a row group, so each lane carries them and the wave fold runs over row groups
@@ -306,7 +358,7 @@ __global__ void __launch_bounds__(NT) k_finalize(const float* __restrict__ hdr_b
     }
     FSTAMP(3);
     bool xlate = false;   // the peer exchange gave the step up: this step keeps the warm start (w_eps = 0)
-    if (xpeers != nullptr && mode != 1) {
+    if (kPeer && xpeers != nullptr && mode != 1) {
         // Peer exchange (sharded V == 1 engines, mppi_dev.h kXW): this block's partial goes to every
         // other rank's region (a FINAL only; READBACK re-reads the last step's), then the other
         // ranks' partials of this block come back from this rank's region, each 8 B word valid once
@@ -535,7 +587,7 @@ __global__ void __launch_bounds__(NT) k_finalize(const float* __restrict__ hdr_b
         if (!(MPPI_FIN_KO & 32))   // (32: timing knockout, u_prev not written)
             __hip_atomic_store(up + t * A + a, un, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (!(MPPI_FIN_KO & 2) && sl == 0 && lane == 0) {   // t = 0 lives in lane 0 of slice 0: outputs into mapped host memory
+    if (kOut && !(MPPI_FIN_KO & 2) && sl == 0 && lane == 0) {   // t = 0 lives in lane 0 of slice 0: outputs into mapped host memory
 #pragma clang fp contract(off)
         const float u0 = un;
         const float uold0 = u_old;
@@ -609,6 +661,52 @@ __global__ void __launch_bounds__(NT) k_finalize(const float* __restrict__ hdr_b
         __hip_atomic_fetch_add(xovl + ((size_t)v * A + a) * ts + sl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The kernel of every role and geometry, as it has always been (kRoleAny, GeoRt).
+template <int CW, int WIN, int NT>
+__global__ void __launch_bounds__(NT) k_finalize(const float* __restrict__ hdr_base,
+                                                          const float* __restrict__ dat_base,
+                                                          const FinTail* __restrict__ tail,
+                                                          const uint32_t nrec_H, const uint32_t geo,
+                                                          const int32_t hdr_rs, const int32_t d_rs,
+                                                          const int32_t d_as, const int32_t hdr_vs,
+                                                          const int32_t d_vs, const uint32_t seq_arg,
+                                                          const FinParams pk) {
+    fin_body<CW, WIN, NT, kRoleAny, GeoRt>(hdr_base, dat_base, tail, nrec_H, geo, hdr_rs, d_rs, d_as, hdr_vs, d_vs,
+                                           seq_arg, pk);
+}
+
+// The geometries the engine creates with its default slices (mppi_engine.cpp: tsz = 8) and each
+// model's default SavGol window (9 taps for the arm and the whole-body, 5 for the drone and the
+// quadrotor), by table index GID: (A, H, tsz, hf, ts).  All have W = tsz + 2 hf <= 16 columns (CW
+// = 16).  nrec stays a run-time argument (any K), and with it the block size NT.
+template <int GID> struct FinGeo;
+template <> struct FinGeo<1> { typedef GeoC<7, 32, 8, 4, 4> type; static constexpr int win = 9; };    // arm
+template <> struct FinGeo<2> { typedef GeoC<3, 32, 8, 2, 4> type; static constexpr int win = 5; };    // drone
+template <> struct FinGeo<3> { typedef GeoC<4, 32, 8, 2, 4> type; static constexpr int win = 5; };    // quadrotor
+template <> struct FinGeo<4> { typedef GeoC<10, 64, 8, 4, 8> type; static constexpr int win = 9; };   // whole-body
+constexpr int kFinGeoCW = 16;
+static int fin_geo_id(const FinParams* p) {
+    if (p->tsz != 8 || p->half != p->window / 2 || p->ts * 8 != p->H) return 0;
+    if (p->window == 9) return (p->H == 32 && p->A == 7) ? 1 : (p->H == 64 && p->A == 10) ? 4 : 0;
+    if (p->window == 5) return (p->H == 32 && p->A == 3) ? 2 : (p->H == 32 && p->A == 4) ? 3 : 0;
+    return 0;
+}
+
+// One role, one table geometry: the same arguments as k_finalize (geo and the H half of nrec_H are
+// passed and not read).
+template <int NT, int ROLE, int GID>
+__global__ void __launch_bounds__(NT) k_finalize_s(const float* __restrict__ hdr_base,
+                                                            const float* __restrict__ dat_base,
+                                                            const FinTail* __restrict__ tail,
+                                                            const uint32_t nrec_H, const uint32_t geo,
+                                                            const int32_t hdr_rs, const int32_t d_rs,
+                                                            const int32_t d_as, const int32_t hdr_vs,
+                                                            const int32_t d_vs, const uint32_t seq_arg,
+                                                            const FinParams pk) {
+    fin_body<kFinGeoCW, FinGeo<GID>::win, NT, ROLE, typename FinGeo<GID>::type>(hdr_base, dat_base, tail, nrec_H, geo, hdr_rs,
+                                                                          d_rs, d_as, hdr_vs, d_vs, seq_arg, pk);
+}
+
 // Native dispatch's check of its one assumption (mppi_aql.cpp step_create): the dispatch id the
 // waves receive is the packet's index in the engine's queue.  A tool that intercepts the queue
 // (a profiler's counter packets) would break it, and with it the rollout's step counter.
@@ -671,7 +769,44 @@ extern "C" int mppi_launch_finalize(const FinParams* p, void* stream) {
         if (c * 16 / cw >= p->nrec) { nt = c; break; }
     const dim3 grid(8 * ((p->A + MPPI_FIN_XCDS - 1) / MPPI_FIN_XCDS) * p->ts, p->V), block(nt);   // XCD-aware map (k_finalize)
     hipStream_t s = (hipStream_t)stream;
-#define MPPI_FIN_GO(CWV, WINV, NTV)                                                                       \
+    // A role kernel at a table geometry where one applies; else (other geometries, READBACK, the
+    // overlap experiment's counters, MPPI_GENERIC_KERNELS) the kernel of every role below.  The quiet
+    // FINAL is the caller's choice (FinParams::kern); a peer-exchange FINAL has no quiet form.
+    const int gid = ((p->kern & kFinKernGeneric) || p->xovl) ? 0 : fin_geo_id(p);
+    const int role = !gid ? kRoleAny
+                     : p->mode == 1 ? kRolePack
+                     : p->mode != 0 ? kRoleAny
+                     : p->xpeers ? kRolePeer
+                     : (p->kern & kFinKernQuiet) ? kRoleQuiet : kRoleFinal;
+#define MPPI_FIN_SGO(NTV, ROLEV, GIDV)                                                                    \
+    return go(k_finalize_s<NTV, ROLEV, GIDV>,                                                             \
+              [](char* b, size_t n) {                                                                     \
+                  snprintf(b, n, "_Z12k_finalize_sILi%dELi%dELi%dEEvPKfS1_PKN4mppi7FinTailEjjiiiiijNS2_9FinParamsE", \
+                           NTV, ROLEV, GIDV);                                                             \
+              },                                                                                          \
+              grid, block, 0, s, p->hdr, p->dat, p->tail, nh, geo, (int32_t)p->hdr_rs, (int32_t)p->d_rs,   \
+              (int32_t)p->d_as, (int32_t)p->hdr_vs, (int32_t)p->d_vs, p->seq, *p)
+#define MPPI_FIN_SNT(ROLEV, GIDV)                                                                         \
+    do {                                                                                                  \
+        if (nt == 128) MPPI_FIN_SGO(128, ROLEV, GIDV);                                                    \
+        else if (nt == 256) MPPI_FIN_SGO(256, ROLEV, GIDV);                                               \
+        else MPPI_FIN_SGO(512, ROLEV, GIDV);                                                              \
+    } while (0)
+#define MPPI_FIN_SGEO(ROLEV)                                                                              \
+    do {                                                                                                  \
+        if (gid == 1) MPPI_FIN_SNT(ROLEV, 1);                                                             \
+        else if (gid == 2) MPPI_FIN_SNT(ROLEV, 2);                                                        \
+        else if (gid == 3) MPPI_FIN_SNT(ROLEV, 3);                                                        \
+        else MPPI_FIN_SNT(ROLEV, 4);                                                                      \
+    } while (0)
+    if (role == kRoleFinal) MPPI_FIN_SGEO(kRoleFinal);
+    else if (role == kRoleQuiet) MPPI_FIN_SGEO(kRoleQuiet);
+    else if (role == kRolePack) MPPI_FIN_SGEO(kRolePack);
+    else if (role == kRolePeer) MPPI_FIN_SGEO(kRolePeer);
+#undef MPPI_FIN_SGEO
+#undef MPPI_FIN_SNT
+#undef MPPI_FIN_SGO
+#define MPPI_FIN_GO(CWV, WINV, NTV)                                                                      \
     return go(k_finalize<CWV, WINV, NTV>,                                                                 \
               [](char* b, size_t n) {                                                                     \
                   snprintf(b, n, "_Z10k_finalizeILi%dELi%dELi%dEEvPKfS1_PKN4mppi7FinTailEjjiiiiijNS2_9FinParamsE", \

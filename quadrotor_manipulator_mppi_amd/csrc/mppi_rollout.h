@@ -673,13 +673,23 @@ __device__ __forceinline__ void integrate_lds(const float (&act)[NA], float* xw,
 // arm kernel would spill at 64 and keeps the 4-wave budget -- C3 runs 2 waves per SIMD).  At the C4 shard
 // (whole-body K=8192 H=64) that is 1024 blocks x 8 waves, all resident at once: twice the
 // latency hiding of 512 blocks x 2 groups, and no wave left alone in the grid's tail.
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG>
-__global__ void __launch_bounds__(512, (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH == 2 ? (XC ? MPPI_ROLL_OCC_NCH2_XC : MPPI_ROLL_OCC_NCH2) : (XC ? MPPI_ROLL_OCC_XC : MPPI_ROLL_OCC))) k_rollout(const uint32_t seed_lo, const uint32_t seed_hi,
-                                                 const uint32_t step_arg, const uint32_t k_off,
-                                                 const int32_t noise_arg, const int32_t H_arg,
-                                                 const int32_t geo_arg,
-                                                 const float* __restrict__ u_prev,
-                                                 const JointDev* __restrict__ jtab, const DevParams pk) {
+// B512 (k_rollout_s, ONEG only): the block is 512 threads and the launch is a plain one (no overlap
+// wait), both known at compile time: one u_prev load per 512 warm-start words the shape can have
+// instead of four, one joint-table load instead of two, and the loops that only a smaller block or
+// a longer warm start needs (the staging tails, the absent waves' fill) and the overlap poll are
+// not in the instantiation.  The launcher picks it when all of that holds (launch_rollout_x).
+template <int NCH, bool F64, bool XC, bool ONEG>
+constexpr int roll_occ() {
+    return (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH == 2 ? (XC ? MPPI_ROLL_OCC_NCH2_XC : MPPI_ROLL_OCC_NCH2) : (XC ? MPPI_ROLL_OCC_XC : MPPI_ROLL_OCC));
+}
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG, bool B512>
+__device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint32_t seed_hi,
+                                             const uint32_t step_arg, const uint32_t k_off,
+                                             const int32_t noise_arg, const int32_t H_arg,
+                                             const int32_t geo_arg,
+                                             const float* __restrict__ u_prev,
+                                             const JointDev* __restrict__ jtab, const DevParams& pk) {
+    static_assert(!B512 || ONEG, "the fixed-block body is a single-group one");
     constexpr int R = 64 / LSEG;
     constexpr int QOFF = (MODEL == MPPI_MODEL_WHOLEBODY) ? 3 : 0;
     constexpr int NQ = (MODEL == MPPI_MODEL_DRONE) ? 0 : NA - QOFF;
@@ -694,7 +704,7 @@ __global__ void __launch_bounds__(512, (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH 
     const int v = blockIdx.y;
     // block size and groups per block as one preloaded argument (threads | iters << 16): blockDim
     // would be an implicit-argument s_load, p.iters a kernel-argument one
-    const int nthr = geo_arg & 0xFFFF, iters = ONEG ? 1 : (geo_arg >> 16);
+    const int nthr = B512 ? 512 : (geo_arg & 0xFFFF), iters = ONEG ? 1 : (geo_arg >> 16);
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nw = nthr >> 6;
     const int sub = lane / LSEG, t0 = lane & (LSEG - 1);
     const int32_t noise_mode = noise_arg & 0xFF;
@@ -709,25 +719,27 @@ __global__ void __launch_bounds__(512, (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH 
     float* u_lds = smem;
     const int HA = H_arg * NA;
     const float* usrc = u_prev + (size_t)v * HA;
-    float ur[4];
-    int jr[2];
+    // loads per thread that cover the warm start (H*A <= LSEG*NCH*NA words) and the joint table
+    constexpr int NU = B512 ? (LSEG * NCH * NA + 511) / 512 : 4, NJ = B512 ? (kJW + 511) / 512 : 2;
+    float ur[NU];
+    int jr[NJ];
     // an overlapped batch (kNoiseOverlap): u_prev is read only after the finalize before this
     // rollout has written it (the wait below, after the first group's normals)
-    const bool ovl = (noise_arg & kNoiseOverlap) != 0;
+    const bool ovl = !B512 && (noise_arg & kNoiseOverlap) != 0;
     auto load_u = [&]() __attribute__((always_inline)) {
         // through a buffer resource over this vehicle's u_prev: 32-bit offsets, and the rows past
         // H*A read 0 from the range check (no per-load branch, no 64-bit address math)
         const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float*>(usrc), 0, (MPPI_KO & 128) ? 0 : HA * 4, 0x00020000);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < NU; ++j)
             ur[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(urs, (tid + j * nthr) * 4, 0, kAuxDev));
     };
     if (!ovl) load_u();
     if (MODEL != MPPI_MODEL_DRONE) {
         const int* js = (const int*)jtab;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < NJ; ++j) {
             const int i = tid + j * nthr;
             jr[j] = (i < kJW) ? js[i] : 0;
         }
@@ -774,18 +786,20 @@ __global__ void __launch_bounds__(512, (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH 
     STAMP(10);
     asm volatile("" :: "s"(kwarm));
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < NU; ++j) {
         const int i = tid + j * nthr;
         if (i < HA) u_lds[i] = ur[j];
     }
-    for (int i = tid + 4 * nthr; i < HA; i += nthr) u_lds[i] = usrc[i];   // H*A > 2048
+    if constexpr (!B512)
+        for (int i = tid + 4 * nthr; i < HA; i += nthr) u_lds[i] = usrc[i];   // H*A > 2048
     if (MODEL != MPPI_MODEL_DRONE) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < NJ; ++j) {
             const int i = tid + j * nthr;
             if (i < kJW) ((int*)jnt)[i] = jr[j];
         }
-        for (int i = tid + 2 * nthr; i < kJW; i += nthr) ((int*)jnt)[i] = ((const int*)jtab)[i];
+        if constexpr (!B512)
+            for (int i = tid + 2 * nthr; i < kJW; i += nthr) ((int*)jnt)[i] = ((const int*)jtab)[i];
     }
     if (tid < kVCW) {
         ((int*)&vcv)[tid] = vcr;
@@ -794,12 +808,14 @@ __global__ void __launch_bounds__(512, (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH 
             __hip_atomic_store((int*)pk.vc + tid, tid == kVcStepWord ? (int)step_ctr : vcr, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
     }
-    for (int i = tid + nthr; i < kVCW; i += nthr) {   // nthr < 124
-        const int x = VONE ? ((const int*)&pk.vc0)[i] : ((const int*)(pk.vc + v))[i];
-        ((int*)&vcv)[i] = x;
-        if (VONE && blockIdx.x == 0)
-            __hip_atomic_store((int*)pk.vc + i, i == kVcStepWord ? (int)step_ctr : x, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (!B512) {
+        for (int i = tid + nthr; i < kVCW; i += nthr) {   // nthr < 124
+            const int x = VONE ? ((const int*)&pk.vc0)[i] : ((const int*)(pk.vc + v))[i];
+            ((int*)&vcv)[i] = x;
+            if (VONE && blockIdx.x == 0)
+                __hip_atomic_store((int*)pk.vc + i, i == kVcStepWord ? (int)step_ctr : x, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
     STAMPW(8);
     if (!(MPPI_KO & 256)) lds_barrier();
@@ -1245,8 +1261,9 @@ __global__ void __launch_bounds__(512, (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH 
     if (lane == 0) {
         mine[0] = rho_w; mine[1] = eta_w; mine[2] = eta2_w; mine[3] = nan_w ? 1.0f : 0.0f;
     }
-    for (int i = nw * wstride + tid; i < 8 * wstride; i += nthr)   // absent waves: rho = inf, acc = 0
-        wsh[i] = ((i - nw * wstride) % wstride == 0) ? INFINITY : 0.0f;
+    if constexpr (!B512)
+        for (int i = nw * wstride + tid; i < 8 * wstride; i += nthr)   // absent waves: rho = inf, acc = 0
+            wsh[i] = ((i - nw * wstride) % wstride == 0) ? INFINITY : 0.0f;
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
 #pragma unroll
@@ -1327,6 +1344,28 @@ __global__ void __launch_bounds__(512, (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH 
     drain_stores();
 }
 
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG>
+__global__ void __launch_bounds__(512, (roll_occ<NCH, F64, XC, ONEG>())) k_rollout(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                 const uint32_t step_arg, const uint32_t k_off,
+                                                 const int32_t noise_arg, const int32_t H_arg,
+                                                 const int32_t geo_arg,
+                                                 const float* __restrict__ u_prev,
+                                                 const JointDev* __restrict__ jtab, const DevParams pk) {
+    rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, XC, ONEG, false>(seed_lo, seed_hi, step_arg, k_off, noise_arg, H_arg,
+                                                                   geo_arg, u_prev, jtab, pk);
+}
+// The single-group kernel at its one block size (B512 above): the same arguments, geo_arg not read.
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC>
+__global__ void __launch_bounds__(512, (roll_occ<NCH, F64, XC, true>())) k_rollout_s(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                 const uint32_t step_arg, const uint32_t k_off,
+                                                 const int32_t noise_arg, const int32_t H_arg,
+                                                 const int32_t geo_arg,
+                                                 const float* __restrict__ u_prev,
+                                                 const JointDev* __restrict__ jtab, const DevParams pk) {
+    rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, XC, true, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg, H_arg,
+                                                                  geo_arg, u_prev, jtab, pk);
+}
+
 // =============================================================================
 // launchers
 // =============================================================================
@@ -1335,6 +1374,12 @@ template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bo
 inline void rollout_symbol(char* buf, size_t n) {
     snprintf(buf, n, "_Z9k_rolloutILi%dELi%dELi%dELi%dELb%dELb%dELb%dELb%dEEvjjjjiiiPKfPKN4mppi8JointDevENS2_9DevParamsE",
              MODEL, NA, NCH, LSEG, (int)F64, (int)VONE, (int)XC, (int)ONEG);
+}
+
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC>
+inline void rollout_s_symbol(char* buf, size_t n) {
+    snprintf(buf, n, "_Z11k_rollout_sILi%dELi%dELi%dELi%dELb%dELb%dELb%dEEvjjjjiiiPKfPKN4mppi8JointDevENS2_9DevParamsE",
+             MODEL, NA, NCH, LSEG, (int)F64, (int)VONE, (int)XC);
 }
 
 template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC, bool ONEG>
@@ -1357,11 +1402,34 @@ inline int launch_rollout_g(const DevParams& p, int threads, hipStream_t s) {
               p);
 }
 
-// the single-group (ONEG) variant exists for the common kernel at NCH == 1
+// the single-group kernel at 512 threads (k_rollout_s): launch_rollout_g's launch of it
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC>
+inline int launch_rollout_s(const DevParams& p, hipStream_t s) {
+    constexpr int threads = 512;
+    const int s_run = cost_run_stride((threads / 64) * (64 / LSEG));
+    if (s_run > kMaxCostRun) return -1;
+    const size_t lds = (size_t)(((p.H * NA + 3) & ~3) + 8 * wave_slot_floats<NA, NCH, LSEG>() + s_run) * sizeof(float);
+    const int32_t geo = threads | (1 << 16);
+    if (p.V == 1)
+        return go(k_rollout_s<MODEL, NA, NCH, LSEG, F64, true, XC>, rollout_s_symbol<MODEL, NA, NCH, LSEG, F64, true, XC>,
+                  dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
+                  p.noise_mode, p.H, geo, p.u_prev, p.joints, p);
+    return go(k_rollout_s<MODEL, NA, NCH, LSEG, F64, false, XC>, rollout_s_symbol<MODEL, NA, NCH, LSEG, F64, false, XC>,
+              dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
+              p.noise_mode, p.H, geo, p.u_prev, p.joints, p);
+}
+
+// the single-group (ONEG) variant exists for the common kernel at NCH == 1; at 512 threads, without
+// the overlap experiment's wait and unless the engine asks for the kernels as they were
+// (DevParams::kern, MPPI_GENERIC_KERNELS), its fixed-block form
 template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC>
 inline int launch_rollout_x(const DevParams& p, int threads, hipStream_t s) {
     if constexpr (!XC && NCH == 1)
-        if (p.iters == 1) return launch_rollout_g<MODEL, NA, NCH, LSEG, F64, XC, true>(p, threads, s);
+        if (p.iters == 1) {
+            if (threads == 512 && !p.kern && !(p.noise_mode & kNoiseOverlap) && p.H <= LSEG * NCH)
+                return launch_rollout_s<MODEL, NA, NCH, LSEG, F64, XC>(p, s);
+            return launch_rollout_g<MODEL, NA, NCH, LSEG, F64, XC, true>(p, threads, s);
+        }
     return launch_rollout_g<MODEL, NA, NCH, LSEG, F64, XC, false>(p, threads, s);
 }
 

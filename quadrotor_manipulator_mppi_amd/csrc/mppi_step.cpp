@@ -81,13 +81,44 @@ mppi_status mppi_rollout(mppi_engine* e, const float* d_noise) {
     return MPPI_OK;
 }
 
+// A batch's steps before its last may run the quiet FINAL (mppi_finalize.hip kRoleQuiet: u_prev and
+// nothing else; the outputs of a batch are those of its last step).  Engines with stamps, timing
+// or output diagnostics, the overlap experiment and MPPI_GENERIC_KERNELS keep the full kernel on
+// every step; so does the launcher where no quiet kernel applies (the geometry, a peer exchange).
+static bool quiet_steps(const mppi_engine* e) {
+    return !(e->generic & 3) && !e->timing && !e->d_stamps && !e->d_fstamps && !e->out_dbg && !e->no_flag_dbg && !e->overlap;
+}
+
+// The symbol a launch would run, by the launchers' own description of it (mppi_device.h go()).
+static std::string fin_symbol(const FinParams& f) {
+    LaunchDesc d{};
+    mppi_aql::set_capture(&d);
+    const int rc = mppi_launch_finalize(&f, nullptr);
+    mppi_aql::set_capture(nullptr);
+    return rc == 0 ? d.symbol : "?";
+}
+static std::string roll_symbol(const DevParams& p, int threads) {
+    LaunchDesc d{};
+    mppi_aql::set_capture(&d);
+    const int rc = mppi_launch_rollout(&p, threads, nullptr);
+    mppi_aql::set_capture(nullptr);
+    return rc == 0 ? d.symbol : "?";
+}
+static std::string kernels_text(const std::string& roll, const std::string& fin, const std::string* quiet) {
+    std::string s = "rollout " + roll + ", finalize " + fin;
+    if (quiet) s += ", quiet finalize " + (*quiet == fin ? std::string("none") : *quiet);
+    return s;
+}
+
 // record_out: mark the outputs' completion with ev_out (read_outputs waits on it).
 // Back-to-back steps (mppi_run_steps) mark only the last one: an event record is
 // a queue packet of its own, ~1 us of device time per step.
-static mppi_status finalize_impl(mppi_engine* e, bool record_out) {
+// quiet: a step of a batch before its last (never read): the quiet FINAL where one applies.
+static mppi_status finalize_impl(mppi_engine* e, bool record_out, bool quiet = false) {
     if (use_device(e)) return MPPI_ERR_HIP;
     FinParams f = e->fp;
     f.mode = 0;
+    if (quiet && !record_out && quiet_steps(e)) f.kern |= kFinKernQuiet;
     f.seq = 0u;   // no completion flag (and no fence) for unread steps
     if (record_out && !e->no_flag_dbg) {   // a fresh value per read step, never 0 (the flags start zeroed):
                                            // the flags the previous read step left can never satisfy this
@@ -339,6 +370,17 @@ mppi_status mppi_step(mppi_engine* e, const double* state, const float* h_noise,
     if ((st = mppi_rollout(e, dn)) != MPPI_OK) return st;
     if (e->comm && (st = mppi_exchange(e)) != MPPI_OK) return st;
     if ((st = mppi_finalize(e)) != MPPI_OK) return st;
+    if (!e->kern_call_hip || e->kern_call_peer != e->peer) {   // (mppi_kernel_info; described once)
+        DevParams p = e->dp;
+        p.noise_in = dn;
+        p.vc0 = e->h_vc[0];
+        FinParams f = e->fp;
+        f.mode = 0;
+        final_records(e, f);
+        e->kern_call = kernels_text(roll_symbol(p, e->threads), fin_symbol(f), nullptr);
+        e->kern_call_hip = true;
+        e->kern_call_peer = e->peer;
+    }
     return mppi_read_outputs(e, out, u0, stats);
 }
 
@@ -397,6 +439,7 @@ static mppi_status run_steps_aql(mppi_engine* e, int32_t n, bool* used) {
     const auto c1 = now();
     LaunchDesc& roll = e->batch_roll;
     LaunchDesc& fin = e->batch_fin;
+    LaunchDesc& finq = e->batch_fin_quiet;   // every step's but the last (quiet_steps)
     DevParams p = e->dp;
     p.noise_in = nullptr;
     p.vc0 = e->h_vc[0];
@@ -411,11 +454,18 @@ static mppi_status run_steps_aql(mppi_engine* e, int32_t n, bool* used) {
     if (!(e->batch_cached && e->batch_threads == e->threads && std::memcmp(&p, &e->batch_p, sizeof(p)) == 0 &&
           std::memcmp(&f, &e->batch_f, sizeof(f)) == 0)) {
         e->batch_cached = false;
+        e->kern_batch_state = 0;
         mppi_aql::set_capture(&roll);
         int rc = mppi_launch_rollout(&p, e->threads, e->stream);
         if (rc == 0) {
             mppi_aql::set_capture(&fin);
             rc = mppi_launch_finalize(&f, e->stream);
+        }
+        if (rc == 0) {
+            FinParams fq = f;
+            if (quiet_steps(e)) fq.kern |= kFinKernQuiet;
+            mppi_aql::set_capture(&finq);
+            rc = mppi_launch_finalize(&fq, e->stream);
         }
         mppi_aql::set_capture(nullptr);
         if (rc != 0) return fail(MPPI_ERR_HIP, "describing the step's launches failed (%d)", rc);
@@ -427,7 +477,7 @@ static mppi_status run_steps_aql(mppi_engine* e, int32_t n, bool* used) {
     std::string err;
     const auto c2 = now();
     const auto guard = mppi_aql::step_guard(e->aql);   // (no prewarm touch between prepare and dispatch)
-    const int pr = mppi_aql::step_prepare(e->aql, roll, fin, e->step_ctr, kRollStepOff, &err);
+    const int pr = mppi_aql::step_prepare(e->aql, roll, fin, finq, e->step_ctr, kRollStepOff, &err);
     const auto c3 = now();
     if (pr == -2) {   // not dispatchable natively (a kernel the code objects lack, hidden arguments)
         e->aql_off = true;
@@ -455,6 +505,11 @@ static mppi_status run_steps_aql(mppi_engine* e, int32_t n, bool* used) {
     e->aql_out = true;
     e->aql_call = false;
     e->aql_why.clear();
+    if (e->kern_batch_state != (n > 1 ? 2 : 1)) {   // (mppi_kernel_info; a one-step batch runs no quiet finalize)
+        const std::string q = n > 1 ? finq.symbol : fin.symbol;
+        e->kern_batch = kernels_text(roll.symbol, fin.symbol, &q);
+        e->kern_batch_state = n > 1 ? 2 : 1;
+    }
     *used = true;
     return MPPI_OK;
 }
@@ -551,6 +606,8 @@ static mppi_status control_call_aql(mppi_engine* e, const double* state, bool* u
     e->out_pending = true;
     e->aql_out = false;
     e->aql_call = true;
+    if (!hit || e->kern_call_hip) e->kern_call = kernels_text(roll.symbol, fin.symbol, nullptr);
+    e->kern_call_hip = false;
     *used = true;
     return MPPI_OK;
 }
@@ -568,8 +625,31 @@ mppi_status mppi_run_steps(mppi_engine* e, int32_t n) {
         mppi_status st = mppi_rollout(e, nullptr);
         if (st != MPPI_OK) return st;
         if (e->comm && (st = mppi_exchange(e)) != MPPI_OK) return st;
-        if ((st = finalize_impl(e, i == n - 1)) != MPPI_OK) return st;
+        if ((st = finalize_impl(e, i == n - 1, true)) != MPPI_OK) return st;
     }
+    {   // (mppi_kernel_info) the launches above, described
+        DevParams p = e->dp;
+        p.vc0 = e->h_vc[0];
+        FinParams f = e->fp;
+        f.mode = 0;
+        final_records(e, f);
+        const std::string full = fin_symbol(f);
+        if (n > 1 && quiet_steps(e)) f.kern |= kFinKernQuiet;
+        const std::string q = fin_symbol(f);
+        e->kern_batch = kernels_text(roll_symbol(p, e->threads), full, &q);
+        e->kern_batch_state = 0;
+    }
+    return MPPI_OK;
+}
+
+// The kernels the last mppi_run_steps and the last mppi_step ran: for each, the rollout's and the
+// finalize's symbols (the instantiations' Itanium names, as the code objects hold them), and for a
+// batch the quiet finalize of its steps before the last ("none": every step ran the full one).
+// "; MPPI_GENERIC_KERNELS" at the end when the engine was created with that switch.
+mppi_status mppi_kernel_info(mppi_engine* e, char* buf, int32_t len) {
+    if (!e || !buf || len <= 0) return fail(MPPI_ERR_INVALID_ARG, "mppi_kernel_info: bad arguments");
+    snprintf(buf, (size_t)len, "batch: %s; call: %s%s", e->kern_batch.c_str(), e->kern_call.c_str(),
+             e->generic == 7 ? "; MPPI_GENERIC_KERNELS" : e->generic ? "; MPPI_GENERIC_KERNELS (in part)" : "");
     return MPPI_OK;
 }
 
@@ -579,6 +659,29 @@ mppi_status mppi_dispatch_info(mppi_engine* e, char* buf, int32_t len) {
              e->calls_native ? "aql (arguments in " : "hip", e->calls_native ? mppi_aql::step_call_memory(e->aql) : "",
              e->calls_native ? ")" : "");
     return MPPI_OK;
+}
+
+// Diagnostic (not part of the public header; no GPU): the finalize kernels a batch's descriptions
+// would name for a launch of this shape -- g = {A, H, tsz, half, ts, window, nrec, mode, peer
+// exchange, MPPI_GENERIC_KERNELS}: the last step's into `full`, the earlier steps' into `quiet`
+// (the same symbol where no quiet kernel applies).  tests/test_capi_specialized_cpu.py.
+int32_t mppi_debug_finalize_kernels(const int32_t* g, char* full, char* quiet, int32_t len) {
+    if (!g || !full || !quiet || len <= 0) return MPPI_ERR_INVALID_ARG;
+    static const FinTail tail{};
+    static unsigned long long* const peers[1] = {nullptr};
+    FinParams f;
+    std::memset(&f, 0, sizeof(f));
+    f.V = 1; f.A = g[0]; f.H = g[1]; f.tsz = g[2]; f.half = g[3]; f.ts = g[4]; f.window = g[5]; f.nrec = g[6];
+    f.mode = g[7];
+    f.tail = &tail;
+    if (g[8]) f.xpeers = peers;
+    f.kern = g[9] ? kFinKernGeneric : 0;
+    const std::string a = fin_symbol(f);
+    if (!g[9]) f.kern |= kFinKernQuiet;   // (as quiet_steps: not under MPPI_GENERIC_KERNELS)
+    const std::string b = fin_symbol(f);
+    snprintf(full, (size_t)len, "%s", a.c_str());
+    snprintf(quiet, (size_t)len, "%s", b.c_str());
+    return (a == "?" || b == "?") ? MPPI_ERR_INVALID_ARG : MPPI_OK;
 }
 
 mppi_status mppi_synchronize(mppi_engine* e) {

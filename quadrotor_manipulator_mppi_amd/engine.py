@@ -356,6 +356,13 @@ class Engine:
         capi.check(self._L.mppi_dispatch_info(self._h, buf, len(buf)), "dispatch_info")
         return buf.value.decode(errors="replace")
 
+    def kernel_info(self) -> str:
+        """Which kernels the last run_steps / step ran: "batch: rollout <symbol>, finalize <symbol>,
+        quiet finalize <symbol | none>; call: rollout <symbol>, finalize <symbol>"."""
+        buf = C.create_string_buffer(1024)
+        capi.check(self._L.mppi_kernel_info(self._h, buf, len(buf)), "kernel_info")
+        return buf.value.decode(errors="replace")
+
     def stats(self) -> List[StepStats]:
         st = self._stats
         return [StepStats(s.rho, s.eta, s.ess, bool(s.nonfinite), bool(s.reach), s.nonfinite == 2)
