@@ -117,7 +117,8 @@ typedef struct {
                               /*   shard_count * n_samples <= 2^32: the noise stream counts the  */
                               /*   global sample in 32 bits (more: MPPI_ERR_INVALID_ARG)         */
     int32_t state_f64;        /* reproduce the reference's fp64 promotion of an fp64 arm state  */
-    int32_t store_trajectory; /* write the trajectory buffer (q / p and EE 3x4 per (k,t))       */
+    int32_t store_trajectory; /* write the trajectory buffer (q / p and EE 3x4 per (k,t)); after */
+                              /*   a batch it holds the LAST step's (mppi_run_steps)            */
     int32_t store_noise;      /* write eps (K,H,A) (debug / parity readback)                    */
     int32_t check_reach;      /* host FK at qdes, L1 position error < reach_tol (mppi.py:95-120)*/
     float reach_tol;          /* 0.005                                                          */
@@ -343,6 +344,9 @@ mppi_status mppi_step(mppi_engine* e, const double* state, const float* h_noise,
  * all-reduce, finalize).
  * No host synchronisation: pair with mppi_synchronize / mppi_read_outputs.  The outputs of a
  * batch (mppi_read_outputs) are those of its LAST step; its earlier steps need not write any.
+ * The same holds for the trajectory and cost buffers (mppi_get_trajectory, mppi_get_costs,
+ * mppi_get_weights): after a batch they hold its last step's values, and the earlier steps do not
+ * write them where the library has a quiet rollout for the engine's shape (mppi_kernel_info).
  * Single-shard and peer-exchange engines dispatch the steps natively: raw AQL packets on an
  * HSA queue the engine owns, the kernels from the library's code objects, their arguments
  * resident in device memory (MPPI_DISPATCH = auto (default) | aql (required) | hip). */
@@ -359,13 +363,16 @@ mppi_status mppi_run_steps(mppi_engine* e, int32_t n);
  * tool that intercepts queues (rocprofv3 --pmc). */
 mppi_status mppi_dispatch_info(mppi_engine* e, char* buf, int32_t len);
 /* Which kernels the last mppi_run_steps and the last mppi_step ran:
- * "batch: rollout <symbol>, finalize <symbol>, quiet finalize <symbol | none>; call: rollout
- * <symbol>, finalize <symbol>" ("none" before the first of either), the symbols as the library's
- * code objects name them.  The outputs of a batch are those of its last step: its earlier steps run
- * a finalize that updates the warm start and writes nothing else (the quiet finalize) wherever the
- * library has one for the engine's shape.  An engine created with MPPI_GENERIC_KERNELS=1 in the
- * environment (tests, A/B) runs the kernels of every shape and the full finalize on every step;
- * the text then ends in "; MPPI_GENERIC_KERNELS". */
+ * "batch: rollout <symbol>, finalize <symbol>, quiet finalize <symbol | none>, quiet rollout
+ * <symbol | none>; call: rollout <symbol>, finalize <symbol>" ("none" before the first of either),
+ * the symbols as the library's code objects name them.  The outputs of a batch are those of its last
+ * step: its earlier steps run a finalize that updates the warm start and writes nothing else (the
+ * quiet finalize) and a rollout that writes its block records and nothing else -- no trajectory
+ * planes, costs or handed-over vehicle constants (the quiet rollout) -- wherever the library has
+ * them for the engine's shape.  Peer-exchange and sharded engines, stored or injected noise and
+ * engines with timing or diagnostics keep the full rollout on every step.  An engine created with
+ * MPPI_GENERIC_KERNELS=1 in the environment (tests, A/B) runs the kernels of every shape and the
+ * full finalize and rollout on every step; the text then ends in "; MPPI_GENERIC_KERNELS". */
 mppi_status mppi_kernel_info(mppi_engine* e, char* buf, int32_t len);
 
 mppi_status mppi_synchronize(mppi_engine* e);
@@ -387,6 +394,8 @@ mppi_status mppi_set_prewarm(mppi_engine* e, int32_t window_us);
 mppi_status mppi_get_prewarm(mppi_engine* e, int32_t* window_us, int64_t* touches);
 
 /* Readback in the reference's layouts (synchronous):
+ * After mppi_run_steps(n) the costs, weights and trajectories are those of the batch's last step
+ * (its earlier steps do not write them: mppi_run_steps).
  *   costs    S (V,K)                         compute_all_cost()
  *   weights  w (V,K)                         compute_weights()
  *   noise    eps (V,K,H,A)                   sampling()            [store_noise]

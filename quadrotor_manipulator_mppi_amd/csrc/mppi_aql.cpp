@@ -237,10 +237,10 @@ constexpr size_t kArgSlot = 4096;       // bytes per argument block
 // control calls rotate through this many rollout argument blocks (each call a fresh address,
 // as HIP's own kernel-argument ring: no copy of an earlier call's block can sit in a cache)
 constexpr uint32_t kCallSlots = 16;
-// the batch path's (rollout, finalize, quiet finalize) argument blocks: re-uploads rotate over
-// this many triples
+// the batch path's (rollout, finalize, quiet finalize, quiet rollout) argument blocks: re-uploads
+// rotate over this many sets
 constexpr uint32_t kBatchSlots = 4;
-constexpr uint32_t kBatchBlocks = 3;
+constexpr uint32_t kBatchBlocks = 4;
 
 struct Step {
     Device* dev = nullptr;
@@ -248,7 +248,7 @@ struct Step {
     hsa_signal_t done{0};                 // outstanding batches; each batch's last packet decrements it
     std::atomic<int> qerr{0};             // HSA status of an asynchronous queue error
     unsigned char* d_args = nullptr;      // device: the control call's finalize at 0, then kBatchSlots
-                                          // (rollout, finalize, quiet finalize) triples for batches
+                                          // (rollout, finalize, quiet finalize, quiet rollout) sets for batches
     uint32_t batch_slot = 0;              // the pair the batches use now
     unsigned char* h_call = nullptr;      // the control calls' rollout arguments: kCallSlots blocks in
     unsigned char* h_call_dev = nullptr;  //   host-writable device memory (else pinned host memory),
@@ -261,6 +261,8 @@ struct Step {
     mppi::LaunchDesc roll{}, fin{};       // what the device blocks hold (step word as uploaded)
     mppi::LaunchDesc fin_quiet{};         // the finalize of a batch's steps before its last (mppi_finalize.hip
     Kern kr, kf, kfq;                     // kRoleQuiet; the same launch as fin where none applies)
+    mppi::LaunchDesc roll_quiet{};        // the rollout of those steps (mppi_rollout.h QUIET; or roll's launch)
+    Kern krq;
     uint32_t step_off = 0, step_word = 0; // the resident rollout's dispatch-id relative step word
     bool valid = false;
     int64_t outstanding = 0;              // batches dispatched and not yet waited for
@@ -401,14 +403,15 @@ static bool same_launch(const mppi::LaunchDesc& a, const mppi::LaunchDesc& b, ui
 
 static unsigned char* batch_args(Step* s) { return s->d_args + (1 + kBatchBlocks * (size_t)s->batch_slot) * kArgSlot; }
 
-int step_prepare(Step* s, const mppi::LaunchDesc& roll, const mppi::LaunchDesc& fin, const mppi::LaunchDesc& fin_quiet,
-                 uint32_t step, uint32_t step_off, std::string* err) {
+int step_prepare(Step* s, const mppi::LaunchDesc& roll, const mppi::LaunchDesc& roll_quiet, const mppi::LaunchDesc& fin,
+                 const mppi::LaunchDesc& fin_quiet, uint32_t step, uint32_t step_off, std::string* err) {
     std::lock_guard<std::recursive_mutex> qlk(s->mu);
     // the next rollout's packet index (the queue holds (rollout, finalize) pairs only, so
     // rollouts sit at indices of one parity and (index >> 1) counts pairs)
     const uint32_t word = step - (uint32_t)(hsa_queue_load_write_index_relaxed(s->q) >> 1);
     if (s->valid && s->step_word == word && s->step_off == step_off && same_launch(roll, s->roll, step_off) &&
-        same_launch(fin, s->fin, ~0u) && same_launch(fin_quiet, s->fin_quiet, ~0u))
+        same_launch(roll_quiet, s->roll_quiet, step_off) && same_launch(fin, s->fin, ~0u) &&
+        same_launch(fin_quiet, s->fin_quiet, ~0u))
         return 0;
     if (getenv("MPPI_AQL_PROFILE") && s->valid) {   // diagnostics: why the blocks are re-uploaded
         int first = -1;
@@ -420,15 +423,20 @@ int step_prepare(Step* s, const mppi::LaunchDesc& roll, const mppi::LaunchDesc& 
         fprintf(stderr, "[mppi aql] re-upload: word %u vs %u, rollout args differ at %d, finalize at %d, sym %d/%d\n", word,
                 s->step_word, first, ffirst, strcmp(roll.symbol, s->roll.symbol), strcmp(fin.symbol, s->fin.symbol));
     }
-    Kern kr, kf, kfq;
+    Kern kr, kf, kfq, krq;
     {
         std::lock_guard<std::mutex> lk(g_mu);
         if (!lookup(s->dev, roll.symbol, &kr, err) || !lookup(s->dev, fin.symbol, &kf, err) ||
-            !lookup(s->dev, fin_quiet.symbol, &kfq, err))
+            !lookup(s->dev, fin_quiet.symbol, &kfq, err) || !lookup(s->dev, roll_quiet.symbol, &krq, err))
             return -2;
     }
-    if (!check_launch(roll, kr, err) || !check_launch(fin, kf, err) || !check_launch(fin_quiet, kfq, err)) return -2;
-    if (step_off + 4 > roll.arg_bytes) { *err = "step counter outside the rollout's arguments"; return -2; }
+    if (!check_launch(roll, kr, err) || !check_launch(fin, kf, err) || !check_launch(fin_quiet, kfq, err) ||
+        !check_launch(roll_quiet, krq, err))
+        return -2;
+    if (step_off + 4 > roll.arg_bytes || step_off + 4 > roll_quiet.arg_bytes) {
+        *err = "step counter outside the rollout's arguments";
+        return -2;
+    }
     // the queue may still be reading the blocks about to be overwritten
     if (s->outstanding && step_wait(s, 60000, err) != 0) return -1;
     std::vector<unsigned char> h(kBatchBlocks * kArgSlot, 0);
@@ -436,6 +444,8 @@ int step_prepare(Step* s, const mppi::LaunchDesc& roll, const mppi::LaunchDesc& 
     memcpy(h.data() + step_off, &word, 4);
     memcpy(h.data() + kArgSlot, fin.args, fin.arg_bytes);
     memcpy(h.data() + 2 * kArgSlot, fin_quiet.args, fin_quiet.arg_bytes);
+    memcpy(h.data() + 3 * kArgSlot, roll_quiet.args, roll_quiet.arg_bytes);
+    memcpy(h.data() + 3 * kArgSlot + step_off, &word, 4);   // (the same step word: either kernel of a pair)
     // a fresh set of blocks for every upload (no cached copy of an earlier upload can be read)
     s->batch_slot = (s->batch_slot + 1) % kBatchSlots;
     if (hipMemcpy(batch_args(s), h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
@@ -446,6 +456,8 @@ int step_prepare(Step* s, const mppi::LaunchDesc& roll, const mppi::LaunchDesc& 
     s->roll = roll;
     s->fin = fin;
     s->fin_quiet = fin_quiet;
+    s->roll_quiet = roll_quiet;
+    s->krq = krq;
     s->kr = kr;
     s->kf = kf;
     s->kfq = kfq;
@@ -587,11 +599,12 @@ int step_dispatch(Step* s, int n, std::string* err, bool overlap) {
     void* ra = batch_args(s);
     void* fa = batch_args(s) + kArgSlot;
     void* fqa = batch_args(s) + 2 * kArgSlot;   // (every finalize but the batch's last: nobody reads its outputs)
+    void* rqa = batch_args(s) + 3 * kArgSlot;   // (likewise every rollout but the last)
     load_fences();
     for (int i = 0; i < n; ++i) {
         const bool last = i == n - 1;
-        put(s->q, s->kr, s->roll, ra, none, i == 0 ? std::max(1, g_fence[0]) : g_fence[0], g_fence[1],
-            !(overlap && i > 0));
+        put(s->q, last ? s->kr : s->krq, last ? s->roll : s->roll_quiet, last ? ra : rqa, none,
+            i == 0 ? std::max(1, g_fence[0]) : g_fence[0], g_fence[1], !(overlap && i > 0));
         if (last) put(s->q, s->kf, s->fin, fa, s->done, g_fence[2], 2);
         else put(s->q, s->kfq, s->fin_quiet, fqa, none, g_fence[2], g_fence[3]);
         // the doorbell takes the index of the last packet written

@@ -36,10 +36,14 @@ bool step_destroy(Step* s);
 // cannot be dispatched natively (a symbol the code objects lack, hidden arguments);
 // -1 on a runtime failure (*err says why).
 // fin_quiet: the finalize of every pair but a batch's last (the quiet FINAL, or fin again).
-int step_prepare(Step* s, const mppi::LaunchDesc& roll, const mppi::LaunchDesc& fin, const mppi::LaunchDesc& fin_quiet,
-                 uint32_t step, uint32_t step_off, std::string* err);
+// roll_quiet: likewise the rollout of those pairs (the quiet rollout, or roll again): the same
+// arguments as roll's, so its block gets the same step word at the same offset, and the dispatch-id
+// step counting holds for whichever of the two a pair runs.
+int step_prepare(Step* s, const mppi::LaunchDesc& roll, const mppi::LaunchDesc& roll_quiet, const mppi::LaunchDesc& fin,
+                 const mppi::LaunchDesc& fin_quiet, uint32_t step, uint32_t step_off, std::string* err);
 // n (rollout, finalize) pairs, each kernel dependent on the one before; the last finalize is
-// `fin` and carries the completion signal and a system-scope release, the others are `fin_quiet`.
+// `fin` and carries the completion signal and a system-scope release, the others are `fin_quiet`;
+// the last rollout is `roll`, the others are `roll_quiet`.
 // overlap: every rollout after the first without the barrier bit (it starts while the finalize
 // before it runs and waits for it in the kernel: mppi_device.h kNoiseOverlap)
 int step_dispatch(Step* s, int n, std::string* err, bool overlap = false);

@@ -129,9 +129,12 @@ struct DevParams {
     // (V, A, ts) words each incremented once per FINAL (FinTail::xovl), and their count per vehicle
     const uint32_t* ovl;
     int32_t ovl_n;
-    int32_t kern;                 // 1: the kernels as before the fixed-block single-group one
-                                  // (MPPI_GENERIC_KERNELS; mppi_rollout.h launch_rollout_x)
+    int32_t kern;                 // kRollKern* bits (mppi_rollout.h launch_rollout_x)
 };
+// DevParams::kern bits.  Generic: the kernels as before the fixed-block single-group one
+// (MPPI_GENERIC_KERNELS).  Quiet: this rollout's trajectory planes, costs, stored noise and
+// handed-over vehicle constants are never read (a batch's step before its last): the records only.
+constexpr int32_t kRollKernGeneric = 1, kRollKernQuiet = 2;
 constexpr int kStamps = 16;
 
 // The finalize tail's parameters, device-resident: written once at create (one copy per

@@ -28,6 +28,9 @@
 #include "mppi_aql.h"
 #include "mppi_dev.h"
 
+// mppi_engine::generic with every part switched back (MPPI_GENERIC_KERNELS=1)
+constexpr int kGenericAll = 15;
+
 struct mppi_engine {
     mppi_config cfg;
     int K, H, A, V, nq, qoff, state_dim, out_dim, C, threads;
@@ -58,10 +61,12 @@ struct mppi_engine {
     mppi::LaunchDesc batch_roll{}, batch_fin{};
     mppi::LaunchDesc batch_fin_quiet{}; // the quiet FINAL of the batch's steps before its last (the same
                                         // description as batch_fin where no quiet kernel applies)
+    mppi::LaunchDesc batch_roll_quiet{};   // likewise the quiet rollout of those steps (or batch_roll's launch)
     int generic = 0;                    // MPPI_GENERIC_KERNELS=1 (tests, A/B): the kernels as before the role and
                                         // fixed-block ones.  Bits: 1 the finalize of every role with run-time
                                         // geometry, 2 the full FINAL on every step, 4 the rollout of every block
-                                        // size ("finalize", "quiet", "rollout" set one of them; 1 sets all)
+                                        // size, 8 the full rollout on every step ("finalize", "quiet",
+                                        // "rollout", "quiet_rollout" set one of them; 1 sets all: kGenericAll)
     // the kernels the last batch and the last control call ran (mppi_kernel_info)
     std::string kern_batch = "none", kern_call = "none";
     int kern_batch_state = 0;           // kern_batch describes the resident native batch: 1 one step, 2 several

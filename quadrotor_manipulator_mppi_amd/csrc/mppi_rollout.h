@@ -24,7 +24,9 @@
 // wrong in such a build): 1 drops the integrator scans, 2 the Philox draw, 4 the FK chain,
 // 8 the pose cost, 16 the trajectory stores, 32 Box-Muller, 64 the block record body,
 // 128 the u_prev loads (H*A <= 4 * block threads), 256 the prologue's block barrier (LDS
-// staging read unsynchronised), 512 the end-of-wave store drain (the hand-off unordered).
+// staging read unsynchronised), 512 the end-of-wave store drain (the hand-off unordered),
+// 1024 the cost vector S (its LDS staging and store runs), 2048 block 0's vehicle-constant
+// hand-off (16 + 1024 + 2048 on every launch: the upper bound of the quiet rollout, below).
 #ifndef MPPI_KO
 #define MPPI_KO 0
 #endif
@@ -682,7 +684,13 @@ template <int NCH, bool F64, bool XC, bool ONEG>
 constexpr int roll_occ() {
     return (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH == 2 ? (XC ? MPPI_ROLL_OCC_NCH2_XC : MPPI_ROLL_OCC_NCH2) : (XC ? MPPI_ROLL_OCC_XC : MPPI_ROLL_OCC));
 }
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG, bool B512>
+// QUIET (k_rollout_q, k_rollout_ql): the rollout of a batch's step before its last (mppi_step.cpp
+// quiet_rollout): nothing reads that step's trajectory planes, costs S, stored noise or handed-over
+// vehicle constants before the next step overwrites them (the quiet FINAL after it reads only the
+// records), so the instantiation has none of those stores, nor the plane descriptor, the S staging
+// in LDS or block 0's hand-off.  Everything the records are made of is the same code in the same
+// order: the records are bit-identical to the full kernel's.
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG, bool B512, bool QUIET = false>
 __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint32_t seed_hi,
                                              const uint32_t step_arg, const uint32_t k_off,
                                              const int32_t noise_arg, const int32_t H_arg,
@@ -690,6 +698,10 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                                              const float* __restrict__ u_prev,
                                              const JointDev* __restrict__ jtab, const DevParams& pk) {
     static_assert(!B512 || ONEG, "the fixed-block body is a single-group one");
+    static_assert(!QUIET || (!XC && NCH == 1), "the quiet body exists for the common one-chunk kernels");
+    constexpr bool kTraj = !QUIET && !(MPPI_KO & 16);      // trajectory planes
+    constexpr bool kCosts = !QUIET && !(MPPI_KO & 1024);   // the cost vector S
+    constexpr bool kHand = !QUIET && !(MPPI_KO & 2048);    // block 0's vehicle-constant hand-off
     constexpr int R = 64 / LSEG;
     constexpr int QOFF = (MODEL == MPPI_MODEL_WHOLEBODY) ? 3 : 0;
     constexpr int NQ = (MODEL == MPPI_MODEL_DRONE) ? 0 : NA - QOFF;
@@ -803,7 +815,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     }
     if (tid < kVCW) {
         ((int*)&vcv)[tid] = vcr;
-        if (VONE && blockIdx.x == 0)   // hand vc0 to the finalize (written through), with this
+        if (kHand && VONE && blockIdx.x == 0)   // hand vc0 to the finalize (written through), with this
                                        // step's Philox counter in a spare word (the peer exchange's tag)
             __hip_atomic_store((int*)pk.vc + tid, tid == kVcStepWord ? (int)step_ctr : vcr, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
@@ -812,7 +824,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         for (int i = tid + nthr; i < kVCW; i += nthr) {   // nthr < 124
             const int x = VONE ? ((const int*)&pk.vc0)[i] : ((const int*)(pk.vc + v))[i];
             ((int*)&vcv)[i] = x;
-            if (VONE && blockIdx.x == 0)
+            if (kHand && VONE && blockIdx.x == 0)
                 __hip_atomic_store((int*)pk.vc + i, i == kVcStepWord ? (int)step_ctr : x, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -833,9 +845,10 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     // descriptor stays in SGPRs)
     // rows padded to 64 B (hp = H rounded up to 16) and written whole, pad lanes included: the
     // write-through stores then never leave a partial 64 B sector for HBM to merge
-    const int hp = pk.hp;
+    const int hp = kTraj ? pk.hp : 0;
     const uint32_t plane_b = (uint32_t)K * (uint32_t)hp * 4u;
-    const __amdgpu_buffer_rsrc_t trs = traj_rsrc(pk.traj + (size_t)v * pk.C * K * hp, plane_b, pk.C);
+    const __amdgpu_buffer_rsrc_t trs = traj_rsrc(kTraj ? pk.traj + (size_t)v * pk.C * K * hp : nullptr, plane_b,
+                                                 kTraj ? pk.C : 0);
 
     float acc[NCH][NA];
 #pragma unroll
@@ -903,7 +916,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 eps[c][a] = val ? eps[c][a] : 0.0f;
                 act[c][a] = val ? ur[a] + eps[c][a] : 0.0f;
             }
-            if (p.store_noise && val) {   // (readback only: written through, st_dev)
+            if (!QUIET && p.store_noise && val) {   // (readback only: written through, st_dev)
                 float* dst = p.noise_out + (((size_t)v * K + k) * H + t) * NA;
 #pragma unroll
                 for (int a = 0; a < NA; ++a) st_dev(dst + a, eps[c][a]);
@@ -1038,7 +1051,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             const bool term = (t == H - 1);
             float x;
             const uint32_t toff = ((uint32_t)k * (uint32_t)hp + (uint32_t)t) * 4u;   // byte offset in a plane
-            const bool stv = p.store_traj && kval && t < hp;   // row incl. its pad (finite values)
+            const bool stv = kTraj && p.store_traj && kval && t < hp;   // row incl. its pad (finite values)
             if (MODEL == MPPI_MODEL_DRONE) {
                 const float dx = posf[c][0] - vc.tpos[0], dy = posf[c][1] - vc.tpos[1],
                             dz = posf[c][2] - vc.tpos[2];
@@ -1189,7 +1202,8 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         float S_mine = S_seg[0];
 #pragma unroll
         for (int s = 1; s < R; ++s) S_mine = (sub == s) ? S_seg[s] : S_mine;
-        if (MPPI_S_PLAIN) { if (kval && t0 == 0) p.S[(size_t)v * K + k] = S_mine; }   // (experiment: round 3's plain store)
+        if (!kCosts) { }
+        else if (MPPI_S_PLAIN) { if (kval && t0 == 0) p.S[(size_t)v * K + k] = S_mine; }   // (experiment: round 3's plain store)
         else if (kval && t0 == 0) s_stage[it * cost_run_stride(nw * R) + wid * R + sub] = S_mine;
 
         // ---- online softmin (mppi.py:184-188) over this wave's rollouts (scalar bookkeeping)
@@ -1271,7 +1285,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     STAMPW(11);
     lds_barrier();
     STAMP(6);
-    if (!MPPI_S_PLAIN && wid == nw - 1) {
+    if (kCosts && !MPPI_S_PLAIN && wid == nw - 1) {
         // The block's costs: one write-through run per group (st_dev_run), nw * R consecutive
         // samples each -- one whole 64 B line per group at R = 2 (H <= 32: C2, C3).  Issued by
         // the block's last wave, which has the fewest record stores behind it: from wave 0 the
@@ -1366,6 +1380,34 @@ __global__ void __launch_bounds__(512, (roll_occ<NCH, F64, XC, true>())) k_rollo
                                                                   geo_arg, u_prev, jtab, pk);
 }
 
+// The quiet rollout (rollout_body QUIET): k_rollout_q is k_rollout_s's quiet form, k_rollout_ql
+// k_rollout's (any block size, one group or a loop of them).  New symbols: the full kernels' names
+// stay as they are.  Same arguments as the full kernels, so a launch differs only in its symbol
+// and its LDS size (no cost runs).
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG>
+__global__ void __launch_bounds__(512, (roll_occ<NCH, F64, XC, ONEG>())) k_rollout_ql(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                 const uint32_t step_arg, const uint32_t k_off,
+                                                 const int32_t noise_arg, const int32_t H_arg,
+                                                 const int32_t geo_arg,
+                                                 const float* __restrict__ u_prev,
+                                                 const JointDev* __restrict__ jtab, const DevParams pk) {
+    rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, XC, ONEG, false, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg,
+                                                                         H_arg, geo_arg, u_prev, jtab, pk);
+}
+// (fp64 state: budgeted for 7 waves per SIMD, the full k_rollout_s's register count (72 VGPRs) gives
+// it that many; at the 4-wave budget max-ilp took 79 for the quiet body, at 7 it takes 60 with the
+// same instruction count and no scratch -- profiles/r08/quiet_rollout/isa_counts.txt)
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC>
+__global__ void __launch_bounds__(512, (F64 ? 7 : roll_occ<NCH, F64, XC, true>())) k_rollout_q(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                 const uint32_t step_arg, const uint32_t k_off,
+                                                 const int32_t noise_arg, const int32_t H_arg,
+                                                 const int32_t geo_arg,
+                                                 const float* __restrict__ u_prev,
+                                                 const JointDev* __restrict__ jtab, const DevParams pk) {
+    rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, XC, true, true, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg,
+                                                                        H_arg, geo_arg, u_prev, jtab, pk);
+}
+
 // =============================================================================
 // launchers
 // =============================================================================
@@ -1380,6 +1422,63 @@ template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC>
 inline void rollout_s_symbol(char* buf, size_t n) {
     snprintf(buf, n, "_Z11k_rollout_sILi%dELi%dELi%dELi%dELb%dELb%dELb%dEEvjjjjiiiPKfPKN4mppi8JointDevENS2_9DevParamsE",
              MODEL, NA, NCH, LSEG, (int)F64, (int)VONE, (int)XC);
+}
+
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG>
+inline void rollout_ql_symbol(char* buf, size_t n) {
+    snprintf(buf, n, "_Z12k_rollout_qlILi%dELi%dELi%dELi%dELb%dELb%dELb%dELb%dEEvjjjjiiiPKfPKN4mppi8JointDevENS2_9DevParamsE",
+             MODEL, NA, NCH, LSEG, (int)F64, (int)VONE, (int)XC, (int)ONEG);
+}
+
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC>
+inline void rollout_q_symbol(char* buf, size_t n) {
+    snprintf(buf, n, "_Z11k_rollout_qILi%dELi%dELi%dELi%dELb%dELb%dELb%dEEvjjjjiiiPKfPKN4mppi8JointDevENS2_9DevParamsE",
+             MODEL, NA, NCH, LSEG, (int)F64, (int)VONE, (int)XC);
+}
+
+// The geometries the quiet rollout is instantiated for: the kernels the default shapes run (arm and
+// drone at H <= 32, whole-body at H in 33..64; common kernel, one chunk).  Every other launch
+// keeps the full kernel on every step.
+template <int MODEL, int NCH, int LSEG, bool XC>
+constexpr bool quiet_geom() {
+    return !XC && NCH == 1 && LSEG == (MODEL == MPPI_MODEL_WHOLEBODY ? 64 : 32);
+}
+// a launch the caller marked quiet (DevParams::kern) and a quiet kernel can run: device noise, not
+// stored, no overlap wait
+inline bool quiet_launch(const DevParams& p) {
+    return (p.kern & kRollKernQuiet) && (p.noise_mode & 0xFF) != MPPI_NOISE_INJECTED && !p.store_noise &&
+           !(p.noise_mode & kNoiseOverlap);
+}
+
+// the quiet forms of launch_rollout_g / launch_rollout_s (no cost runs in LDS)
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC, bool ONEG>
+inline int launch_rollout_gq(const DevParams& p, int threads, hipStream_t s) {
+    const int iters = ONEG ? 1 : p.iters;
+    if (threads <= 0 || threads > 512 || iters < 1) return -1;
+    const size_t lds = (size_t)(((p.H * NA + 3) & ~3) + 8 * wave_slot_floats<NA, NCH, LSEG>()) * sizeof(float);
+    const int32_t geo = threads | (iters << 16);
+    if (p.V == 1)
+        return go(k_rollout_ql<MODEL, NA, NCH, LSEG, F64, true, XC, ONEG>,
+                  rollout_ql_symbol<MODEL, NA, NCH, LSEG, F64, true, XC, ONEG>, dim3(p.nb, p.V), dim3(threads), lds, s,
+                  p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset, p.noise_mode, p.H, geo, p.u_prev,
+                  p.joints, p);
+    return go(k_rollout_ql<MODEL, NA, NCH, LSEG, F64, false, XC, ONEG>,
+              rollout_ql_symbol<MODEL, NA, NCH, LSEG, F64, false, XC, ONEG>, dim3(p.nb, p.V), dim3(threads), lds, s,
+              p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset, p.noise_mode, p.H, geo, p.u_prev, p.joints,
+              p);
+}
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC>
+inline int launch_rollout_sq(const DevParams& p, hipStream_t s) {
+    constexpr int threads = 512;
+    const size_t lds = (size_t)(((p.H * NA + 3) & ~3) + 8 * wave_slot_floats<NA, NCH, LSEG>()) * sizeof(float);
+    const int32_t geo = threads | (1 << 16);
+    if (p.V == 1)
+        return go(k_rollout_q<MODEL, NA, NCH, LSEG, F64, true, XC>, rollout_q_symbol<MODEL, NA, NCH, LSEG, F64, true, XC>,
+                  dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
+                  p.noise_mode, p.H, geo, p.u_prev, p.joints, p);
+    return go(k_rollout_q<MODEL, NA, NCH, LSEG, F64, false, XC>, rollout_q_symbol<MODEL, NA, NCH, LSEG, F64, false, XC>,
+              dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
+              p.noise_mode, p.H, geo, p.u_prev, p.joints, p);
 }
 
 template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC, bool ONEG>
@@ -1422,14 +1521,25 @@ inline int launch_rollout_s(const DevParams& p, hipStream_t s) {
 // the single-group (ONEG) variant exists for the common kernel at NCH == 1; at 512 threads, without
 // the overlap experiment's wait and unless the engine asks for the kernels as they were
 // (DevParams::kern, MPPI_GENERIC_KERNELS), its fixed-block form
+// A launch marked quiet (quiet_launch) runs the quiet form of whichever of the three it would run,
+// where that form is instantiated (quiet_geom); the full kernel otherwise.
 template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC>
 inline int launch_rollout_x(const DevParams& p, int threads, hipStream_t s) {
+    bool quiet = false;
+    if constexpr (quiet_geom<MODEL, NCH, LSEG, XC>()) quiet = quiet_launch(p);
     if constexpr (!XC && NCH == 1)
         if (p.iters == 1) {
-            if (threads == 512 && !p.kern && !(p.noise_mode & kNoiseOverlap) && p.H <= LSEG * NCH)
+            if (threads == 512 && !(p.kern & kRollKernGeneric) && !(p.noise_mode & kNoiseOverlap) && p.H <= LSEG * NCH) {
+                if constexpr (quiet_geom<MODEL, NCH, LSEG, XC>())
+                    if (quiet) return launch_rollout_sq<MODEL, NA, NCH, LSEG, F64, XC>(p, s);
                 return launch_rollout_s<MODEL, NA, NCH, LSEG, F64, XC>(p, s);
+            }
+            if constexpr (quiet_geom<MODEL, NCH, LSEG, XC>())
+                if (quiet) return launch_rollout_gq<MODEL, NA, NCH, LSEG, F64, XC, true>(p, threads, s);
             return launch_rollout_g<MODEL, NA, NCH, LSEG, F64, XC, true>(p, threads, s);
         }
+    if constexpr (quiet_geom<MODEL, NCH, LSEG, XC>())
+        if (quiet) return launch_rollout_gq<MODEL, NA, NCH, LSEG, F64, XC, false>(p, threads, s);
     return launch_rollout_g<MODEL, NA, NCH, LSEG, F64, XC, false>(p, threads, s);
 }
 

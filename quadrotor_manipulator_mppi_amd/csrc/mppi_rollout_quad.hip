@@ -78,12 +78,17 @@ __device__ __forceinline__ float qsum(float x) {
 // NWD dynamics waves per block (1 or 4): 16 rollouts per block while the grid stays at most
 // 1024 blocks (a small K spreads its noise tile and dynamics over the most CUs), 64 above
 // (fewer records for the finalize: its record loop is sequential in chunks).
-template <bool VONE, bool LIT, int NWD, int NT>
-__global__ void __launch_bounds__(NT) k_rollout_quad(const uint32_t seed_lo, const uint32_t seed_hi,
-                                                            const uint32_t step_arg, const uint32_t k_off,
-                                                            const int32_t noise_arg, const int32_t H,
-                                                            const float* __restrict__ u_prev, const DevParams pk) {
+// QUIET (k_rollout_quad_q): the rollout of a batch's step before its last, as k_rollout's quiet form
+// (mppi_rollout.h rollout_body): no trajectory stores or plane descriptor, no cost staging or store
+// run, no stored noise, no hand-off of the vehicle constants; the record is bit-identical.
+template <bool VONE, bool LIT, int NWD, int NT, bool QUIET>
+__device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                  const uint32_t step_arg, const uint32_t k_off,
+                                                  const int32_t noise_arg, const int32_t H,
+                                                  const float* __restrict__ u_prev, const DevParams& pk) {
     static_assert(NWD == 1 || NWD == kQWaves, "dynamics waves per block");
+    constexpr bool kTraj = !QUIET && !(MPPI_KO & 16), kCosts = !QUIET && !(MPPI_KO & 1024),
+                   kHand = !QUIET && !(MPPI_KO & 2048);
     static_assert(NT == kQThreads || (NWD == 1 && NT == kQThreadsWide), "block size");
     constexpr int QR = kQR * NWD;              // rollouts per block
     constexpr int kQPitch = QR * kQA + 1;      // LDS floats per t row of the eps tile (odd: the record
@@ -103,7 +108,7 @@ __global__ void __launch_bounds__(NT) k_rollout_quad(const uint32_t seed_lo, con
     float* const eps_t = qlds;
     float* const u_t = qlds + (H + 1) * kQPitch;
     const VehicleConst& vc = VONE ? pk.vc0 : pk.vc[v];
-    if (VONE && b == 0) {   // hand vc0 to the finalize (it reads vc[v])
+    if (kHand && VONE && b == 0) {   // hand vc0 to the finalize (it reads vc[v])
         constexpr int kVCW = (int)(sizeof(VehicleConst) / 4);
         for (int i = tid; i < kVCW; i += NT)   // (written through: k_rollout's drain_stores)
             __hip_atomic_store((int*)pk.vc + i, i == kVcStepWord ? (int)step_ctr : ((const int*)&pk.vc0)[i],
@@ -122,7 +127,7 @@ __global__ void __launch_bounds__(NT) k_rollout_quad(const uint32_t seed_lo, con
 #pragma unroll
     for (int d = 0; d < 3; ++d) { tg3[d] = uniform_f32(vc.tpos[d]); ii3[d] = p.q_iinv[d]; }
     float sdt = p.dt, sim = p.q_inv_m, skd = p.q_kd, sg = p.q_g, swsp = p.w_sp, swtp = p.w_tp, scoef = p.coef;
-    const int sstore = p.store_traj;
+    const int sstore = kTraj ? p.store_traj : 0;
     // one asm consumes them all: the loads issue together and are waited for once
     asm volatile("" : "+s"(x6[0]), "+s"(x6[1]), "+s"(x6[2]), "+s"(x6[3]), "+s"(x6[4]), "+s"(x6[5]),
                       "+s"(v6[0]), "+s"(v6[1]), "+s"(v6[2]), "+s"(v6[3]), "+s"(v6[4]), "+s"(v6[5]),
@@ -157,7 +162,7 @@ __global__ void __launch_bounds__(NT) k_rollout_quad(const uint32_t seed_lo, con
         float* dst = eps_t + t * kQPitch + r * kQA;
 #pragma unroll
         for (int a = 0; a < kQA; ++a) dst[a] = eps[a];
-        if (p.store_noise && kval) {   // (readback only: written through, st_dev)
+        if (!QUIET && p.store_noise && kval) {   // (readback only: written through, st_dev)
             float* dst = p.noise_out + (((size_t)v * K + k) * H + t) * kQA;
 #pragma unroll
             for (int a = 0; a < kQA; ++a) st_dev(dst + a, eps[a]);
@@ -188,12 +193,13 @@ __global__ void __launch_bounds__(NT) k_rollout_quad(const uint32_t seed_lo, con
     // 3 + j (angle) of sample k; a store instruction covers 16 consecutive k (64 B) of 3
     // planes.  Rows are padded to Kp = K rounded up to 16 (pk.hp) and the lanes past K write
     // the pad (sample K-1's values), so a ragged K leaves no partial 64 B sector
-    const int kp = pk.hp;
+    const int kp = kTraj ? pk.hp : 0;
     const uint32_t plane_b = (uint32_t)kp * (uint32_t)H * 4u;
-    const __amdgpu_buffer_rsrc_t trs = traj_rsrc(pk.traj + (size_t)v * pk.C * kp * H, plane_b, pk.C);
+    const __amdgpu_buffer_rsrc_t trs = traj_rsrc(kTraj ? pk.traj + (size_t)v * pk.C * kp * H : nullptr, plane_b,
+                                                 kTraj ? pk.C : 0);
     const uint32_t off_p = (uint32_t)(k < kp ? k : kc) * 4u + (uint32_t)jj * plane_b, off_e = off_p + 3u * plane_b;
     const uint32_t tstep_b = (uint32_t)kp * 4u;
-    const bool store = sstore != 0;
+    const bool store = kTraj && sstore != 0;
     float stage = 0.0f, term = 0.0f;
     const float a0 = (j == 0) ? 1.0f : 0.0f;   // J's column 0 is (1, 0, 0)
     // v = u + eps (drone_mppi.py:144): thrust and this axis' torque.  The LDS operands are
@@ -268,7 +274,7 @@ __global__ void __launch_bounds__(NT) k_rollout_quad(const uint32_t seed_lo, con
     stage = qbc<0>(stage) + qbc<1>(stage) + qbc<2>(stage);
     term = qbc<0>(term) + qbc<1>(term) + qbc<2>(term);
     const float S = kval ? (swsp * stage) + (swtp * term) : INFINITY;
-    if (j == 0) s_lds[r] = S;
+    if (kCosts && j == 0) s_lds[r] = S;
     // ---- online softmin over the block's rollouts (mppi.py:184-188 / drone_mppi.py:111-130)
     const bool mine = kval && j == 0, bad = S != S;
     float rho = wave_fold_all((mine && !bad) ? S : INFINITY, OpMin());
@@ -283,7 +289,7 @@ __global__ void __launch_bounds__(NT) k_rollout_quad(const uint32_t seed_lo, con
     float eta = wave_fold_all(e, OpAdd()), eta2 = wave_fold_all(e * e, OpAdd());
     if (j == 0) e_lds[r] = e;
     wave_lds_handoff();
-    {   // this wave's 16 costs as one write-through 64 B run (mppi_device.h st_dev_run)
+    if constexpr (kCosts) {   // this wave's 16 costs as one write-through 64 B run (mppi_device.h st_dev_run)
         const int k0 = kb + wid * kQR, n = min(kQR, K - k0);
         if (lane < 4) st_dev_run(uniform_ptr(p.S + (size_t)v * K), (uint32_t)k0, s_lds + wid * kQR, n, lane);
     }
@@ -325,6 +331,22 @@ __global__ void __launch_bounds__(NT) k_rollout_quad(const uint32_t seed_lo, con
     drain_stores();
 }
 
+template <bool VONE, bool LIT, int NWD, int NT>
+__global__ void __launch_bounds__(NT) k_rollout_quad(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                            const uint32_t step_arg, const uint32_t k_off,
+                                                            const int32_t noise_arg, const int32_t H,
+                                                            const float* __restrict__ u_prev, const DevParams pk) {
+    rollout_quad_body<VONE, LIT, NWD, NT, false>(seed_lo, seed_hi, step_arg, k_off, noise_arg, H, u_prev, pk);
+}
+// the quiet form (a new symbol: k_rollout_quad's names stay as they are), same arguments
+template <bool VONE, bool LIT, int NWD, int NT>
+__global__ void __launch_bounds__(NT) k_rollout_quad_q(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                              const uint32_t step_arg, const uint32_t k_off,
+                                                              const int32_t noise_arg, const int32_t H,
+                                                              const float* __restrict__ u_prev, const DevParams pk) {
+    rollout_quad_body<VONE, LIT, NWD, NT, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg, H, u_prev, pk);
+}
+
 extern "C" int mppi_launch_rollout_quad(const DevParams* p, int threads, void* stream) {
     (void)threads;   // block size chosen below; p->iters = dynamics waves per block (1 or 4)
     const int nwd = p->iters;
@@ -332,14 +354,25 @@ extern "C" int mppi_launch_rollout_quad(const DevParams* p, int threads, void* s
     const size_t lds = (size_t)((p->H + 1) * (kQR * nwd * kQA + 1) + (p->H + 1) * kQA) * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
     const bool wide = nwd == 1 && (size_t)p->nb * p->V <= 512;
+    const bool quiet = quiet_launch(*p);   // (a batch's step before its last: mppi_rollout.h)
 #define MPPI_QUAD_GO(VO, LI, NW, NT)                                                                             \
+    do {                                                                                                         \
+    if (quiet)                                                                                                   \
+        return go(k_rollout_quad_q<VO, LI, NW, NT>,                                                              \
+                  [](char* b, size_t n) {                                                                        \
+                      snprintf(b, n, "_Z16k_rollout_quad_qILb%dELb%dELi%dELi%dEEvjjjjiiPKfN4mppi9DevParamsE",    \
+                               (int)VO, (int)LI, NW, NT);                                                        \
+                  },                                                                                             \
+                  dim3(p->nb, p->V), dim3(NT), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,                      \
+                  (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, *p);                                    \
     return go(k_rollout_quad<VO, LI, NW, NT>,                                                                    \
               [](char* b, size_t n) {                                                                            \
                   snprintf(b, n, "_Z14k_rollout_quadILb%dELb%dELi%dELi%dEEvjjjjiiPKfN4mppi9DevParamsE", (int)VO, \
                            (int)LI, NW, NT);                                                                     \
               },                                                                                                 \
               dim3(p->nb, p->V), dim3(NT), lds, s, p->seed_lo, p->seed_hi, p->step_ctr, (uint32_t)p->k_offset,   \
-              p->noise_mode, p->H, p->u_prev, *p)
+              p->noise_mode, p->H, p->u_prev, *p);                                                               \
+    } while (0)
 #define MPPI_QUAD_NW(VO, LI)                                                                                     \
     do {                                                                                                         \
         if (wide) MPPI_QUAD_GO(VO, LI, 1, kQThreadsWide);                                                        \

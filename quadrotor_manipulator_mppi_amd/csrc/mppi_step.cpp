@@ -45,9 +45,25 @@ void final_records(const mppi_engine* e, FinParams& f) {
 
 using namespace mppi_host;
 
-extern "C" {
+// A batch's steps before its last may run the quiet FINAL (mppi_finalize.hip kRoleQuiet: u_prev and
+// nothing else; the outputs of a batch are those of its last step).  Engines with stamps, timing
+// or output diagnostics, the overlap experiment and MPPI_GENERIC_KERNELS keep the full kernel on
+// every step; so does the launcher where no quiet kernel applies (the geometry, a peer exchange).
+static bool quiet_steps(const mppi_engine* e) {
+    return !(e->generic & 3) && !e->timing && !e->d_stamps && !e->d_fstamps && !e->out_dbg && !e->no_flag_dbg && !e->overlap;
+}
 
-mppi_status mppi_rollout(mppi_engine* e, const float* d_noise) {
+// Those steps' rollouts likewise run the quiet rollout (mppi_rollout.h rollout_body QUIET: the
+// records and nothing else), so a batch's trajectory planes, costs and handed-over vehicle
+// constants are its last step's.  Not on a peer engine (the exchange's tag rides in the handed-over
+// step word every step) or a shard (its PACK and collective are left as they are); the launcher
+// keeps the full kernel where no quiet one applies (stored or injected noise, the extended kernels,
+// other geometries).
+static bool quiet_rollout(const mppi_engine* e) {
+    return quiet_steps(e) && !(e->generic & 8) && !e->peer && !sharded(e);
+}
+
+static mppi_status rollout_impl(mppi_engine* e, const float* d_noise, bool quiet) {
     if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
     if (!e->state_set) return fail(MPPI_ERR_STATE, "mppi_rollout before mppi_set_state");
     if (e->cfg.noise_mode == MPPI_NOISE_INJECTED && !d_noise)
@@ -59,6 +75,7 @@ mppi_status mppi_rollout(mppi_engine* e, const float* d_noise) {
     p.noise_in = d_noise;
     p.vc0 = e->h_vc[0];
     p.step_ctr = e->step_ctr;
+    if (quiet && quiet_rollout(e)) p.kern |= kRollKernQuiet;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (e->timing) { e0 = pool_event(e); e1 = pool_event(e); HIP_TRY(hipEventRecord(e0, e->stream)); }
     int rc = mppi_launch_rollout(&p, e->threads, e->stream);
@@ -81,13 +98,9 @@ mppi_status mppi_rollout(mppi_engine* e, const float* d_noise) {
     return MPPI_OK;
 }
 
-// A batch's steps before its last may run the quiet FINAL (mppi_finalize.hip kRoleQuiet: u_prev and
-// nothing else; the outputs of a batch are those of its last step).  Engines with stamps, timing
-// or output diagnostics, the overlap experiment and MPPI_GENERIC_KERNELS keep the full kernel on
-// every step; so does the launcher where no quiet kernel applies (the geometry, a peer exchange).
-static bool quiet_steps(const mppi_engine* e) {
-    return !(e->generic & 3) && !e->timing && !e->d_stamps && !e->d_fstamps && !e->out_dbg && !e->no_flag_dbg && !e->overlap;
-}
+extern "C" {
+
+mppi_status mppi_rollout(mppi_engine* e, const float* d_noise) { return rollout_impl(e, d_noise, false); }
 
 // The symbol a launch would run, by the launchers' own description of it (mppi_device.h go()).
 static std::string fin_symbol(const FinParams& f) {
@@ -104,9 +117,11 @@ static std::string roll_symbol(const DevParams& p, int threads) {
     mppi_aql::set_capture(nullptr);
     return rc == 0 ? d.symbol : "?";
 }
-static std::string kernels_text(const std::string& roll, const std::string& fin, const std::string* quiet) {
+static std::string kernels_text(const std::string& roll, const std::string& fin, const std::string* quiet,
+                                const std::string* roll_quiet = nullptr) {
     std::string s = "rollout " + roll + ", finalize " + fin;
     if (quiet) s += ", quiet finalize " + (*quiet == fin ? std::string("none") : *quiet);
+    if (roll_quiet) s += ", quiet rollout " + (*roll_quiet == roll ? std::string("none") : *roll_quiet);
     return s;
 }
 
@@ -440,6 +455,7 @@ static mppi_status run_steps_aql(mppi_engine* e, int32_t n, bool* used) {
     LaunchDesc& roll = e->batch_roll;
     LaunchDesc& fin = e->batch_fin;
     LaunchDesc& finq = e->batch_fin_quiet;   // every step's but the last (quiet_steps)
+    LaunchDesc& rollq = e->batch_roll_quiet; // likewise (quiet_rollout)
     DevParams p = e->dp;
     p.noise_in = nullptr;
     p.vc0 = e->h_vc[0];
@@ -457,6 +473,12 @@ static mppi_status run_steps_aql(mppi_engine* e, int32_t n, bool* used) {
         e->kern_batch_state = 0;
         mppi_aql::set_capture(&roll);
         int rc = mppi_launch_rollout(&p, e->threads, e->stream);
+        if (rc == 0) {
+            DevParams pq = p;
+            if (quiet_rollout(e)) pq.kern |= kRollKernQuiet;
+            mppi_aql::set_capture(&rollq);
+            rc = mppi_launch_rollout(&pq, e->threads, e->stream);
+        }
         if (rc == 0) {
             mppi_aql::set_capture(&fin);
             rc = mppi_launch_finalize(&f, e->stream);
@@ -477,7 +499,7 @@ static mppi_status run_steps_aql(mppi_engine* e, int32_t n, bool* used) {
     std::string err;
     const auto c2 = now();
     const auto guard = mppi_aql::step_guard(e->aql);   // (no prewarm touch between prepare and dispatch)
-    const int pr = mppi_aql::step_prepare(e->aql, roll, fin, finq, e->step_ctr, kRollStepOff, &err);
+    const int pr = mppi_aql::step_prepare(e->aql, roll, rollq, fin, finq, e->step_ctr, kRollStepOff, &err);
     const auto c3 = now();
     if (pr == -2) {   // not dispatchable natively (a kernel the code objects lack, hidden arguments)
         e->aql_off = true;
@@ -505,9 +527,9 @@ static mppi_status run_steps_aql(mppi_engine* e, int32_t n, bool* used) {
     e->aql_out = true;
     e->aql_call = false;
     e->aql_why.clear();
-    if (e->kern_batch_state != (n > 1 ? 2 : 1)) {   // (mppi_kernel_info; a one-step batch runs no quiet finalize)
-        const std::string q = n > 1 ? finq.symbol : fin.symbol;
-        e->kern_batch = kernels_text(roll.symbol, fin.symbol, &q);
+    if (e->kern_batch_state != (n > 1 ? 2 : 1)) {   // (mppi_kernel_info; a one-step batch runs no quiet kernels)
+        const std::string q = n > 1 ? finq.symbol : fin.symbol, rq = n > 1 ? rollq.symbol : roll.symbol;
+        e->kern_batch = kernels_text(roll.symbol, fin.symbol, &q, &rq);
         e->kern_batch_state = n > 1 ? 2 : 1;
     }
     *used = true;
@@ -622,7 +644,7 @@ mppi_status mppi_run_steps(mppi_engine* e, int32_t n) {
     mppi_status st = run_steps_aql(e, n, &used);
     if (st != MPPI_OK || used) return st;
     for (int i = 0; i < n; ++i) {
-        mppi_status st = mppi_rollout(e, nullptr);
+        mppi_status st = rollout_impl(e, nullptr, i < n - 1);
         if (st != MPPI_OK) return st;
         if (e->comm && (st = mppi_exchange(e)) != MPPI_OK) return st;
         if ((st = finalize_impl(e, i == n - 1, true)) != MPPI_OK) return st;
@@ -635,8 +657,10 @@ mppi_status mppi_run_steps(mppi_engine* e, int32_t n) {
         final_records(e, f);
         const std::string full = fin_symbol(f);
         if (n > 1 && quiet_steps(e)) f.kern |= kFinKernQuiet;
-        const std::string q = fin_symbol(f);
-        e->kern_batch = kernels_text(roll_symbol(p, e->threads), full, &q);
+        const std::string q = fin_symbol(f), roll = roll_symbol(p, e->threads);
+        if (n > 1 && quiet_rollout(e)) p.kern |= kRollKernQuiet;
+        const std::string rq = roll_symbol(p, e->threads);
+        e->kern_batch = kernels_text(roll, full, &q, &rq);
         e->kern_batch_state = 0;
     }
     return MPPI_OK;
@@ -645,11 +669,12 @@ mppi_status mppi_run_steps(mppi_engine* e, int32_t n) {
 // The kernels the last mppi_run_steps and the last mppi_step ran: for each, the rollout's and the
 // finalize's symbols (the instantiations' Itanium names, as the code objects hold them), and for a
 // batch the quiet finalize of its steps before the last ("none": every step ran the full one).
+// A batch also names the quiet rollout of those steps, likewise.
 // "; MPPI_GENERIC_KERNELS" at the end when the engine was created with that switch.
 mppi_status mppi_kernel_info(mppi_engine* e, char* buf, int32_t len) {
     if (!e || !buf || len <= 0) return fail(MPPI_ERR_INVALID_ARG, "mppi_kernel_info: bad arguments");
     snprintf(buf, (size_t)len, "batch: %s; call: %s%s", e->kern_batch.c_str(), e->kern_call.c_str(),
-             e->generic == 7 ? "; MPPI_GENERIC_KERNELS" : e->generic ? "; MPPI_GENERIC_KERNELS (in part)" : "");
+             e->generic == kGenericAll ? "; MPPI_GENERIC_KERNELS" : e->generic ? "; MPPI_GENERIC_KERNELS (in part)" : "");
     return MPPI_OK;
 }
 
@@ -679,6 +704,28 @@ int32_t mppi_debug_finalize_kernels(const int32_t* g, char* full, char* quiet, i
     const std::string a = fin_symbol(f);
     if (!g[9]) f.kern |= kFinKernQuiet;   // (as quiet_steps: not under MPPI_GENERIC_KERNELS)
     const std::string b = fin_symbol(f);
+    snprintf(full, (size_t)len, "%s", a.c_str());
+    snprintf(quiet, (size_t)len, "%s", b.c_str());
+    return (a == "?" || b == "?") ? MPPI_ERR_INVALID_ARG : MPPI_OK;
+}
+
+// Likewise the rollout kernels of a batch -- g = {model, A, H, L, nch, iters, block threads, V,
+// state_f64, noise mode, store_noise, cost_terms, full Sigma, peer exchange, MPPI_GENERIC_KERNELS}:
+// the last step's into `full`, the earlier steps' into `quiet` (the same symbol where the full
+// kernel runs on every step).  tests/test_capi_quiet_rollout_cpu.py.
+int32_t mppi_debug_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len) {
+    if (!g || !full || !quiet || len <= 0) return MPPI_ERR_INVALID_ARG;
+    DevParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.model = g[0]; p.A = g[1]; p.H = g[2]; p.L = g[3]; p.nch = g[4]; p.iters = g[5]; p.V = g[7];
+    p.R = p.L > 0 ? 64 / p.L : 0;
+    p.state_f64 = g[8]; p.noise_mode = g[9]; p.store_noise = g[10]; p.cost_terms = g[11]; p.sigma_diag = !g[12];
+    p.nb = 16; p.K = 16; p.store_traj = 1;
+    p.chain_fast = 2;
+    p.kern = g[14] ? kRollKernGeneric : 0;
+    const std::string a = roll_symbol(p, g[6]);
+    if (!g[13] && !g[14]) p.kern |= kRollKernQuiet;   // (as quiet_rollout: no peer exchange, not under MPPI_GENERIC_KERNELS)
+    const std::string b = roll_symbol(p, g[6]);
     snprintf(full, (size_t)len, "%s", a.c_str());
     snprintf(quiet, (size_t)len, "%s", b.c_str());
     return (a == "?" || b == "?") ? MPPI_ERR_INVALID_ARG : MPPI_OK;

@@ -358,7 +358,8 @@ class Engine:
 
     def kernel_info(self) -> str:
         """Which kernels the last run_steps / step ran: "batch: rollout <symbol>, finalize <symbol>,
-        quiet finalize <symbol | none>; call: rollout <symbol>, finalize <symbol>"."""
+        quiet finalize <symbol | none>, quiet rollout <symbol | none>; call: rollout <symbol>,
+        finalize <symbol>"."""
         buf = C.create_string_buffer(1024)
         capi.check(self._L.mppi_kernel_info(self._h, buf, len(buf)), "kernel_info")
         return buf.value.decode(errors="replace")
