@@ -102,7 +102,22 @@ struct GeoRt { static constexpr bool kStatic = false; static constexpr int A = 0
 template <int A_, int H_, int TSZ_, int HF_, int TS_>
 struct GeoC { static constexpr bool kStatic = true; static constexpr int A = A_, H = H_, tsz = TSZ_, hf = HF_, ts = TS_; };
 
-template <int CW, int WIN, int NT, int ROLE, typename GEO>
+// Lane maps (CPL = window columns per lane).  CPL = 1 is the map above.  CPL = 4 or 2 (CW = 16 only; the
+// role kernels, kFinCPL): a lane takes CPL consecutive columns of its records with ONE body load (b128 /
+// b64), so a block of record-capacity class NT runs NT / CPL threads and each CU issues 1 / CPL of the
+// record loads (headers too: a row's header is fetched by CW / CPL lanes instead of CW).  The rows a lane
+// folds, their order and every operation on them are those of lane group (wv, g) of the CPL = 1 map --
+// "sequence" s = 4 wv + g -- so the result is bit-identical:
+//   the low log2(LPR) lane bits = column group (LPR = CW / CPL lanes per row: adjacent lanes, adjacent columns),
+//   bits 3..4 = g (the wave fold's two levels are then lane xor 8 = row_ror:8 and xor 16 =
+//   v_permlane16_swap: the same pairs (g0, g1), (g2, g3), then the two sums, as fold_rows), and the
+//   remaining bits (bit 2 at CPL = 4, bit 5) with the wave index = wv of the CPL = 1 map.
+// The window is read from its start aligned down to a multiple of CPL columns (the drone's and the
+// quadrotor's start at sl*8 - 2): CW = 16 still covers it, and the columns before the window and past
+// its end are dropped where the fold is handed on (a select: they hold other columns' sums).  Each
+// sequence's fold goes to LDS under its CPL = 1 wave index and window column, so the combine of the
+// waves and the tail below are the same code; a block of one wave needs no block barrier for it.
+template <int CW, int WIN, int NT, int ROLE, typename GEO, int CPL = 1>
 __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, const float* __restrict__ dat_base,
                                          const FinTail* __restrict__ tail, const uint32_t nrec_H, const uint32_t geo,
                                          const int32_t hdr_rs, const int32_t d_rs, const int32_t d_as,
@@ -117,6 +132,9 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
     constexpr int ROWS = 64 / CW;          // rows per wave
     constexpr int TR = NWV * ROWS;         // rows per block
     constexpr int kNPT = 16;
+    static_assert(CPL == 1 || ((CPL == 2 || CPL == 4) && CW == 16 && NT / CPL >= 32), "lane maps: see above");
+    constexpr int LPR = CW / CPL;                          // lanes per row
+    constexpr int kLanes = NT / CPL < 64 ? NT / CPL : 64;   // lanes of wave 0 (the tail's wave)
     __shared__ float wcol[NWV][CW];
     __shared__ float wrho[NWV], wnan[NWV], weta[NWV], weta2[NWV];
     __shared__ float wsg[96];   // wave 0: w over the window + reflected pads (SavGol taps by LDS reads)
@@ -145,10 +163,16 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
     // (both bases and the header range kept in SGPRs: in a build where the compiler put one
     // in VGPRs, every record load became a waterfall loop over a "divergent" resource)
     const float* hdr = uniform_ptr(hdr_base + (size_t)v * (uint32_t)hdr_vs);
-    const float* col = uniform_ptr(dat_base + (size_t)v * (uint32_t)d_vs + (size_t)a * d_as + w0);
+    const int doff = CPL == 1 ? 0 : w0 & (CPL - 1);   // the window starts at column doff of the columns read
+    const float* col = uniform_ptr(dat_base + (size_t)v * (uint32_t)d_vs + (size_t)a * d_as + (CPL == 1 ? w0 : w0 - doff));
     const FinTail& T = *tail;
-    const int g = lane / CW, q = lane - g * CW, gr = wv * ROWS + g;
-    const bool qv = q < W;
+    // CPL = 1: lane (g, q) of wave wv.  CPL > 1: lane (sequence 4 wo + g, column group q), wo the CPL = 1
+    // wave index
+    const int g = CPL == 1 ? lane / CW : (lane >> 3) & 3, q = CPL == 1 ? lane - g * CW : lane & (LPR - 1);
+    const int wo = CPL == 1 ? wv : CPL == 4 ? wv * 4 + (((lane >> 2) & 1) | ((lane >> 5) << 1)) : wv * 2 + (lane >> 5);
+    const int gr = wo * ROWS + g;
+    const int nqd = (doff + W + CPL - 1) / CPL;   // column groups that reach into the window
+    const bool qv = CPL == 1 ? q < W : q < nqd;
     // wave 0's u_prev over the window (lane q <-> t = w0 + q, incl. the OLD u_prev[0],
     // mppi.py:157) and the vehicle constants of the outputs (slice 0 of each dim, lane 0) are
     // loaded AFTER the first chunk of record loads is issued (pin_tail below): they need the
@@ -233,7 +257,11 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
         if constexpr (kUpd) {
             up += (size_t)v * H * A;
             // (device-scope loads: the previous finalize's u_prev, the rollout's handed-over vc)
-            if (wv == 0 && q < W && g == 0) u_old = ld_dev(up + (w0 + q) * A + a);
+            if constexpr (CPL == 1) {
+                if (wv == 0 && q < W && g == 0) u_old = ld_dev(up + (w0 + q) * A + a);
+            } else {   // (the tail's lanes: wave 0, lane = window column)
+                if (wv == 0 && lane < W) u_old = ld_dev(up + (w0 + lane) * A + a);
+            }
         }
         if constexpr (kOut) {
             if (tid == 0 && sl == 0) {
@@ -260,7 +288,10 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
     // column of a row group, so each lane carries them and the wave fold runs over row groups
     // only.  eta in fp32, like the reference's torch.sum of the fp32 exponentials
     // (mppi.py:184-188): <= 16 terms per lane, then 2 + 3 (8 waves) folds.
-    float rho_t = INFINITY, acc = 0.0f, nanflag = 0.0f, eta = 0.0f, eta2 = 0.0f;
+    float rho_t = INFINITY, nanflag = 0.0f, eta = 0.0f, eta2 = 0.0f;
+    float acc[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) acc[j] = 0.0f;
     // Record loads through buffer resources over this vehicle's headers and this (dim,
     // window)'s body columns: each load is one 32-bit VGPR offset (a full-rate add per row)
     // instead of a 64-bit address (v_mad_u64_u32 + v_lshl_add_u64, both quarter-rate: ~380
@@ -272,23 +303,37 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
                                           0x00020000);
     // (the range is block-uniform, but its W reaches the compiler through VGPR math: without
     // readfirstlane every body load became a waterfall loop over a "divergent" resource)
+    // (CPL > 1: whole column groups of the last row; they end at or before the row's end, w1 <= H
+    // and H a multiple of 4 at every table geometry)
     const __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(col), 0, __builtin_amdgcn_readfirstlane((int)((uint32_t)(n - 1) * drs_b + (uint32_t)W * 4u)),
+        const_cast<float*>(col), 0,
+        __builtin_amdgcn_readfirstlane((int)((uint32_t)(n - 1) * drs_b + (uint32_t)(CPL == 1 ? W : nqd * CPL) * 4u)),
         0x00020000);
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     for (int base = 0; base < n; base += TR * kNPT) {
         float4 hd[kNPT];
-        float xv[kNPT];
+        float xv[kNPT][CPL];
         uint32_t okm = 0;   // rows past n are masked at use: a select on the loaded value
                             // here made the compiler wait for each load in turn
         const uint32_t r0 = (uint32_t)(base + gr);
-        const uint32_t hoff = r0 * hrs_b, coff = r0 * drs_b + (uint32_t)(qv ? q : 0) * 4u;
+        const uint32_t hoff = r0 * hrs_b, coff = r0 * drs_b + (uint32_t)(qv ? q : 0) * (uint32_t)(4 * CPL);
 #pragma unroll
         for (int i = 0; i < kNPT; ++i) {
             okm |= (uint32_t)(r0 + (uint32_t)(i * TR) < (uint32_t)n) << i;
             const u32x4 h = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, (int)(hoff + (uint32_t)(i * TR) * hrs_b), 0, kAuxDev);
             hd[i] = make_float4(__uint_as_float(h.x), __uint_as_float(h.y), __uint_as_float(h.z), __uint_as_float(h.w));
-            xv[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(crsrc, (int)(coff + (uint32_t)(i * TR) * drs_b), 0, kAuxDev));
+            const int bo = (int)(coff + (uint32_t)(i * TR) * drs_b);
+            if constexpr (CPL == 4) {
+                const u32x4 b = __builtin_amdgcn_raw_buffer_load_b128(crsrc, bo, 0, kAuxDev);
+                xv[i][0] = __uint_as_float(b.x); xv[i][1] = __uint_as_float(b.y);
+                xv[i][2] = __uint_as_float(b.z); xv[i][3] = __uint_as_float(b.w);
+            } else if constexpr (CPL == 2) {
+                const u32x2 b = __builtin_amdgcn_raw_buffer_load_b64(crsrc, bo, 0, kAuxDev);
+                xv[i][0] = __uint_as_float(b.x); xv[i][1] = __uint_as_float(b.y);
+            } else {
+                xv[i][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(crsrc, bo, 0, kAuxDev));
+            }
         }
         if (base == 0) {
             __builtin_amdgcn_sched_barrier(0);   // the first chunk's record loads issue first
@@ -312,7 +357,8 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
             const float rn = fminf(rho_t, m);
             if (rho_t < INFINITY) {   // rescale the running sums to the new reference
                 const float sc = __expf(coef * (rho_t - rn));
-                acc *= sc;
+#pragma unroll
+                for (int j = 0; j < CPL; ++j) acc[j] *= sc;
                 eta *= sc;
                 eta2 *= sc * sc;
             }
@@ -326,21 +372,49 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
             }
         }
 #pragma unroll
-        for (int i = 0; i < kNPT; ++i) acc = fmaf(fr[i], xv[i], acc);
+        for (int i = 0; i < kNPT; ++i) {
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) acc[j] = fmaf(fr[i], xv[i][j], acc[j]);
+        }
         FSTAMP(8);
     }
-    {   // fold the wave's row groups: rescale every lane to the wave's rho, sum the rows
+    if constexpr (CPL == 1) {   // fold the wave's row groups: rescale every lane to the wave's rho, sum the rows
         const float rw = fold_rows<CW>(rho_t, OpMin());
         const float sc = (rho_t < INFINITY) ? __expf(coef * (rho_t - rw)) : 0.0f;
-        acc = fold_rows<CW>(acc * sc, OpAdd());
+        acc[0] = fold_rows<CW>(acc[0] * sc, OpAdd());
         const float e1 = fold_rows<CW>(eta * sc, OpAdd()), e2 = fold_rows<CW>(eta2 * (sc * sc), OpAdd());
         const float nf = fold_rows<CW>(nanflag, OpMax());
-        if (lane < CW) wcol[wv][lane] = acc;
+        if (lane < CW) wcol[wv][lane] = acc[0];
         if (lane == 0) { wrho[wv] = rw; wnan[wv] = nf; weta[wv] = e1; weta2[wv] = e2; }
+    } else {   // the same fold over the four sequences of each CPL = 1 wave (lane bits 3 and 4)
+        auto fold_g = [](float x, auto op) {
+            // (x is a product at three of the calls: opaque here, or the compiler contracts it into the
+            // add -- fma(a, b, partner's rounded product), which differs between the two partners and
+            // from fold_rows, whose operands both come out of a swap already rounded)
+            asm volatile("" : "+v"(x));
+            x = op(x, dpp_all<0x128>(x));   // row_ror:8 = lane xor 8
+            const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+            return op(__uint_as_float(r[0]), __uint_as_float(r[1]));
+        };
+        const float rw = fold_g(rho_t, OpMin());
+        const float sc = (rho_t < INFINITY) ? __expf(coef * (rho_t - rw)) : 0.0f;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) acc[j] = fold_g(acc[j] * sc, OpAdd());
+        const float e1 = fold_g(eta * sc, OpAdd()), e2 = fold_g(eta2 * (sc * sc), OpAdd());
+        const float nf = fold_g(nanflag, OpMax());
+        if (g == 0) {
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) {
+                const int wq = q * CPL + j - doff;   // window column (the tail's lane)
+                if (wq >= 0 && wq < W) wcol[wo][wq] = acc[j];
+            }
+            if (q == 0) { wrho[wo] = rw; wnan[wo] = nf; weta[wo] = e1; weta2[wo] = e2; }
+        }
     }
     FSTAMP(1);
-    if (MPPI_FIN_KO & 8) { if (lane < CW) p.u_prev[lane] += acc + (float)eta; return; }   // timing knockout
-    lds_barrier();
+    if (MPPI_FIN_KO & 8) { if (lane < CW) p.u_prev[lane] += acc[0] + (float)eta; return; }   // timing knockout
+    if constexpr (NT / CPL <= 64) wave_lds_handoff();   // one wave: nothing to wait for but its own LDS stores
+    else lds_barrier();
     if (wv != 0) return;
     FSTAMP(2);
     // wave 0: combine the 4 waves (lane q = column q)
@@ -481,7 +555,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
                 while (__builtin_amdgcn_s_memrealtime() - t_rep < kDecGraceTicks) __builtin_amdgcn_s_sleep(8);
                 bool marked = false;   // any block of this rank marked this step (the words carry the tag:
                                        // an earlier step's marks never match)
-                for (size_t i = lane; i < nbk; i += 64) {
+                for (size_t i = lane; i < nbk; i += kLanes) {
                     const unsigned long long w = __hip_atomic_load(dw + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     marked |= (uint32_t)(w >> 32) == tag && ((uint32_t)w & 3u) == kDecCommit;
                 }
@@ -693,9 +767,14 @@ static int fin_geo_id(const FinParams* p) {
 }
 
 // One role, one table geometry: the same arguments as k_finalize (geo and the H half of nrec_H are
-// passed and not read).
+// passed and not read).  NT is the record-capacity class (the block size k_finalize would run the
+// shape at); the block is NT / kFinCPL threads (fin_body, lane maps).
+#ifndef MPPI_FIN_CPL
+#define MPPI_FIN_CPL 4   // window columns per lane of the role kernels: 4 (b128 body loads) or 2 (b64)
+#endif
+constexpr int kFinCPL = MPPI_FIN_CPL;
 template <int NT, int ROLE, int GID>
-__global__ void __launch_bounds__(NT) k_finalize_s(const float* __restrict__ hdr_base,
+__global__ void __launch_bounds__(NT / kFinCPL) k_finalize_s(const float* __restrict__ hdr_base,
                                                             const float* __restrict__ dat_base,
                                                             const FinTail* __restrict__ tail,
                                                             const uint32_t nrec_H, const uint32_t geo,
@@ -703,7 +782,7 @@ __global__ void __launch_bounds__(NT) k_finalize_s(const float* __restrict__ hdr
                                                             const int32_t d_as, const int32_t hdr_vs,
                                                             const int32_t d_vs, const uint32_t seq_arg,
                                                             const FinParams pk) {
-    fin_body<kFinGeoCW, FinGeo<GID>::win, NT, ROLE, typename FinGeo<GID>::type>(hdr_base, dat_base, tail, nrec_H, geo, hdr_rs,
+    fin_body<kFinGeoCW, FinGeo<GID>::win, NT, ROLE, typename FinGeo<GID>::type, kFinCPL>(hdr_base, dat_base, tail, nrec_H, geo, hdr_rs,
                                                                           d_rs, d_as, hdr_vs, d_vs, seq_arg, pk);
 }
 
@@ -784,8 +863,8 @@ extern "C" int mppi_launch_finalize(const FinParams* p, void* stream) {
                   snprintf(b, n, "_Z12k_finalize_sILi%dELi%dELi%dEEvPKfS1_PKN4mppi7FinTailEjjiiiiijNS2_9FinParamsE", \
                            NTV, ROLEV, GIDV);                                                             \
               },                                                                                          \
-              grid, block, 0, s, p->hdr, p->dat, p->tail, nh, geo, (int32_t)p->hdr_rs, (int32_t)p->d_rs,   \
-              (int32_t)p->d_as, (int32_t)p->hdr_vs, (int32_t)p->d_vs, p->seq, *p)
+              grid, dim3(NTV / kFinCPL), 0, s, p->hdr, p->dat, p->tail, nh, geo, (int32_t)p->hdr_rs,       \
+              (int32_t)p->d_rs, (int32_t)p->d_as, (int32_t)p->hdr_vs, (int32_t)p->d_vs, p->seq, *p)
 #define MPPI_FIN_SNT(ROLEV, GIDV)                                                                         \
     do {                                                                                                  \
         if (nt == 128) MPPI_FIN_SGO(128, ROLEV, GIDV);                                                    \

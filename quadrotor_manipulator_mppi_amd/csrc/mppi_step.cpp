@@ -103,11 +103,12 @@ extern "C" {
 mppi_status mppi_rollout(mppi_engine* e, const float* d_noise) { return rollout_impl(e, d_noise, false); }
 
 // The symbol a launch would run, by the launchers' own description of it (mppi_device.h go()).
-static std::string fin_symbol(const FinParams& f) {
+static std::string fin_symbol(const FinParams& f, LaunchDesc* desc = nullptr) {
     LaunchDesc d{};
     mppi_aql::set_capture(&d);
     const int rc = mppi_launch_finalize(&f, nullptr);
     mppi_aql::set_capture(nullptr);
+    if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
 static std::string roll_symbol(const DevParams& p, int threads) {
@@ -686,6 +687,7 @@ mppi_status mppi_dispatch_info(mppi_engine* e, char* buf, int32_t len) {
     return MPPI_OK;
 }
 
+static thread_local int32_t g_fin_launch[6];   // (mppi_debug_finalize_launch)
 // Diagnostic (not part of the public header; no GPU): the finalize kernels a batch's descriptions
 // would name for a launch of this shape -- g = {A, H, tsz, half, ts, window, nrec, mode, peer
 // exchange, MPPI_GENERIC_KERNELS}: the last step's into `full`, the earlier steps' into `quiet`
@@ -701,12 +703,28 @@ int32_t mppi_debug_finalize_kernels(const int32_t* g, char* full, char* quiet, i
     f.tail = &tail;
     if (g[8]) f.xpeers = peers;
     f.kern = g[9] ? kFinKernGeneric : 0;
-    const std::string a = fin_symbol(f);
+    LaunchDesc da{}, db{};
+    const std::string a = fin_symbol(f, &da);
     if (!g[9]) f.kern |= kFinKernQuiet;   // (as quiet_steps: not under MPPI_GENERIC_KERNELS)
-    const std::string b = fin_symbol(f);
+    const std::string b = fin_symbol(f, &db);
     snprintf(full, (size_t)len, "%s", a.c_str());
     snprintf(quiet, (size_t)len, "%s", b.c_str());
+    // the captured launches' geometry, as native dispatch would store it in its packets
+    // (mppi_debug_finalize_launch below)
+    const LaunchDesc* ds[2] = {&da, &db};
+    for (int i = 0; i < 2; ++i) {
+        g_fin_launch[3 * i] = (int32_t)ds[i]->block[0];
+        g_fin_launch[3 * i + 1] = (int32_t)ds[i]->grid[0];
+        g_fin_launch[3 * i + 2] = (int32_t)ds[i]->lds;
+    }
     return (a == "?" || b == "?") ? MPPI_ERR_INVALID_ARG : MPPI_OK;
+}
+
+// Diagnostic (no GPU): {block threads, grid.x, dynamic LDS bytes} of the two launches the calling
+// thread's last mppi_debug_finalize_kernels described, the full one then the quiet one.
+// tests/test_capi_finalize_quads_cpu.py.
+void mppi_debug_finalize_launch(int32_t* out6) {
+    if (out6) std::memcpy(out6, g_fin_launch, sizeof(g_fin_launch));
 }
 
 // Likewise the rollout kernels of a batch -- g = {model, A, H, L, nch, iters, block threads, V,
