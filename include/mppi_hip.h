@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define MPPI_ABI_VERSION 9
+#define MPPI_ABI_VERSION 10
 #define MPPI_COMM_ID_BYTES 128  /* ncclUniqueId */
 #define MPPI_PEER_HANDLE_BYTES 64  /* hipIpcMemHandle_t */
 #define MPPI_MAX_ACTION 16
@@ -410,6 +410,20 @@ mppi_status mppi_get_weights(mppi_engine* e, float* w);
 mppi_status mppi_get_noise(mppi_engine* e, float* eps);
 mppi_status mppi_get_trajectory(mppi_engine* e, float* traj);
 mppi_status mppi_get_weighted_noise(mppi_engine* e, float* raw, float* smoothed);
+
+/* The nominal plan: the rollout of the current warm start u_prev with zero noise from the current
+ * state (synchronous; any engine: single, fleet, sharded, peer -- u_prev is the same on every rank).
+ *   traj    (V,H,C)  C = mppi_traj_channels, the per-(t) layout of mppi_get_trajectory
+ *   cost_t  (V,H)    the step's share of S: every enabled term, stage weights for t < H-1, terminal at H-1
+ *   pos_err (V,H)    L1 distance of the EE (ARM, WHOLEBODY) or the vehicle (DRONE, QUADROTOR) position to
+ *                    the target: check_reach's measure (utils/pose.py:121-123) along the plan
+ *   S       (V)      the cost the rollout kernel gives this sample; sum_t cost_t
+ * Any pointer may be NULL.  The state and targets are the ones last set (mppi_set_state / mppi_step,
+ * mppi_set_target, mppi_set_joint_trajectory; zeros before the first), the controls the device's
+ * u_prev: a zero warm start gives the ballistic path, after a step it is the plan just committed to.
+ * One launch of k_plan on the engine's stream (one block per vehicle, lane = horizon step), outside
+ * the control step: nothing the step reads or writes is touched. */
+mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos_err, float* S);
 
 /* Kernel timing with HIP events on the engine stream (bench / roofline). */
 mppi_status mppi_enable_timing(mppi_engine* e, int32_t enable);

@@ -21,7 +21,7 @@ NOISE_PHILOX, NOISE_INJECTED = 0, 1
 JOINT_FIXED, JOINT_REVOLUTE, JOINT_PRISMATIC, JOINT_FLOATING = 0, 1, 2, 3
 OK, ERR_INVALID_ARG, ERR_HIP, ERR_NONFINITE, ERR_STATE, ERR_COMM, ERR_PEER_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
 COST_COVAR, COST_CENTER, COST_JOINT_TRACK, COST_ACTION, COST_JOINT_LIMIT = 1, 2, 4, 8, 16
-ABI_VERSION = 9
+ABI_VERSION = 10
 MAX_PEERS = 8
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 64
@@ -126,6 +126,7 @@ PROTOTYPES = {
     "mppi_get_noise": (_ST, [_P, _F]),
     "mppi_get_trajectory": (_ST, [_P, _F]),
     "mppi_get_weighted_noise": (_ST, [_P, _F, _F]),
+    "mppi_get_plan": (_ST, [_P, _F, _F, _F, _F]),
     "mppi_enable_timing": (_ST, [_P, C.c_int32]),
     "mppi_get_timing": (_ST, [_P, _D, _D, _I64, _I64]),
     "mppi_kernel_timing": (_ST, [_P, C.c_int32, _D, _D]),

@@ -244,6 +244,16 @@ struct LaunchDesc {
 // FINAL's outputs are never read (a batch's step before its last): u_prev and nothing else.
 constexpr int32_t kFinKernGeneric = 1, kFinKernQuiet = 2;
 
+// The plan kernel's own parameters (mppi_plan.hip k_plan; mppi_get_plan): the vehicle constants as
+// the host holds them and the engine-owned outputs.  Everything else it reads from DevParams.
+struct PlanParams {
+    const VehicleConst* vc;  // (V) a device copy of the host's current constants (state, targets)
+    float* traj;             // (V,C,H) SoA planes: the state channels, then the EE rows (ARM, WHOLEBODY)
+    float* cost_t;           // (V,H) the step's share of S
+    float* pos_err;          // (V,H) L1 distance of the EE / vehicle position to the target
+    float* S;                // (V)
+};
+
 // Finalize / pack kernel parameters.
 struct FinParams {
     int32_t model, V, H, A, nq, qoff, state_f64;
@@ -297,6 +307,7 @@ int mppi_launch_rollout_arm32(const mppi::DevParams* p, int block_threads, void*
 int mppi_launch_rollout_wb(const mppi::DevParams* p, int block_threads, void* stream);
 int mppi_launch_rollout_quad(const mppi::DevParams* p, int block_threads, void* stream);
 int mppi_launch_finalize(const mppi::FinParams* p, void* stream);
+int mppi_launch_plan(const mppi::DevParams* p, const mppi::PlanParams* pp, void* stream);
 int mppi_launch_peer_probe(unsigned long long* const* peers, unsigned long long* local, int n, int me,
                            unsigned long long slot_words, uint32_t tag, unsigned long long ticks,
                            unsigned long long* out, void* stream);

@@ -540,10 +540,12 @@ void mppi_destroy(mppi_engine* e) {
     exchange_release(e);   // the communicator and the other ranks' mapped regions
     void* dev[] = {e->d_xregion, e->d_xpeers, e->d_sigma, e->d_joints, e->d_vc, e->d_u_prev, e->d_noise_in, e->d_traj, e->d_noise_out,
                    e->d_S, e->d_hdr, e->d_rdata, e->d_out, e->d_wraw, e->d_wsmooth, e->d_w,
-                   e->d_sinv, e->d_gamma, e->d_jtraj, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec};
+                   e->d_sinv, e->d_gamma, e->d_jtraj, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec,
+                   e->d_plan_vc, e->d_plan};
     for (void* p : dev) if (p) (void)hipFree(p);
     if (e->h_out) (void)hipHostFree(e->h_out);
     if (e->h_vc) (void)hipHostFree(e->h_vc);
+    if (e->h_plan) (void)hipHostFree(e->h_plan);
     if (e->ev_vc) (void)hipEventDestroy(e->ev_vc);
     if (e->ev_out) (void)hipEventDestroy(e->ev_out);
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -808,6 +810,61 @@ mppi_status mppi_get_weighted_noise(mppi_engine* e, float* raw, float* smoothed)
     if (raw) HIP_TRY(hipMemcpyAsync(raw, e->d_wraw, n, hipMemcpyDeviceToHost, e->stream));
     if (smoothed) HIP_TRY(hipMemcpyAsync(smoothed, e->d_wsmooth, n, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return MPPI_OK;
+}
+
+// The nominal plan: k_plan (mppi_plan.hip) on the engine's stream, ordered like the READBACK launch
+// above (use_device joins a native batch first), then the copies and one synchronise.  The vehicle
+// constants are the host's (build_vehicle_consts: the last state and targets set), copied into a
+// buffer of the plan's own: vc[0] in device memory is whatever the last rollout handed over.
+mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos_err, float* S) {
+    if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
+    if (use_device(e)) return MPPI_ERR_HIP;
+    const size_t V = (size_t)e->V, H = (size_t)e->H, C = (size_t)e->C;
+    const size_t n_traj = V * C * H, n_vh = V * H;
+    const size_t n_all = n_traj + 2 * n_vh + V;
+    if (!e->h_plan) {
+        if (!e->d_plan_vc) HIP_TRY(hipMalloc(&e->d_plan_vc, sizeof(VehicleConst) * V));
+        if (!e->d_plan) HIP_TRY(hipMalloc(&e->d_plan, sizeof(float) * n_all));
+        HIP_TRY(hipHostMalloc((void**)&e->h_plan, sizeof(float) * n_all, hipHostMallocDefault));
+    }
+    if (!e->state_set) {   // no state yet: the constants of the zero state and the targets as they stand
+        mppi_status st = build_vehicle_consts(e);
+        if (st != MPPI_OK) return st;
+    }
+    PlanParams pp;
+    pp.vc = e->d_plan_vc;
+    pp.traj = e->d_plan; pp.cost_t = pp.traj + n_traj; pp.pos_err = pp.cost_t + n_vh; pp.S = pp.pos_err + n_vh;
+    HIP_TRY(hipMemcpyAsync(e->d_plan_vc, e->h_vc, sizeof(VehicleConst) * V, hipMemcpyHostToDevice, e->stream));
+    const int rc = mppi_launch_plan(&e->dp, &pp, e->stream);
+    if (rc != 0) return fail(MPPI_ERR_HIP, "plan launch failed (%d: %s)", rc,
+                             rc > 0 ? hipGetErrorString((hipError_t)rc) : "no kernel for this model/A/H");
+    // ONE copy of the block into pinned memory (each copy into the caller's pageable arrays cost
+    // ~12 us of the call: profiles/r10/plan), from the first output asked for; handed out below
+    const size_t first = traj ? 0 : n_traj;
+    if (traj || cost_t || pos_err || S)
+        HIP_TRY(hipMemcpyAsync(e->h_plan + first, e->d_plan + first, (n_all - first) * sizeof(float),
+                               hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (cost_t) std::memcpy(cost_t, e->h_plan + n_traj, n_vh * sizeof(float));
+    if (pos_err) std::memcpy(pos_err, e->h_plan + n_traj + n_vh, n_vh * sizeof(float));
+    if (S) std::memcpy(S, e->h_plan + n_traj + 2 * n_vh, V * sizeof(float));
+    if (traj) {   // planes (V,C,H) -> (V,H,Cr), the per-(t) layout of mppi_get_trajectory
+        const int Cr = mppi_traj_channels(&e->cfg);
+        const bool has_ee = e->cfg.model == MPPI_MODEL_ARM || e->cfg.model == MPPI_MODEL_WHOLEBODY;
+        const int nstate = has_ee ? e->A : e->C;
+        for (size_t v = 0; v < V; ++v)
+            for (size_t t = 0; t < H; ++t) {
+                float* dst = traj + (v * H + t) * Cr;
+                const float* src = e->h_plan + v * C * H + t;
+                for (int c = 0; c < nstate; ++c) dst[c] = src[(size_t)c * H];
+                if (has_ee) {
+                    float* ee = dst + nstate;
+                    for (int r = 0; r < 12; ++r) ee[r] = src[(size_t)(nstate + r) * H];
+                    ee[12] = 0.0f; ee[13] = 0.0f; ee[14] = 0.0f; ee[15] = 1.0f;
+                }
+            }
+    }
     return MPPI_OK;
 }
 

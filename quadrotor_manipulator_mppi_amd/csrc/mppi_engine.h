@@ -96,6 +96,11 @@ struct mppi_engine {
     float* d_gamma = nullptr;     //   gamma^t (H)
     float* d_jtraj = nullptr;     //   joint tracking target (V,H,nq)
     float* d_exchange = nullptr;
+    // mppi_get_plan's buffers (allocated at its first call): the host's vehicle constants; the
+    // planes (V,C,H), cost_t (V,H), pos_err (V,H) and S (V) in one block, and its pinned host copy
+    mppi::VehicleConst* d_plan_vc = nullptr;
+    float* d_plan = nullptr;
+    float* h_plan = nullptr;
     ncclComm_t comm = nullptr;          // engine-owned RCCL communicator (mppi_comm_init)
     float* d_xown = nullptr;            // its exchange buffer (shard_count * V * P floats)
     bool peer = false;                  // peer exchange connected (mppi_peer_connect): no PACK, no collective

@@ -1,0 +1,357 @@
+// mppi_plan.hip -- k_plan, the nominal plan (mppi_get_plan): the rollout of the warm start u_prev
+// with zero noise, v_t = u_prev[v, t], one trajectory per vehicle.  Not part of the control step.
+//
+// One block per vehicle, ceil(H/64) waves, lane = horizon step t.  The double-integrator models
+// (drone, arm, whole-body) integrate as k_rollout's multi-chunk path does: two fp32 DPP segment
+// scans over t (seg_scan_f32_multi), wave w standing for chunk w, the carries between the 64-lane
+// chunks handed on through LDS and added in the same order; the measured position is added in the
+// state dtype (fp64 state -> fp64 positions and sin/cos reduction).  Each lane then runs the FK
+// chain and the cost terms of its own step with the rollout's device functions (mppi_rollout.h
+// kin_joint, mul_affine, mul_revolute, mul_prismatic, sincos_joint, pose_cost), and the block sums
+// the steps' costs.
+// The quadrotor's dynamics are sequential in t: one wave per vehicle, its first four lanes stepping
+// the vehicle's axes through k_rollout_quad's step (mppi_quad_step.h).
+//
+// Outputs (engine-owned, plain stores by the lanes): the state channels and EE rows as planes
+// (V, C, H), cost_t (V, H), pos_err (V, H), S (V).
+#include "mppi_quad_step.h"
+
+namespace {
+
+// The chain of one step over the rollout's joint functions (mppi_rollout.h kin_joint, mul_affine,
+// sincos_joint, mul_revolute, mul_prismatic), chosen at run time as the rollout's extended kernel
+// chooses it (DevParams::chain_fast).  Only this dispatch and the three loops below are the plan's
+// own: lifted out of rollout_body into functions both kernels call, they changed the rollout's
+// register allocation (the step's code objects must stay as they are), so rollout_body keeps its
+// copy.  T = base (whole-body: its position added) times the joints at pf (pd: the fp64 angles).
+template <int MODEL, int NA, bool F64>
+__device__ __forceinline__ void plan_fk(Mat34& T, const float (&pf)[NA], const double (&pd)[F64 ? NA : 1],
+                                        const VehicleConst& vc, const JointDev* jnt, const DevParams& p) {
+    constexpr int QOFF = (MODEL == MPPI_MODEL_WHOLEBODY) ? 3 : 0;
+    constexpr int NQ = NA - QOFF;
+    auto qang = [&](int j) {   // joint angle j in the state dtype
+        if constexpr (F64) return pd[QOFF + j]; else return pf[QOFF + j];
+    };
+#pragma unroll
+    for (int i = 0; i < 12; ++i) T.m[i] = vc.base[i];
+    if (MODEL == MPPI_MODEL_WHOLEBODY) {
+        T.m[3] += pf[0]; T.m[7] += pf[1]; T.m[11] += pf[2];
+    }
+    if (NQ == 7 && p.chain_fast == 2) {   // Kinova
+        kin_joint<0>(T, jnt[p.j0 + 0].O, qang(0));
+        kin_joint<1>(T, jnt[p.j0 + 1].O, qang(1));
+        kin_joint<2>(T, jnt[p.j0 + 2].O, qang(2));
+        kin_joint<3>(T, jnt[p.j0 + 3].O, qang(3));
+        kin_joint<4>(T, jnt[p.j0 + 4].O, qang(4));
+        kin_joint<5>(T, jnt[p.j0 + 5].O, qang(5));
+        kin_joint<6>(T, jnt[p.j0 + 6].O, qang(6));
+    } else if (p.chain_fast) {   // nq revolute-z joints, q_index = 0..nq-1 in order
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const JointDev& J = jnt[p.j0 + j];
+            mul_affine(T, J.O);
+            float s, cc;
+            sincos_joint(qang(j), s, cc);
+            const float omc = 1.0f - cc, r22 = cc + omc;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const float a0 = T.m[4 * i], a1 = T.m[4 * i + 1];
+                T.m[4 * i] = a0 * cc + a1 * s;
+                T.m[4 * i + 1] = a1 * cc - a0 * s;
+                T.m[4 * i + 2] = T.m[4 * i + 2] * r22;
+            }
+        }
+    } else {
+        for (int jn = p.j0; jn < p.nj; ++jn) {
+            const JointDev& J = jnt[jn];
+            mul_affine(T, J.O);
+            if (J.type == MPPI_JOINT_FIXED) continue;
+            double qd = 0.0;
+            float qf = 0.0f;
+#pragma unroll
+            for (int a = 0; a < NQ; ++a)
+                if (a == J.q_index) {
+                    qd = F64 ? pd[QOFF + a] : 0.0;
+                    qf = pf[QOFF + a];
+                }
+            if (J.type == MPPI_JOINT_REVOLUTE) {
+                float s, cc;
+                if constexpr (F64) sincos_joint(qd, s, cc); else sincos_joint(qf, s, cc);
+                mul_revolute(T, J, cc, s);
+            } else {
+                mul_prismatic(T, J, qf);
+            }
+        }
+    }
+}
+
+// The extra CostManager terms of one step before their weights and discount (cost_manager.py:83-87),
+// in rollout_body's operation order.  On the controls: u_t^T Sigma^-1 v_t (covar_cost.py:20-25;
+// zero noise: v_t = u_t) and ||v_t||^2 (action_cost.py:14-24).
+template <int NA>
+__device__ __forceinline__ float covar_form(const DevParams& p, const float (&act)[NA]) {
+    float qd = 0.0f;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        float y = 0.0f;
+        if (p.sigma_diag) {
+            y = p.sinv[a * NA + a] * act[a];
+        } else {
+#pragma unroll
+            for (int b = 0; b < NA; ++b) y = fmaf(p.sinv[a * NA + b], act[b], y);
+        }
+        qd = fmaf(act[a], y, qd);
+    }
+    return qd;
+}
+template <int NA>
+__device__ __forceinline__ float action_sumsq(const float (&act)[NA]) {
+    float s2 = 0.0f;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) s2 = fmaf(act[a], act[a], s2);
+    return s2;
+}
+// On the joints (joint_space_cost.py): sc = ||q - q_c||^2, sj = ||q - q*_t||^2 (jt = the tracking
+// target's row, null = zeros), out = any joint outside its limits (compared in the state dtype).
+template <int NA, int QOFF, int NQ, bool F64>
+__device__ __forceinline__ void joint_terms(const float (&pf)[NA], const double (&pd)[F64 ? NA : 1],
+                                            const VehicleConst& vc, const float* jt, float& sc, float& sj, bool& out) {
+    sc = 0.0f; sj = 0.0f;
+    out = false;
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+        const float qj = pf[QOFF + j];
+        const float dc = qj - vc.qc[j];
+        sc = fmaf(dc, dc, sc);
+        const float dj = qj - (jt ? jt[j] : 0.0f);
+        sj = fmaf(dj, dj, sj);
+        const double qd = F64 ? pd[QOFF + j] : (double)qj;
+        out |= (qd < (double)vc.qlo[j]) | (qd > (double)vc.qhi[j]);
+    }
+}
+
+}  // namespace
+
+template <int MODEL, int NA, bool F64>
+__global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, const JointDev* __restrict__ jtab,
+                                              const PlanParams pp, const DevParams pk) {
+    constexpr int QOFF = (MODEL == MPPI_MODEL_WHOLEBODY) ? 3 : 0;
+    constexpr int NQ = (MODEL == MPPI_MODEL_DRONE) ? 0 : NA - QOFF;
+    constexpr int kJW = (int)(sizeof(JointDev) * kMaxJ / 4);
+    constexpr int kVCW = (int)(sizeof(VehicleConst) / 4);
+    constexpr int kMaxWaves = MPPI_MAX_HORIZON / 64;
+    __shared__ JointDev jnt[kMaxJ];
+    __shared__ VehicleConst vcv;
+    __shared__ float tot1[kMaxWaves][NA], tot2[kMaxWaves][NA];   // the waves' scan totals (the chunk carries)
+    __shared__ float wsum[kMaxWaves];
+    const DevParams& p = pk;
+    const int v = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int nthr = blockDim.x, nw = nthr >> 6;
+    const int H = p.H, t = tid;
+    const bool val = t < H;
+    const int tc = val ? t : H - 1;
+    // the warm-start row of this step (the last finalize's: device scope)
+    float act[NA];
+    {
+        const float* ur = u_prev + ((size_t)v * H + tc) * NA;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) act[a] = ld_dev(ur + a);
+#pragma unroll
+        for (int a = 0; a < NA; ++a) act[a] = val ? act[a] : 0.0f;
+    }
+    if (MODEL != MPPI_MODEL_DRONE)
+        for (int i = tid; i < kJW; i += nthr) ((int*)jnt)[i] = ((const int*)jtab)[i];
+    for (int i = tid; i < kVCW; i += nthr) ((int*)&vcv)[i] = ((const int*)(pp.vc + v))[i];
+    const VehicleConst& vc = vcv;
+
+    // ---- double integrator (standard_normal_noise.py:41-48), k_rollout's NCH > 1 arithmetic
+    float posf[NA];
+    double posd[F64 ? NA : 1];
+    {
+#pragma clang fp contract(off)
+        float c1[NA], c2[NA];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) c1[a] = act[a] * p.dt;
+        seg_scan_f32_multi<64, NA>(c1);
+        if (lane == 63) {
+#pragma unroll
+            for (int a = 0; a < NA; ++a) tot1[wid][a] = c1[a];
+        }
+        lds_barrier();   // (also: the joint table and the vehicle constants are staged)
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            float carry = 0.0f;   // the velocity increment at the end of the chunk before this one
+            for (int w = 0; w < wid; ++w) carry = tot1[w][a] + carry;
+            c1[a] += carry;
+            const float h2 = act[a] * (0.5f * p.dt2);
+            const float velf = c1[a] + vc.vel0f[a];
+            float prev = dpp_f32<0x138, 0xF>(velf);     // wave_shr:1
+            if (lane == 0) prev = (wid == 0) ? vc.vel0f[a] : carry + vc.vel0f[a];
+            c2[a] = prev * p.dt + h2;
+        }
+        seg_scan_f32_multi<64, NA>(c2);
+        if (lane == 63) {
+#pragma unroll
+            for (int a = 0; a < NA; ++a) tot2[wid][a] = c2[a];
+        }
+        lds_barrier();
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            float carry = 0.0f;
+            for (int w = 0; w < wid; ++w) carry = tot2[w][a] + carry;
+            c2[a] += carry;
+            if (!F64) {
+                posf[a] = c2[a] + vc.pos0f[a];
+            } else {
+                posd[a] = (double)c2[a] + vc.pos0[a];
+                posf[a] = (float)posd[a];
+            }
+        }
+    }
+
+    // ---- FK, the step's cost and position error, the planes
+    const bool term = (t == H - 1);
+    float* const planes = pp.traj + (size_t)v * p.C * H;
+    float cost, perr;
+    if (MODEL == MPPI_MODEL_DRONE) {
+        const float dx = posf[0] - vc.tpos[0], dy = posf[1] - vc.tpos[1], dz = posf[2] - vc.tpos[2];
+        cost = (term ? p.w_tp : p.w_sp) * (dx * dx + dy * dy + dz * dz);
+        perr = fabsf(dx) + fabsf(dy) + fabsf(dz);
+        if (val) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) planes[(size_t)a * H + t] = posf[a];
+        }
+    } else {
+        Mat34 T;
+        plan_fk<MODEL, NA, F64>(T, posf, posd, vc, jnt, p);
+        cost = pose_cost(T, vc, term ? p.w_tp : p.w_sp, term ? p.w_to : p.w_so);
+        perr = fabsf(T.m[3] - vc.tpos[0]) + fabsf(T.m[7] - vc.tpos[1]) + fabsf(T.m[11] - vc.tpos[2]);
+        if (val) {
+#pragma unroll
+            for (int a = 0; a < NA; ++a) planes[(size_t)a * H + t] = posf[a];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) planes[(size_t)(NA + i) * H + t] = T.m[i];
+        }
+        if (p.cost_terms) {   // the extra CostManager terms in the reference's order (cost_manager.py:83-87)
+            const float g = p.gamma_t[tc];
+            if (p.cost_terms & MPPI_COST_COVAR) cost += p.w_cov * covar_form<NA>(p, act);
+            float sc = 0.0f, sj = 0.0f;
+            bool out = false;
+            if (p.cost_terms & (MPPI_COST_CENTER | MPPI_COST_JOINT_TRACK | MPPI_COST_JOINT_LIMIT))
+                joint_terms<NA, QOFF, NQ, F64>(posf, posd, vc, p.jtraj ? p.jtraj + ((size_t)v * H + tc) * NQ : nullptr,
+                                               sc, sj, out);
+            if (p.cost_terms & MPPI_COST_CENTER) cost += (p.w_cen * sc) * g;
+            if (p.cost_terms & MPPI_COST_JOINT_TRACK) cost += (p.w_jt * sj) * g;
+            if (p.cost_terms & MPPI_COST_ACTION) cost += (p.w_act * action_sumsq<NA>(act)) * g;
+            if ((p.cost_terms & MPPI_COST_JOINT_LIMIT) && out) cost += p.lim_pen * g;
+        }
+    }
+    if (val) {
+        pp.cost_t[(size_t)v * H + t] = cost;
+        pp.pos_err[(size_t)v * H + t] = perr;
+    }
+    // ---- S = sum_t cost_t: a fold per wave, the waves' sums through LDS, one lane writes
+    const float ws = wave_fold_all(val ? cost : 0.0f, OpAdd());
+    if (lane == 0) wsum[wid] = ws;
+    lds_barrier();
+    if (tid == 0) {
+        float S = 0.0f;
+        for (int w = 0; w < nw; ++w) S += wsum[w];
+        pp.S[v] = S;
+    }
+}
+
+// QUADROTOR: lanes 0..3 of the block's one wave are the vehicle's axis lanes (mppi_quad_step.h);
+// the other lanes only help stage u_prev.
+template <bool LIT>
+__global__ void __launch_bounds__(64) k_plan_quad(const float* __restrict__ u_prev, const PlanParams pp,
+                                                  const DevParams pk) {
+    constexpr int kQA = 4;
+    __shared__ float u_t[(64 + 1) * kQA];   // (a spare row: the step loads one row ahead)
+    const DevParams& p = pk;
+    const int v = blockIdx.x, lane = threadIdx.x, H = p.H;
+    const float* up = u_prev + (size_t)v * H * kQA;
+    for (int i = lane; i < (64 + 1) * kQA; i += 64) u_t[i] = (i < H * kQA) ? ld_dev(up + i) : 0.0f;
+    lds_barrier();
+    if (lane >= 4) return;
+    const VehicleConst& vc = pp.vc[v];
+    const int j = lane & 3, jj = j < 3 ? j : 2;
+    const float dt = p.dt, im = p.q_inv_m, kd = p.q_kd;
+    const float gj = (j >= 2) ? -p.q_g : 0.0f;      // g = (0, 0, -q_g)
+    const float ij = p.q_iinv[jj], tg = vc.tpos[jj];
+    float pj = vc.pos0f[jj], ej = vc.pos0f[3 + jj], vj = vc.vel0f[jj], wj = vc.vel0f[3 + jj];
+    const float ox0 = vc.vel0f[3], oy0 = vc.vel0f[4], oz0 = vc.vel0f[5];
+    const float a0 = (j == 0) ? 1.0f : 0.0f;
+    float* const planes = pp.traj + (size_t)v * p.C * H;
+    float S = 0.0f;
+    auto step = [&](const int t, auto first_c) {
+        constexpr bool FIRST = decltype(first_c)::value;
+        const float thr = u_t[t * kQA], tau = u_t[t * kQA + 1 + jj];
+        quad_axis_step<LIT, FIRST>(pj, ej, vj, wj, thr, tau, dt, im, kd, gj, ij, a0, ox0, oy0, oz0);
+        if (j < 3) {
+            planes[(size_t)j * H + t] = pj;
+            planes[(size_t)(3 + j) * H + t] = ej;
+        }
+        // squared and L1 position error over the three axes (drone_mppi.py:87-107)
+        const float dd = pj - tg, d2 = dd * dd, d1 = fabsf(dd);
+        const float x = qbc<0>(d2) + qbc<1>(d2) + qbc<2>(d2);
+        const float e1 = qbc<0>(d1) + qbc<1>(d1) + qbc<2>(d1);
+        const float c = ((t == H - 1) ? p.w_tp : p.w_sp) * x;
+        S += c;
+        if (j == 0) {
+            pp.cost_t[(size_t)v * H + t] = c;
+            pp.pos_err[(size_t)v * H + t] = e1;
+        }
+    };
+    step(0, std::true_type{});
+    for (int t = 1; t < H; ++t) step(t, std::false_type{});
+    if (j == 0) pp.S[v] = S;
+}
+
+namespace {
+
+template <typename NameF, typename... P, typename... Arg>
+int plan_go(void (*k)(P...), NameF namef, const DevParams& p, hipStream_t s, Arg... a) {
+    return go(k, namef, dim3(p.V), dim3(64 * ((p.H + 63) / 64)), 0, s, a...);
+}
+
+}  // namespace
+
+// The launch of the plan kernel for a configuration (through HIP, or described into the calling
+// thread's capture target: mppi_debug_plan_kernel).
+extern "C" int mppi_launch_plan(const DevParams* p, const PlanParams* pp, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
+    if (p->H < 1 || p->H > MPPI_MAX_HORIZON || p->V < 1) return -1;
+#define MPPI_PLAN_GO(MODEL, NA, F64)                                                                             \
+    return plan_go(k_plan<MODEL, NA, F64>,                                                                       \
+                   [](char* b, size_t n) {                                                                       \
+                       snprintf(b, n, "_Z6k_planILi%dELi%dELb%dEEvPKfPKN4mppi8JointDevENS2_10PlanParamsENS2_9DevParamsE", \
+                                (int)MODEL, NA, (int)F64);                                                       \
+                   },                                                                                            \
+                   *p, s, p->u_prev, p->joints, *pp, *p)
+    switch (p->model) {
+        case MPPI_MODEL_DRONE:
+            if (p->A == 3) MPPI_PLAN_GO(MPPI_MODEL_DRONE, 3, false);
+            break;
+        case MPPI_MODEL_ARM:
+            if (p->A == 7) {
+                if (p->state_f64) MPPI_PLAN_GO(MPPI_MODEL_ARM, 7, true);
+                MPPI_PLAN_GO(MPPI_MODEL_ARM, 7, false);
+            }
+            break;
+        case MPPI_MODEL_WHOLEBODY:
+            if (p->A == 10) MPPI_PLAN_GO(MPPI_MODEL_WHOLEBODY, 10, false);
+            break;
+        case MPPI_MODEL_QUADROTOR:
+            if (p->A != 4 || p->H > 64) break;
+            if (p->q_literal_jinv)
+                return plan_go(k_plan_quad<true>,
+                               [](char* b, size_t n) { snprintf(b, n, "_Z11k_plan_quadILb1EEvPKfN4mppi10PlanParamsENS2_9DevParamsE"); },
+                               *p, s, p->u_prev, *pp, *p);
+            return plan_go(k_plan_quad<false>,
+                           [](char* b, size_t n) { snprintf(b, n, "_Z11k_plan_quadILb0EEvPKfN4mppi10PlanParamsENS2_9DevParamsE"); },
+                           *p, s, p->u_prev, *pp, *p);
+    }
+#undef MPPI_PLAN_GO
+    return -1;
+}

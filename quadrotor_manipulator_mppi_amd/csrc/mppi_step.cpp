@@ -749,6 +749,25 @@ int32_t mppi_debug_rollout_kernels(const int32_t* g, char* full, char* quiet, in
     return (a == "?" || b == "?") ? MPPI_ERR_INVALID_ARG : MPPI_OK;
 }
 
+// Likewise the plan kernel (mppi_plan.hip; mppi_get_plan) -- g = {model, A, H, V, state_f64,
+// quad_literal_jinv}: "<symbol> grid <blocks> block <threads>" of its launch into `sym`.
+// tests/test_capi_plan_cpu.py.
+int32_t mppi_debug_plan_kernel(const int32_t* g, char* sym, int32_t len) {
+    if (!g || !sym || len <= 0) return MPPI_ERR_INVALID_ARG;
+    DevParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.model = g[0]; p.A = g[1]; p.H = g[2]; p.V = g[3]; p.state_f64 = g[4]; p.q_literal_jinv = g[5];
+    PlanParams pp;
+    std::memset(&pp, 0, sizeof(pp));
+    LaunchDesc d{};
+    mppi_aql::set_capture(&d);
+    const int rc = mppi_launch_plan(&p, &pp, nullptr);
+    mppi_aql::set_capture(nullptr);
+    if (rc != 0) return MPPI_ERR_INVALID_ARG;
+    snprintf(sym, (size_t)len, "%s grid %u block %u", d.symbol, d.grid[0], d.block[0]);
+    return MPPI_OK;
+}
+
 mppi_status mppi_synchronize(mppi_engine* e) {
     if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
     if (use_device(e)) return MPPI_ERR_HIP;

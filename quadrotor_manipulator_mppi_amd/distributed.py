@@ -380,6 +380,11 @@ class ShardedEngine:
         eng.set_u_prev(u.cpu().numpy())
         self.resyncs += 1
 
+    def get_plan(self):
+        """The nominal plan (``Engine.get_plan``): the warm start is the same on every rank, so each
+        rank's engine returns the same plan; no collective."""
+        return self.engine.get_plan()
+
     def __getattr__(self, name):
         if name == "engine":
             raise AttributeError(name)

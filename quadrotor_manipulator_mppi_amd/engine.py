@@ -32,6 +32,26 @@ class StepStats:
     exchange_timeout: bool = False   # a peer-exchange step gave up waiting for a rank (u_prev kept)
 
 
+@dataclass(slots=True)
+class Plan:
+    """The nominal plan (``Engine.get_plan``): the zero-noise rollout of the warm start ``u_prev``
+    from the current state.  Arrays are per vehicle, ``(V, ...)``; ``vehicle(v)`` drops that axis."""
+    traj: np.ndarray      # (V, H, C): the per-(t) layout of get_trajectory
+    cost_t: np.ndarray    # (V, H): each step's share of S
+    pos_err: np.ndarray   # (V, H): L1 distance of the EE / vehicle position to the target
+    S: np.ndarray         # (V,)
+    ee_path: np.ndarray   # (V, H, 3): the EE (arm, whole-body) or vehicle (drone, quadrotor) positions
+
+    def first_reach(self, tol: float = 0.005):
+        """The first t with pos_err < tol (check_reach's measure), -1 if none: per vehicle."""
+        hit = self.pos_err < tol
+        t = np.where(hit.any(axis=-1), hit.argmax(axis=-1), -1)
+        return int(t) if t.ndim == 0 else t
+
+    def vehicle(self, v: int = 0) -> "Plan":
+        return Plan(self.traj[v], self.cost_t[v], self.pos_err[v], self.S[v], self.ee_path[v])
+
+
 def fill_joints(cfg: capi.Config, chain: Sequence[Dict]) -> None:
     if len(chain) > capi.MAX_JOINTS:
         raise ValueError(f"chain has {len(chain)} joints (max {capi.MAX_JOINTS})")
@@ -404,6 +424,21 @@ class Engine:
         sm = np.empty_like(raw)
         capi.check(self._L.mppi_get_weighted_noise(self._h, capi.fptr(raw), capi.fptr(sm)), "get_weighted_noise")
         return raw, sm
+
+    def get_plan(self) -> Plan:
+        """The nominal plan of every vehicle (mppi_get_plan): one small kernel and four copies,
+        outside the control step."""
+        traj = np.empty((self.V, self.H, self.traj_channels), np.float32)
+        cost_t = np.empty((self.V, self.H), np.float32)
+        pos_err = np.empty_like(cost_t)
+        S = np.empty(self.V, np.float32)
+        capi.check(self._L.mppi_get_plan(self._h, capi.fptr(traj), capi.fptr(cost_t), capi.fptr(pos_err),
+                                         capi.fptr(S)), "get_plan")
+        if self.cfg.model in (capi.MODEL_ARM, capi.MODEL_WHOLEBODY):   # the EE matrix's translation column
+            ee_path = traj[..., self.A:].reshape(self.V, self.H, 4, 4)[..., :3, 3].copy()
+        else:
+            ee_path = traj[..., :3].copy()
+        return Plan(traj, cost_t, pos_err, S, ee_path)
 
     # ---------------------------------------------------------------- timing
     def enable_timing(self, on: bool = True):

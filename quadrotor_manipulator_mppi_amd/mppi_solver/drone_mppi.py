@@ -120,5 +120,10 @@ class MPPI(LazyU):
     def get_trajectory(self) -> np.ndarray:
         return self._engine.get_trajectory()[0]
 
+    def get_plan(self):
+        """The nominal plan: the zero-noise rollout of u_prev from the last state (engine.Plan of
+        vehicle 0: traj (H,3), cost_t (H), pos_err (H), S, ee_path (H,3), first_reach(tol))."""
+        return self._engine.get_plan().vehicle(0)
+
     def get_costs(self) -> np.ndarray:
         return self._engine.get_costs()[0]

@@ -27,7 +27,12 @@ def main() -> int:
     a, b = sys.argv[1], sys.argv[2]
     same = True
     for unit in KERNEL_UNITS:
-        la, lb = isa(code_object_path(a, unit)), isa(code_object_path(b, unit))
+        ca, cb = code_object_path(a, unit), code_object_path(b, unit)
+        if not os.path.exists(ca) or not os.path.exists(cb):   # a unit one build does not have (e.g. a new one)
+            print(f"{unit:28s} only in {'the second' if os.path.exists(cb) else 'the first' if os.path.exists(ca) else 'neither'}"
+                  " build: not compared")
+            continue
+        la, lb = isa(ca), isa(cb)
         nd = sum(1 for x, y in zip(la, lb) if x != y) + abs(len(la) - len(lb))
         same &= nd == 0
         print(f"{unit:28s} {len(lb):7d} lines  {'identical' if nd == 0 else f'{nd} lines differ'}")
