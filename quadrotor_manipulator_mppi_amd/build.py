@@ -124,7 +124,7 @@ def build(force: bool = False, debug: bool = False, verbose: bool = False, stamp
         os.replace(co + ".tmp", co)
     rocm_lib = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
     cmd = [hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", tmp] + objs + \
-        ["-L", rocm_lib, "-lhsa-runtime64"] + \
+        ["-L", rocm_lib, "-lhsa-runtime64", "-ldl"] + \
         (["-Xarch_host", "-fsanitize=address", "-shared-libsan"] if asan else [])
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:

@@ -83,5 +83,12 @@ bool step_busy(Step* s);
 // Install (or, with nullptr, remove) the calling thread's capture target: the launchers then
 // describe their launch into it instead of launching (mppi_device.h go()).
 void set_capture(mppi::LaunchDesc* d);
+// A capture target for a scope: removed however the scope is left.
+struct Capture {
+    explicit Capture(mppi::LaunchDesc* d) { set_capture(d); }
+    ~Capture() { set_capture(nullptr); }
+    Capture(const Capture&) = delete;
+    Capture& operator=(const Capture&) = delete;
+};
 
 }  // namespace mppi_aql

@@ -136,6 +136,19 @@ struct DevParams {
 // handed-over vehicle constants are never read (a batch's step before its last): the records only.
 constexpr int32_t kRollKernGeneric = 1, kRollKernQuiet = 2;
 constexpr int kStamps = 16;
+// noise-mode flag of native dispatch (mppi_aql.cpp): the rollout's step-counter argument is
+// relative to the dispatch id -- step = arg + (dispatch id >> 1) -- so one argument block,
+// written once, serves every (rollout, finalize) pair the engine's queue runs
+constexpr int32_t kNoiseStepFromId = 0x100;
+// noise-mode flag of an overlapped native batch (MPPI_OVERLAP=1, mppi_step.cpp run_steps_aql): the
+// rollout is dispatched while the finalize before it still runs (no barrier bit), draws its first
+// group's normals, then waits for that finalize's blocks (DevParams::ovl counters) before it reads
+// u_prev or hands the vehicle constants on
+constexpr int32_t kNoiseOverlap = 0x200;
+// The rollout's step counter word in its kernel-argument segment: the third argument (seed_lo,
+// seed_hi, step, ...) of every rollout kernel (mppi_rollout.h, mppi_rollout_quad.hip: their
+// launchers assert it).  Native dispatch rewrites it per batch or call.
+constexpr uint32_t kRollStepOff = 8;
 
 // The finalize tail's parameters, device-resident: written once at create (one copy per
 // launch kind), read by k_finalize through a preloaded pointer.  Read from the kernel

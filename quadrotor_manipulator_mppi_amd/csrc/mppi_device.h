@@ -1,14 +1,16 @@
 // mppi_device.h -- device helpers shared by the gfx950 kernels (rollout, finalize).
 // Internal: included only by mppi_rollout.hip / mppi_finalize.hip.
 #pragma once
+#include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "mppi_dev.h"
 
@@ -21,15 +23,7 @@ extern "C" __device__ uint64_t mppi_dispatch_id(void) __asm("llvm.amdgcn.dispatc
 
 namespace {
 
-// noise-mode flag of native dispatch (mppi_aql.cpp): the rollout's step-counter argument is
-// relative to the dispatch id -- step = arg + (dispatch id >> 1) -- so one argument block,
-// written once, serves every (rollout, finalize) pair the engine's queue runs
-constexpr int32_t kNoiseStepFromId = 0x100;
-// noise-mode flag of an overlapped native batch (MPPI_OVERLAP=1, mppi_step.cpp run_steps_aql): the
-// rollout is dispatched while the finalize before it still runs (no barrier bit), draws its first
-// group's normals, then waits for that finalize's blocks (DevParams::ovl counters) before it reads
-// u_prev or hands the vehicle constants on
-constexpr int32_t kNoiseOverlap = 0x200;
+// the step counter of a launch (mppi_dev.h kNoiseStepFromId: relative to the dispatch id)
 __device__ __forceinline__ uint32_t step_of(uint32_t step_arg, int32_t noise_arg) {
     return (noise_arg & kNoiseStepFromId) ? step_arg + (uint32_t)(mppi_dispatch_id() >> 1) : step_arg;
 }
@@ -178,20 +172,48 @@ __device__ __forceinline__ float wave_fold_all(float x, Op op) {
 // ------------------------------------------------------------------ launches
 // Every launch of the control step goes through go(): through HIP, or -- while the calling
 // thread has a capture target (mppi_aql.cpp, native dispatch) -- described into it: the
-// symbol (namef fills it; the Itanium name of the instantiation, which the code object's
-// symbol table holds), the geometry, and the arguments converted to the kernel's parameter
-// types and laid out at their natural alignment, as the kernel-argument segment holds them.
+// symbol (kernel_symbol below), the geometry, and the arguments converted to the kernel's
+// parameter types and laid out at their natural alignment, as the kernel-argument segment
+// holds them.
 template <typename T>
 inline void pack_arg(unsigned char* buf, uint32_t& off, const T& v) {
     off = (off + (uint32_t)alignof(T) - 1u) & ~((uint32_t)alignof(T) - 1u);
     if (off + sizeof(T) <= sizeof(LaunchDesc::args)) memcpy(buf + off, &v, sizeof(T));
     off += (uint32_t)sizeof(T);
 }
-template <typename NameF, typename... P, typename... Arg>
-inline int go(void (*k)(P...), NameF namef, dim3 grid, dim3 block, size_t lds, hipStream_t s, Arg... a) {
+// The byte offset of a kernel's N-th parameter in that layout.
+template <size_t N, typename... P>
+constexpr uint32_t arg_offset(void (*)(P...)) {
+    constexpr uint32_t size[] = {sizeof(std::decay_t<P>)...}, align[] = {alignof(std::decay_t<P>)...};
+    uint32_t off = 0;
+    for (size_t i = 0; i <= N; ++i) {
+        off = (off + align[i] - 1u) & ~(align[i] - 1u);
+        if (i < N) off += size[i];
+    }
+    return off;
+}
+// The symbol native dispatch looks a kernel up by in its unit's code object: the Itanium name of
+// the instantiation.  The host-side handle of a kernel is an exported object of this library
+// under that very name, so the dynamic linker knows it (dladdr).  Precondition: a kernel launched
+// through go() has external linkage -- not static, not in an anonymous namespace -- or its handle
+// has no dynamic symbol.  Each handle is resolved once per thread (the names live in the
+// library's string table); nullptr: no such symbol.
+inline const char* kernel_symbol(const void* handle) {
+    thread_local std::vector<std::pair<const void*, const char*>> seen;
+    for (const auto& e : seen)
+        if (e.first == handle) return e.second;
+    Dl_info info;
+    const bool ok = dladdr(handle, &info) != 0 && info.dli_saddr == handle && info.dli_sname && info.dli_sname[0];
+    seen.emplace_back(handle, ok ? info.dli_sname : nullptr);
+    return seen.back().second;
+}
+template <typename... P, typename... Arg>
+inline int go(void (*k)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, Arg... a) {
     static_assert(sizeof...(P) == sizeof...(Arg), "one value per kernel parameter");
     if (LaunchDesc* d = mppi_capture_target()) {
-        namef(d->symbol, sizeof(d->symbol));
+        const char* const sym = kernel_symbol((const void*)k);
+        if (!sym || strlen(sym) >= sizeof(d->symbol)) return -1;   // (never a truncated or empty name)
+        strcpy(d->symbol, sym);
         d->grid[0] = grid.x; d->grid[1] = grid.y; d->grid[2] = grid.z;
         d->block[0] = block.x; d->block[1] = block.y; d->block[2] = block.z;
         d->lds = (uint32_t)lds;
@@ -202,6 +224,17 @@ inline int go(void (*k)(P...), NameF namef, dim3 grid, dim3 block, size_t lds, h
     }
     hipLaunchKernelGGL(k, grid, block, lds, s, a...);
     return (int)hipGetLastError();
+}
+
+// The launchers' choice of a template argument by a run-time value: f(integral_constant<Alt>) of
+// the alternative equal to v, tried in the order listed (the order the instantiations are made
+// in); -1 when none is.
+template <auto... Alt, typename T, typename F>
+inline int pick(T v, F&& f) {
+    int rc = -1;
+    // (a left fold: the compiler expands a right fold from its last element, and with it the kernels)
+    (void)(... || (v == Alt && ((rc = f(std::integral_constant<decltype(Alt), Alt>{})), true)));
+    return rc;
 }
 
 }  // namespace

@@ -31,6 +31,11 @@
 // mppi_engine::generic with every part switched back (MPPI_GENERIC_KERNELS=1)
 constexpr int kGenericAll = 15;
 
+// Whose completion the pending outputs wait for: nothing to read; a HIP-launched read step (its
+// tagged records, ev_out as the backstop); a native batch (its completion signal); a native
+// control call (its records, tagged with a bit-31 sequence number).
+enum class Pending { None, Hip, Batch, Call };
+
 struct mppi_engine {
     mppi_config cfg;
     int K, H, A, V, nq, qoff, state_dim, out_dim, C, threads;
@@ -120,7 +125,8 @@ struct mppi_engine {
     unsigned char* h_out = nullptr;     // pinned + mapped: k_finalize writes it directly
     unsigned char* h_out_dev = nullptr; // device view of h_out
     hipEvent_t ev_vc = nullptr, ev_out = nullptr;
-    bool vc_pending = false, state_set = false, out_pending = false;
+    bool vc_pending = false, state_set = false;
+    Pending pending = Pending::None;    // the finalised step mppi_read_outputs may read
     std::vector<float> tpos, tquat;
     std::vector<double> state;
     // timing
@@ -142,8 +148,6 @@ struct mppi_engine {
     bool aql_tried = false;             // step_create attempted (its failure is final for the engine)
     bool aql_off = false;               // this engine's launches are not dispatchable natively
     std::string aql_why = "no mppi_run_steps yet";   // why the last run went through HIP ("" = native)
-    bool aql_out = false;               // the pending outputs come from a native batch
-    bool aql_call = false;              // ... from a native control call (flags carry bit 31)
     bool calls_native = false;          // the last mppi_step went out as native packets
     double call_wait_us = 0.0;          // diagnostics (MPPI_AQL_PROFILE): the last call's flag wait
     // prewarm (mppi_set_prewarm, mppi_prewarm.cpp): a host thread learns the control calls' cadence

@@ -857,61 +857,24 @@ extern "C" int mppi_launch_finalize(const FinParams* p, void* stream) {
                      : p->mode != 0 ? kRoleAny
                      : p->xpeers ? kRolePeer
                      : (p->kern & kFinKernQuiet) ? kRoleQuiet : kRoleFinal;
-#define MPPI_FIN_SGO(NTV, ROLEV, GIDV)                                                                    \
-    return go(k_finalize_s<NTV, ROLEV, GIDV>,                                                             \
-              [](char* b, size_t n) {                                                                     \
-                  snprintf(b, n, "_Z12k_finalize_sILi%dELi%dELi%dEEvPKfS1_PKN4mppi7FinTailEjjiiiiijNS2_9FinParamsE", \
-                           NTV, ROLEV, GIDV);                                                             \
-              },                                                                                          \
-              grid, dim3(NTV / kFinCPL), 0, s, p->hdr, p->dat, p->tail, nh, geo, (int32_t)p->hdr_rs,       \
-              (int32_t)p->d_rs, (int32_t)p->d_as, (int32_t)p->hdr_vs, (int32_t)p->d_vs, p->seq, *p)
-#define MPPI_FIN_SNT(ROLEV, GIDV)                                                                         \
-    do {                                                                                                  \
-        if (nt == 128) MPPI_FIN_SGO(128, ROLEV, GIDV);                                                    \
-        else if (nt == 256) MPPI_FIN_SGO(256, ROLEV, GIDV);                                               \
-        else MPPI_FIN_SGO(512, ROLEV, GIDV);                                                              \
-    } while (0)
-#define MPPI_FIN_SGEO(ROLEV)                                                                              \
-    do {                                                                                                  \
-        if (gid == 1) MPPI_FIN_SNT(ROLEV, 1);                                                             \
-        else if (gid == 2) MPPI_FIN_SNT(ROLEV, 2);                                                        \
-        else if (gid == 3) MPPI_FIN_SNT(ROLEV, 3);                                                        \
-        else MPPI_FIN_SNT(ROLEV, 4);                                                                      \
-    } while (0)
-    if (role == kRoleFinal) MPPI_FIN_SGEO(kRoleFinal);
-    else if (role == kRoleQuiet) MPPI_FIN_SGEO(kRoleQuiet);
-    else if (role == kRolePack) MPPI_FIN_SGEO(kRolePack);
-    else if (role == kRolePeer) MPPI_FIN_SGEO(kRolePeer);
-#undef MPPI_FIN_SGEO
-#undef MPPI_FIN_SNT
-#undef MPPI_FIN_SGO
-#define MPPI_FIN_GO(CWV, WINV, NTV)                                                                      \
-    return go(k_finalize<CWV, WINV, NTV>,                                                                 \
-              [](char* b, size_t n) {                                                                     \
-                  snprintf(b, n, "_Z10k_finalizeILi%dELi%dELi%dEEvPKfS1_PKN4mppi7FinTailEjjiiiiijNS2_9FinParamsE", \
-                           CWV, WINV, NTV);                                                               \
-              },                                                                                          \
-              grid, block, 0, s, p->hdr, p->dat, p->tail, nh, geo, (int32_t)p->hdr_rs, (int32_t)p->d_rs,   \
-              (int32_t)p->d_as, (int32_t)p->hdr_vs, (int32_t)p->d_vs, p->seq, *p)
-#define MPPI_FIN_LAUNCH(CWV, WINV)                                                                        \
-    do {                                                                                                  \
-        if (nt == 128) MPPI_FIN_GO(CWV, WINV, 128);                                                       \
-        else if (nt == 256) MPPI_FIN_GO(CWV, WINV, 256);                                                  \
-        else MPPI_FIN_GO(CWV, WINV, 512);                                                                 \
-    } while (0)
-#define MPPI_FIN_WIN(CWV)                                                                                 \
-    do {                                                                                                  \
-        if (p->window == 9) MPPI_FIN_LAUNCH(CWV, 9);                                                      \
-        else if (p->window == 5) MPPI_FIN_LAUNCH(CWV, 5);                                                 \
-        else MPPI_FIN_LAUNCH(CWV, 0);                                                                     \
-    } while (0)
-    if (W <= 16) MPPI_FIN_WIN(16);
-    else if (W <= 32) MPPI_FIN_WIN(32);
-    else MPPI_FIN_WIN(64);
-#undef MPPI_FIN_WIN
-#undef MPPI_FIN_LAUNCH
-#undef MPPI_FIN_GO
-    return -1;
+    const auto launch = [&](auto k, dim3 blk) {
+        return go(k, grid, blk, 0, s, p->hdr, p->dat, p->tail, nh, geo, (int32_t)p->hdr_rs, (int32_t)p->d_rs,
+                  (int32_t)p->d_as, (int32_t)p->hdr_vs, (int32_t)p->d_vs, p->seq, *p);
+    };
+    if (role != kRoleAny)
+        return pick<kRoleFinal, kRoleQuiet, kRolePack, kRolePeer>(role, [&](auto r) {
+            return pick<1, 2, 3, 4>(gid, [&](auto g) {
+                return pick<128, 256, 512>(nt, [&](auto n) {
+                    return launch(k_finalize_s<n(), r(), g()>, dim3(n() / kFinCPL));
+                });
+            });
+        });
+    const int win = (p->window == 9 || p->window == 5) ? p->window : 0;   // the taps a kernel is built for, or run-time taps
+    return pick<16, 32, 64>(cw, [&](auto c) {
+        return pick<9, 5, 0>(win, [&](auto w) {
+            return pick<128, 256, 512>(nt, [&](auto n) { return launch(k_finalize<c(), w(), n()>, block); });
+        });
+    });
 }
 
 #ifdef MPPI_PROBE

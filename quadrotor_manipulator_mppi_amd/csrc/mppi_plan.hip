@@ -308,50 +308,29 @@ __global__ void __launch_bounds__(64) k_plan_quad(const float* __restrict__ u_pr
     if (j == 0) pp.S[v] = S;
 }
 
-namespace {
-
-template <typename NameF, typename... P, typename... Arg>
-int plan_go(void (*k)(P...), NameF namef, const DevParams& p, hipStream_t s, Arg... a) {
-    return go(k, namef, dim3(p.V), dim3(64 * ((p.H + 63) / 64)), 0, s, a...);
-}
-
-}  // namespace
-
 // The launch of the plan kernel for a configuration (through HIP, or described into the calling
 // thread's capture target: mppi_debug_plan_kernel).
 extern "C" int mppi_launch_plan(const DevParams* p, const PlanParams* pp, void* stream) {
     const hipStream_t s = (hipStream_t)stream;
     if (p->H < 1 || p->H > MPPI_MAX_HORIZON || p->V < 1) return -1;
-#define MPPI_PLAN_GO(MODEL, NA, F64)                                                                             \
-    return plan_go(k_plan<MODEL, NA, F64>,                                                                       \
-                   [](char* b, size_t n) {                                                                       \
-                       snprintf(b, n, "_Z6k_planILi%dELi%dELb%dEEvPKfPKN4mppi8JointDevENS2_10PlanParamsENS2_9DevParamsE", \
-                                (int)MODEL, NA, (int)F64);                                                       \
-                   },                                                                                            \
-                   *p, s, p->u_prev, p->joints, *pp, *p)
+    const dim3 grid(p->V), block(64 * ((p->H + 63) / 64));   // a block per vehicle, a lane per horizon step
+    const auto chain = [&](auto k) { return go(k, grid, block, 0, s, p->u_prev, p->joints, *pp, *p); };
     switch (p->model) {
         case MPPI_MODEL_DRONE:
-            if (p->A == 3) MPPI_PLAN_GO(MPPI_MODEL_DRONE, 3, false);
+            if (p->A == 3) return chain(k_plan<MPPI_MODEL_DRONE, 3, false>);
             break;
         case MPPI_MODEL_ARM:
-            if (p->A == 7) {
-                if (p->state_f64) MPPI_PLAN_GO(MPPI_MODEL_ARM, 7, true);
-                MPPI_PLAN_GO(MPPI_MODEL_ARM, 7, false);
-            }
+            if (p->A == 7)
+                return pick<true, false>(p->state_f64 != 0, [&](auto f64) { return chain(k_plan<MPPI_MODEL_ARM, 7, f64()>); });
             break;
         case MPPI_MODEL_WHOLEBODY:
-            if (p->A == 10) MPPI_PLAN_GO(MPPI_MODEL_WHOLEBODY, 10, false);
+            if (p->A == 10) return chain(k_plan<MPPI_MODEL_WHOLEBODY, 10, false>);
             break;
         case MPPI_MODEL_QUADROTOR:
             if (p->A != 4 || p->H > 64) break;
-            if (p->q_literal_jinv)
-                return plan_go(k_plan_quad<true>,
-                               [](char* b, size_t n) { snprintf(b, n, "_Z11k_plan_quadILb1EEvPKfN4mppi10PlanParamsENS2_9DevParamsE"); },
-                               *p, s, p->u_prev, *pp, *p);
-            return plan_go(k_plan_quad<false>,
-                           [](char* b, size_t n) { snprintf(b, n, "_Z11k_plan_quadILb0EEvPKfN4mppi10PlanParamsENS2_9DevParamsE"); },
-                           *p, s, p->u_prev, *pp, *p);
+            return pick<true, false>(p->q_literal_jinv != 0, [&](auto lit) {
+                return go(k_plan_quad<lit()>, grid, block, 0, s, p->u_prev, *pp, *p);
+            });
     }
-#undef MPPI_PLAN_GO
     return -1;
 }

@@ -1411,31 +1411,6 @@ __global__ void __launch_bounds__(512, (F64 ? 7 : roll_occ<NCH, F64, XC, true>()
 // =============================================================================
 // launchers
 // =============================================================================
-// the instantiation's symbol (native dispatch looks it up in the code object)
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG>
-inline void rollout_symbol(char* buf, size_t n) {
-    snprintf(buf, n, "_Z9k_rolloutILi%dELi%dELi%dELi%dELb%dELb%dELb%dELb%dEEvjjjjiiiPKfPKN4mppi8JointDevENS2_9DevParamsE",
-             MODEL, NA, NCH, LSEG, (int)F64, (int)VONE, (int)XC, (int)ONEG);
-}
-
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC>
-inline void rollout_s_symbol(char* buf, size_t n) {
-    snprintf(buf, n, "_Z11k_rollout_sILi%dELi%dELi%dELi%dELb%dELb%dELb%dEEvjjjjiiiPKfPKN4mppi8JointDevENS2_9DevParamsE",
-             MODEL, NA, NCH, LSEG, (int)F64, (int)VONE, (int)XC);
-}
-
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG>
-inline void rollout_ql_symbol(char* buf, size_t n) {
-    snprintf(buf, n, "_Z12k_rollout_qlILi%dELi%dELi%dELi%dELb%dELb%dELb%dELb%dEEvjjjjiiiPKfPKN4mppi8JointDevENS2_9DevParamsE",
-             MODEL, NA, NCH, LSEG, (int)F64, (int)VONE, (int)XC, (int)ONEG);
-}
-
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC>
-inline void rollout_q_symbol(char* buf, size_t n) {
-    snprintf(buf, n, "_Z11k_rollout_qILi%dELi%dELi%dELi%dELb%dELb%dELb%dEEvjjjjiiiPKfPKN4mppi8JointDevENS2_9DevParamsE",
-             MODEL, NA, NCH, LSEG, (int)F64, (int)VONE, (int)XC);
-}
-
 // The geometries the quiet rollout is instantiated for: the kernels the default shapes run (arm and
 // drone at H <= 32, whole-body at H in 33..64; common kernel, one chunk).  Every other launch
 // keeps the full kernel on every step.
@@ -1450,72 +1425,35 @@ inline bool quiet_launch(const DevParams& p) {
            !(p.noise_mode & kNoiseOverlap);
 }
 
-// the quiet forms of launch_rollout_g / launch_rollout_s (no cost runs in LDS)
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC, bool ONEG>
-inline int launch_rollout_gq(const DevParams& p, int threads, hipStream_t s) {
-    const int iters = ONEG ? 1 : p.iters;
-    if (threads <= 0 || threads > 512 || iters < 1) return -1;
-    const size_t lds = (size_t)(((p.H * NA + 3) & ~3) + 8 * wave_slot_floats<NA, NCH, LSEG>()) * sizeof(float);
-    const int32_t geo = threads | (iters << 16);
-    if (p.V == 1)
-        return go(k_rollout_ql<MODEL, NA, NCH, LSEG, F64, true, XC, ONEG>,
-                  rollout_ql_symbol<MODEL, NA, NCH, LSEG, F64, true, XC, ONEG>, dim3(p.nb, p.V), dim3(threads), lds, s,
-                  p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset, p.noise_mode, p.H, geo, p.u_prev,
-                  p.joints, p);
-    return go(k_rollout_ql<MODEL, NA, NCH, LSEG, F64, false, XC, ONEG>,
-              rollout_ql_symbol<MODEL, NA, NCH, LSEG, F64, false, XC, ONEG>, dim3(p.nb, p.V), dim3(threads), lds, s,
-              p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset, p.noise_mode, p.H, geo, p.u_prev, p.joints,
-              p);
-}
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC>
-inline int launch_rollout_sq(const DevParams& p, hipStream_t s) {
-    constexpr int threads = 512;
-    const size_t lds = (size_t)(((p.H * NA + 3) & ~3) + 8 * wave_slot_floats<NA, NCH, LSEG>()) * sizeof(float);
-    const int32_t geo = threads | (1 << 16);
-    if (p.V == 1)
-        return go(k_rollout_q<MODEL, NA, NCH, LSEG, F64, true, XC>, rollout_q_symbol<MODEL, NA, NCH, LSEG, F64, true, XC>,
-                  dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
-                  p.noise_mode, p.H, geo, p.u_prev, p.joints, p);
-    return go(k_rollout_q<MODEL, NA, NCH, LSEG, F64, false, XC>, rollout_q_symbol<MODEL, NA, NCH, LSEG, F64, false, XC>,
-              dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
-              p.noise_mode, p.H, geo, p.u_prev, p.joints, p);
+// The kernel of a launch form: FIXED = the single-group kernel at 512 threads (k_rollout_s, quiet
+// k_rollout_q), else the kernel of every block size (k_rollout, quiet k_rollout_ql).
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG, bool FIXED, bool QUIET>
+constexpr auto rollout_kernel() {
+    if constexpr (FIXED && QUIET) return k_rollout_q<MODEL, NA, NCH, LSEG, F64, VONE, XC>;
+    else if constexpr (FIXED) return k_rollout_s<MODEL, NA, NCH, LSEG, F64, VONE, XC>;
+    else if constexpr (QUIET) return k_rollout_ql<MODEL, NA, NCH, LSEG, F64, VONE, XC, ONEG>;
+    else return k_rollout<MODEL, NA, NCH, LSEG, F64, VONE, XC, ONEG>;
 }
 
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC, bool ONEG>
-inline int launch_rollout_g(const DevParams& p, int threads, hipStream_t s) {
+// The launch of all four (FIXED implies ONEG and ignores `threads`).
+// (LDS: warm start, 8 wave slots, and -- not in the quiet forms -- the block's cost runs: iters of
+// them, one per group, each (threads / 64) * R floats padded to 16 B -- sized by the block's own
+// waves, not by 8)
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC, bool ONEG, bool FIXED, bool QUIET>
+inline int launch_rollout_k(const DevParams& p, int threads, hipStream_t s) {
+    static_assert(ONEG || !FIXED, "the fixed-block kernel runs one group");
+    if (FIXED) threads = 512;
     const int iters = ONEG ? 1 : p.iters;
-    // (LDS: warm start, 8 wave slots, the block's cost runs: iters of them, one per group, each
-    // (threads / 64) * R floats padded to 16 B -- sized by the block's own waves, not by 8)
-    const int s_run = iters * cost_run_stride((threads / 64) * (64 / LSEG));
+    const int s_run = QUIET ? 0 : iters * cost_run_stride((threads / 64) * (64 / LSEG));
     if (threads <= 0 || threads > 512 || iters < 1 || s_run > kMaxCostRun) return -1;
     const size_t lds = (size_t)(((p.H * NA + 3) & ~3) + 8 * wave_slot_floats<NA, NCH, LSEG>() + s_run) * sizeof(float);
     const int32_t geo = threads | (iters << 16);
-    if (p.V == 1)
-        return go(k_rollout<MODEL, NA, NCH, LSEG, F64, true, XC, ONEG>,
-                  rollout_symbol<MODEL, NA, NCH, LSEG, F64, true, XC, ONEG>, dim3(p.nb, p.V), dim3(threads), lds, s,
-                  p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset, p.noise_mode, p.H, geo, p.u_prev,
-                  p.joints, p);
-    return go(k_rollout<MODEL, NA, NCH, LSEG, F64, false, XC, ONEG>,
-              rollout_symbol<MODEL, NA, NCH, LSEG, F64, false, XC, ONEG>, dim3(p.nb, p.V), dim3(threads), lds, s,
-              p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset, p.noise_mode, p.H, geo, p.u_prev, p.joints,
-              p);
-}
-
-// the single-group kernel at 512 threads (k_rollout_s): launch_rollout_g's launch of it
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC>
-inline int launch_rollout_s(const DevParams& p, hipStream_t s) {
-    constexpr int threads = 512;
-    const int s_run = cost_run_stride((threads / 64) * (64 / LSEG));
-    if (s_run > kMaxCostRun) return -1;
-    const size_t lds = (size_t)(((p.H * NA + 3) & ~3) + 8 * wave_slot_floats<NA, NCH, LSEG>() + s_run) * sizeof(float);
-    const int32_t geo = threads | (1 << 16);
-    if (p.V == 1)
-        return go(k_rollout_s<MODEL, NA, NCH, LSEG, F64, true, XC>, rollout_s_symbol<MODEL, NA, NCH, LSEG, F64, true, XC>,
-                  dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
+    return pick<true, false>(p.V == 1, [&](auto vone) {
+        const auto k = rollout_kernel<MODEL, NA, NCH, LSEG, F64, vone(), XC, ONEG, FIXED, QUIET>();
+        static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+        return go(k, dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
                   p.noise_mode, p.H, geo, p.u_prev, p.joints, p);
-    return go(k_rollout_s<MODEL, NA, NCH, LSEG, F64, false, XC>, rollout_s_symbol<MODEL, NA, NCH, LSEG, F64, false, XC>,
-              dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
-              p.noise_mode, p.H, geo, p.u_prev, p.joints, p);
+    });
 }
 
 // the single-group (ONEG) variant exists for the common kernel at NCH == 1; at 512 threads, without
@@ -1531,16 +1469,16 @@ inline int launch_rollout_x(const DevParams& p, int threads, hipStream_t s) {
         if (p.iters == 1) {
             if (threads == 512 && !(p.kern & kRollKernGeneric) && !(p.noise_mode & kNoiseOverlap) && p.H <= LSEG * NCH) {
                 if constexpr (quiet_geom<MODEL, NCH, LSEG, XC>())
-                    if (quiet) return launch_rollout_sq<MODEL, NA, NCH, LSEG, F64, XC>(p, s);
-                return launch_rollout_s<MODEL, NA, NCH, LSEG, F64, XC>(p, s);
+                    if (quiet) return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, true, true, true>(p, threads, s);
+                return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, true, true, false>(p, threads, s);
             }
             if constexpr (quiet_geom<MODEL, NCH, LSEG, XC>())
-                if (quiet) return launch_rollout_gq<MODEL, NA, NCH, LSEG, F64, XC, true>(p, threads, s);
-            return launch_rollout_g<MODEL, NA, NCH, LSEG, F64, XC, true>(p, threads, s);
+                if (quiet) return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, true, false, true>(p, threads, s);
+            return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, true, false, false>(p, threads, s);
         }
     if constexpr (quiet_geom<MODEL, NCH, LSEG, XC>())
-        if (quiet) return launch_rollout_gq<MODEL, NA, NCH, LSEG, F64, XC, false>(p, threads, s);
-    return launch_rollout_g<MODEL, NA, NCH, LSEG, F64, XC, false>(p, threads, s);
+        if (quiet) return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, false, false, true>(p, threads, s);
+    return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, false, false, false>(p, threads, s);
 }
 
 // The extended (XC) instantiation carries the extra CostManager terms, a full

@@ -297,6 +297,12 @@ __global__ void __launch_bounds__(NT) k_rollout_quad_q(const uint32_t seed_lo, c
     rollout_quad_body<VONE, LIT, NWD, NT, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg, H, u_prev, pk);
 }
 
+template <bool VONE, bool LIT, int NWD, int NT, bool QUIET>
+constexpr auto quad_kernel() {
+    if constexpr (QUIET) return k_rollout_quad_q<VONE, LIT, NWD, NT>;
+    else return k_rollout_quad<VONE, LIT, NWD, NT>;
+}
+
 extern "C" int mppi_launch_rollout_quad(const DevParams* p, int threads, void* stream) {
     (void)threads;   // block size chosen below; p->iters = dynamics waves per block (1 or 4)
     const int nwd = p->iters;
@@ -305,36 +311,19 @@ extern "C" int mppi_launch_rollout_quad(const DevParams* p, int threads, void* s
     hipStream_t s = (hipStream_t)stream;
     const bool wide = nwd == 1 && (size_t)p->nb * p->V <= 512;
     const bool quiet = quiet_launch(*p);   // (a batch's step before its last: mppi_rollout.h)
-#define MPPI_QUAD_GO(VO, LI, NW, NT)                                                                             \
-    do {                                                                                                         \
-    if (quiet)                                                                                                   \
-        return go(k_rollout_quad_q<VO, LI, NW, NT>,                                                              \
-                  [](char* b, size_t n) {                                                                        \
-                      snprintf(b, n, "_Z16k_rollout_quad_qILb%dELb%dELi%dELi%dEEvjjjjiiPKfN4mppi9DevParamsE",    \
-                               (int)VO, (int)LI, NW, NT);                                                        \
-                  },                                                                                             \
-                  dim3(p->nb, p->V), dim3(NT), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,                      \
-                  (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, *p);                                    \
-    return go(k_rollout_quad<VO, LI, NW, NT>,                                                                    \
-              [](char* b, size_t n) {                                                                            \
-                  snprintf(b, n, "_Z14k_rollout_quadILb%dELb%dELi%dELi%dEEvjjjjiiPKfN4mppi9DevParamsE", (int)VO, \
-                           (int)LI, NW, NT);                                                                     \
-              },                                                                                                 \
-              dim3(p->nb, p->V), dim3(NT), lds, s, p->seed_lo, p->seed_hi, p->step_ctr, (uint32_t)p->k_offset,   \
-              p->noise_mode, p->H, p->u_prev, *p);                                                               \
-    } while (0)
-#define MPPI_QUAD_NW(VO, LI)                                                                                     \
-    do {                                                                                                         \
-        if (wide) MPPI_QUAD_GO(VO, LI, 1, kQThreadsWide);                                                        \
-        else if (nwd == 1) MPPI_QUAD_GO(VO, LI, 1, kQThreads);                                                   \
-        else MPPI_QUAD_GO(VO, LI, kQWaves, kQThreads);                                                           \
-    } while (0)
-    if (p->V == 1) {
-        if (p->q_literal_jinv) MPPI_QUAD_NW(true, true); else MPPI_QUAD_NW(true, false);
-    } else {
-        if (p->q_literal_jinv) MPPI_QUAD_NW(false, true); else MPPI_QUAD_NW(false, false);
-    }
-#undef MPPI_QUAD_NW
-#undef MPPI_QUAD_GO
-    return -1;
+    // the block: 512 threads of one dynamics wave (few blocks), 256 of one, or 256 of four
+    const int shape = wide ? 0 : nwd == 1 ? 1 : 2;
+    return pick<true, false>(p->V == 1, [&](auto vone) {
+        return pick<true, false>(p->q_literal_jinv != 0, [&](auto lit) {
+            return pick<0, 1, 2>(shape, [&](auto sh) {
+                constexpr int NW = sh() == 2 ? kQWaves : 1, NT = sh() == 0 ? kQThreadsWide : kQThreads;
+                return pick<true, false>(quiet, [&](auto q) {
+                    const auto k = quad_kernel<vone(), lit(), NW, NT, q()>();
+                    static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+                    return go(k, dim3(p->nb, p->V), dim3(NT), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,
+                              (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, *p);
+                });
+            });
+        });
+    });
 }

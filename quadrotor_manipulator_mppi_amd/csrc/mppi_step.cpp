@@ -63,6 +63,37 @@ static bool quiet_rollout(const mppi_engine* e) {
     return quiet_steps(e) && !(e->generic & 8) && !e->peer && !sharded(e);
 }
 
+// The step's (rollout, finalize) parameters as a path hands them to the launchers: the HIP
+// launches' (step counter and completion flag are the launch's own: rollout_impl, finalize_impl),
+// or a native batch's or control call's description -- the step counter relative to the dispatch
+// id (set by step_prepare / step_call), completion by the batch's signal or by the flags whose
+// sequence number rides in the vehicle constants.
+enum class StepPath { Hip, Batch, Call };
+struct StepParams { DevParams p; FinParams f; };
+static StepParams step_params(const mppi_engine* e, StepPath path, const float* d_noise = nullptr) {
+    StepParams sp{e->dp, e->fp};
+    sp.p.noise_in = d_noise;
+    sp.p.vc0 = e->h_vc[0];
+    sp.f.mode = 0;
+    final_records(e, sp.f);
+    if (path != StepPath::Hip) {
+        sp.p.step_ctr = 0u;
+        sp.p.noise_mode |= kNoiseStepFromId;
+        sp.f.seq = path == StepPath::Call ? kSeqFromVc : 0u;
+    }
+    return sp;
+}
+
+// A launch described into d instead of made (mppi_device.h go(); the launchers' status).
+static int describe(const DevParams& p, int threads, LaunchDesc* d) {
+    const mppi_aql::Capture c(d);
+    return mppi_launch_rollout(&p, threads, nullptr);
+}
+static int describe(const FinParams& f, LaunchDesc* d) {
+    const mppi_aql::Capture c(d);
+    return mppi_launch_finalize(&f, nullptr);
+}
+
 static mppi_status rollout_impl(mppi_engine* e, const float* d_noise, bool quiet) {
     if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
     if (!e->state_set) return fail(MPPI_ERR_STATE, "mppi_rollout before mppi_set_state");
@@ -102,20 +133,17 @@ extern "C" {
 
 mppi_status mppi_rollout(mppi_engine* e, const float* d_noise) { return rollout_impl(e, d_noise, false); }
 
-// The symbol a launch would run, by the launchers' own description of it (mppi_device.h go()).
+// The symbol a launch would run, by the launchers' own description of it.
 static std::string fin_symbol(const FinParams& f, LaunchDesc* desc = nullptr) {
     LaunchDesc d{};
-    mppi_aql::set_capture(&d);
-    const int rc = mppi_launch_finalize(&f, nullptr);
-    mppi_aql::set_capture(nullptr);
+    const int rc = describe(f, &d);
     if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
-static std::string roll_symbol(const DevParams& p, int threads) {
+static std::string roll_symbol(const DevParams& p, int threads, LaunchDesc* desc = nullptr) {
     LaunchDesc d{};
-    mppi_aql::set_capture(&d);
-    const int rc = mppi_launch_rollout(&p, threads, nullptr);
-    mppi_aql::set_capture(nullptr);
+    const int rc = describe(p, threads, &d);
+    if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
 static std::string kernels_text(const std::string& roll, const std::string& fin, const std::string* quiet,
@@ -152,9 +180,7 @@ static mppi_status finalize_impl(mppi_engine* e, bool record_out, bool quiet = f
     if (record_out) e->out_seq = f.seq;
     if (record_out) HIP_TRY(hipEventRecord(e->ev_out, e->stream));   // outputs land in mapped host memory
     ++e->step_ctr;
-    e->out_pending = record_out;
-    e->aql_out = false;
-    e->aql_call = false;
+    e->pending = record_out ? Pending::Hip : Pending::None;
     return MPPI_OK;
 }
 
@@ -187,8 +213,11 @@ static inline bool load_record(const mppi_engine* e, size_t i, uint32_t want, ui
 // by one queue packet).  The event stays the backstop: it is queried every few hundred
 // polls, which also surfaces a faulted queue as an error.
 static mppi_status wait_outputs(mppi_engine* e) {
-    if (e->aql_out) return aql_join(e);   // a native batch: its completion signal (system-scope release)
-    if (e->aql_call) {   // a native control call: its flags, the queue's error state as the backstop
+    switch (e->pending) {
+    case Pending::None: return MPPI_OK;
+    case Pending::Batch: return aql_join(e);   // its completion signal (system-scope release)
+    case Pending::Hip: break;                  // (below)
+    case Pending::Call: {   // its flags, the queue's error state as the backstop
         const uint32_t want = e->out_seq;
         const auto t0 = std::chrono::steady_clock::now();
         for (uint64_t it = 1;; ++it) {
@@ -204,6 +233,7 @@ static mppi_status wait_outputs(mppi_engine* e) {
         mppi_aql::step_call_read(e->aql);
         e->call_wait_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
         return MPPI_OK;
+    }
     }
     if (!e->event_wait) {
         const uint32_t want = e->out_seq;
@@ -268,9 +298,12 @@ static mppi_status assemble_records(mppi_engine* e) {
 
 mppi_status mppi_read_outputs(mppi_engine* e, double* out, float* u0, mppi_stats* stats) {
     if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
-    if (!e->out_pending) return fail(MPPI_ERR_STATE, "no finalised step to read");
-    if (e->aql_call) HIP_TRY(hipSetDevice(e->cfg.device));   // (its flags, not the queue's drain)
-    else if (use_device(e)) return MPPI_ERR_HIP;
+    switch (e->pending) {
+    case Pending::None: return fail(MPPI_ERR_STATE, "no finalised step to read");
+    case Pending::Call: HIP_TRY(hipSetDevice(e->cfg.device)); break;   // (its flags, not the queue's drain)
+    case Pending::Hip:
+    case Pending::Batch: if (use_device(e)) return MPPI_ERR_HIP;
+    }
     {   mppi_status st = wait_outputs(e);
         if (st != MPPI_OK) return st; }
     if (e->d_stamps) {   // diagnostic: average phase cycles over all waves
@@ -296,7 +329,7 @@ mppi_status mppi_read_outputs(mppi_engine* e, double* out, float* u0, mppi_stats
     const double* o = (const double*)e->h_out;
     const float* uu = (const float*)(e->h_out + off_u0(e));
     const float* st = (const float*)(e->h_out + off_stats(e));
-    if (!e->aql_out && e->out_seq != 0u) {   // a read step: its values from its tagged records
+    if (e->pending != Pending::Batch && e->out_seq != 0u) {   // a read step: its values from its tagged records
         mppi_status rs = assemble_records(e);
         if (rs != MPPI_OK) return rs;
         o = e->rec_out.data();
@@ -387,13 +420,8 @@ mppi_status mppi_step(mppi_engine* e, const double* state, const float* h_noise,
     if (e->comm && (st = mppi_exchange(e)) != MPPI_OK) return st;
     if ((st = mppi_finalize(e)) != MPPI_OK) return st;
     if (!e->kern_call_hip || e->kern_call_peer != e->peer) {   // (mppi_kernel_info; described once)
-        DevParams p = e->dp;
-        p.noise_in = dn;
-        p.vc0 = e->h_vc[0];
-        FinParams f = e->fp;
-        f.mode = 0;
-        final_records(e, f);
-        e->kern_call = kernels_text(roll_symbol(p, e->threads), fin_symbol(f), nullptr);
+        const StepParams sp = step_params(e, StepPath::Hip, dn);
+        e->kern_call = kernels_text(roll_symbol(sp.p, e->threads), fin_symbol(sp.f), nullptr);
         e->kern_call_hip = true;
         e->kern_call_peer = e->peer;
     }
@@ -411,13 +439,6 @@ static const char* aql_ineligible(const mppi_engine* e, bool batch = false) {
     if (e->out_dbg || (e->no_flag_dbg && !batch)) return "output diagnostics";
     return nullptr;
 }
-
-// The rollout's step counter word: its third argument (seed_lo, seed_hi, step, ...), the same
-// position in k_rollout and k_rollout_quad (mppi_rollout.h, mppi_rollout_quad.hip).  Under
-// native dispatch it is relative to the dispatch id (kNoiseStepFromId in the noise-mode word).
-constexpr uint32_t kRollStepOff = 8;
-constexpr int32_t kNoiseStepFromId = 0x100;   // = mppi_device.h
-constexpr int32_t kNoiseOverlap = 0x200;      // = mppi_device.h
 
 // n steps as native AQL packets (mppi_aql.cpp).  *used = false: the caller runs them through
 // HIP (auto mode, native dispatch unavailable for this engine; e->aql_why says why).
@@ -457,41 +478,23 @@ static mppi_status run_steps_aql(mppi_engine* e, int32_t n, bool* used) {
     LaunchDesc& fin = e->batch_fin;
     LaunchDesc& finq = e->batch_fin_quiet;   // every step's but the last (quiet_steps)
     LaunchDesc& rollq = e->batch_roll_quiet; // likewise (quiet_rollout)
-    DevParams p = e->dp;
-    p.noise_in = nullptr;
-    p.vc0 = e->h_vc[0];
-    p.step_ctr = 0u;                      // (set by step_prepare: relative to the dispatch id)
-    p.noise_mode |= kNoiseStepFromId;
+    StepParams sp = step_params(e, StepPath::Batch);
+    DevParams& p = sp.p;
+    const FinParams& f = sp.f;
     const bool ovl = e->overlap && n > 1;   // (experiment, MPPI_OVERLAP=1)
     if (ovl) p.noise_mode |= kNoiseOverlap;
-    FinParams f = e->fp;
-    f.mode = 0;
-    f.seq = 0u;   // completion: the batch's signal, not a flag
-    final_records(e, f);
     if (!(e->batch_cached && e->batch_threads == e->threads && std::memcmp(&p, &e->batch_p, sizeof(p)) == 0 &&
           std::memcmp(&f, &e->batch_f, sizeof(f)) == 0)) {
         e->batch_cached = false;
         e->kern_batch_state = 0;
-        mppi_aql::set_capture(&roll);
-        int rc = mppi_launch_rollout(&p, e->threads, e->stream);
-        if (rc == 0) {
-            DevParams pq = p;
-            if (quiet_rollout(e)) pq.kern |= kRollKernQuiet;
-            mppi_aql::set_capture(&rollq);
-            rc = mppi_launch_rollout(&pq, e->threads, e->stream);
-        }
-        if (rc == 0) {
-            mppi_aql::set_capture(&fin);
-            rc = mppi_launch_finalize(&f, e->stream);
-        }
-        if (rc == 0) {
-            FinParams fq = f;
-            if (quiet_steps(e)) fq.kern |= kFinKernQuiet;
-            mppi_aql::set_capture(&finq);
-            rc = mppi_launch_finalize(&fq, e->stream);
-        }
-        mppi_aql::set_capture(nullptr);
-        if (rc != 0) return fail(MPPI_ERR_HIP, "describing the step's launches failed (%d)", rc);
+        DevParams pq = p;
+        if (quiet_rollout(e)) pq.kern |= kRollKernQuiet;
+        FinParams fq = f;
+        if (quiet_steps(e)) fq.kern |= kFinKernQuiet;
+        int rc;
+        if ((rc = describe(p, e->threads, &roll)) != 0 || (rc = describe(pq, e->threads, &rollq)) != 0 ||
+            (rc = describe(f, &fin)) != 0 || (rc = describe(fq, &finq)) != 0)
+            return fail(MPPI_ERR_HIP, "describing the step's launches failed (%d)", rc);
         e->batch_p = p;
         e->batch_f = f;
         e->batch_threads = e->threads;
@@ -524,9 +527,7 @@ static mppi_status run_steps_aql(mppi_engine* e, int32_t n, bool* used) {
                     pt[0] / pn, pt[1] / pn, pt[2] / pn, pt[3] / pn);
     }
     e->step_ctr += (uint32_t)n;
-    e->out_pending = true;
-    e->aql_out = true;
-    e->aql_call = false;
+    e->pending = Pending::Batch;
     e->aql_why.clear();
     if (e->kern_batch_state != (n > 1 ? 2 : 1)) {   // (mppi_kernel_info; a one-step batch runs no quiet kernels)
         const std::string q = n > 1 ? finq.symbol : fin.symbol, rq = n > 1 ? rollq.symbol : roll.symbol;
@@ -566,15 +567,9 @@ static mppi_status control_call_aql(mppi_engine* e, const double* state, bool* u
         else if (q != hipSuccess) return fail(MPPI_ERR_HIP, "engine stream: %s", hipGetErrorString(q));
     }
     const auto q3 = std::chrono::steady_clock::now();
-    DevParams p = e->dp;
-    p.noise_in = nullptr;
-    p.vc0 = e->h_vc[0];
-    p.step_ctr = 0u;
-    p.noise_mode |= kNoiseStepFromId;
-    FinParams f = e->fp;
-    f.mode = 0;
-    f.seq = kSeqFromVc;
-    final_records(e, f);
+    const StepParams sp = step_params(e, StepPath::Call);
+    const DevParams& p = sp.p;
+    const FinParams& f = sp.f;
     // The launch descriptions of the previous call are reused when only the state changed:
     // the state lives in the vehicle constants (DevParams::vc0, inside the rollout's last
     // argument), which are patched in; anything else that differs re-captures (the capture
@@ -591,14 +586,9 @@ static mppi_status control_call_aql(mppi_engine* e, const double* state, bool* u
         std::memcpy(roll.args + roll.arg_bytes - sizeof(DevParams) + kVo, &p.vc0, kVn);
     } else {
         e->call_cached = false;
-        mppi_aql::set_capture(&roll);
-        int rc = mppi_launch_rollout(&p, e->threads, e->stream);
-        if (rc == 0) {
-            mppi_aql::set_capture(&fin);
-            rc = mppi_launch_finalize(&f, e->stream);
-        }
-        mppi_aql::set_capture(nullptr);
-        if (rc != 0) return fail(MPPI_ERR_HIP, "describing the step's launches failed (%d)", rc);
+        int rc;
+        if ((rc = describe(p, e->threads, &roll)) != 0 || (rc = describe(f, &fin)) != 0)
+            return fail(MPPI_ERR_HIP, "describing the step's launches failed (%d)", rc);
         e->call_p = p;
         e->call_f = f;
         e->call_threads = e->threads;
@@ -626,9 +616,7 @@ static mppi_status control_call_aql(mppi_engine* e, const double* state, bool* u
     if (pr != 0) return fail(MPPI_ERR_HIP, "native dispatch: %s", err.c_str());
     ++e->step_ctr;
     e->out_seq = seq;
-    e->out_pending = true;
-    e->aql_out = false;
-    e->aql_call = true;
+    e->pending = Pending::Call;
     if (!hit || e->kern_call_hip) e->kern_call = kernels_text(roll.symbol, fin.symbol, nullptr);
     e->kern_call_hip = false;
     *used = true;
@@ -651,11 +639,9 @@ mppi_status mppi_run_steps(mppi_engine* e, int32_t n) {
         if ((st = finalize_impl(e, i == n - 1, true)) != MPPI_OK) return st;
     }
     {   // (mppi_kernel_info) the launches above, described
-        DevParams p = e->dp;
-        p.vc0 = e->h_vc[0];
-        FinParams f = e->fp;
-        f.mode = 0;
-        final_records(e, f);
+        StepParams sp = step_params(e, StepPath::Hip);
+        DevParams& p = sp.p;
+        FinParams& f = sp.f;
         const std::string full = fin_symbol(f);
         if (n > 1 && quiet_steps(e)) f.kern |= kFinKernQuiet;
         const std::string q = fin_symbol(f), roll = roll_symbol(p, e->threads);
@@ -687,7 +673,17 @@ mppi_status mppi_dispatch_info(mppi_engine* e, char* buf, int32_t len) {
     return MPPI_OK;
 }
 
-static thread_local int32_t g_fin_launch[6];   // (mppi_debug_finalize_launch)
+static thread_local int32_t g_fin_launch[6];    // (mppi_debug_finalize_launch)
+static thread_local int32_t g_roll_launch[6];   // (mppi_debug_rollout_launch)
+// the captured launches' geometry, as native dispatch would store it in its packets
+static void note_launches(const LaunchDesc& a, const LaunchDesc& b, int32_t (&out)[6]) {
+    const LaunchDesc* ds[2] = {&a, &b};
+    for (int i = 0; i < 2; ++i) {
+        out[3 * i] = (int32_t)ds[i]->block[0];
+        out[3 * i + 1] = (int32_t)ds[i]->grid[0];
+        out[3 * i + 2] = (int32_t)ds[i]->lds;
+    }
+}
 // Diagnostic (not part of the public header; no GPU): the finalize kernels a batch's descriptions
 // would name for a launch of this shape -- g = {A, H, tsz, half, ts, window, nrec, mode, peer
 // exchange, MPPI_GENERIC_KERNELS}: the last step's into `full`, the earlier steps' into `quiet`
@@ -709,14 +705,7 @@ int32_t mppi_debug_finalize_kernels(const int32_t* g, char* full, char* quiet, i
     const std::string b = fin_symbol(f, &db);
     snprintf(full, (size_t)len, "%s", a.c_str());
     snprintf(quiet, (size_t)len, "%s", b.c_str());
-    // the captured launches' geometry, as native dispatch would store it in its packets
-    // (mppi_debug_finalize_launch below)
-    const LaunchDesc* ds[2] = {&da, &db};
-    for (int i = 0; i < 2; ++i) {
-        g_fin_launch[3 * i] = (int32_t)ds[i]->block[0];
-        g_fin_launch[3 * i + 1] = (int32_t)ds[i]->grid[0];
-        g_fin_launch[3 * i + 2] = (int32_t)ds[i]->lds;
-    }
+    note_launches(da, db, g_fin_launch);   // (mppi_debug_finalize_launch below)
     return (a == "?" || b == "?") ? MPPI_ERR_INVALID_ARG : MPPI_OK;
 }
 
@@ -741,12 +730,21 @@ int32_t mppi_debug_rollout_kernels(const int32_t* g, char* full, char* quiet, in
     p.nb = 16; p.K = 16; p.store_traj = 1;
     p.chain_fast = 2;
     p.kern = g[14] ? kRollKernGeneric : 0;
-    const std::string a = roll_symbol(p, g[6]);
+    LaunchDesc da{}, db{};
+    const std::string a = roll_symbol(p, g[6], &da);
     if (!g[13] && !g[14]) p.kern |= kRollKernQuiet;   // (as quiet_rollout: no peer exchange, not under MPPI_GENERIC_KERNELS)
-    const std::string b = roll_symbol(p, g[6]);
+    const std::string b = roll_symbol(p, g[6], &db);
     snprintf(full, (size_t)len, "%s", a.c_str());
     snprintf(quiet, (size_t)len, "%s", b.c_str());
+    note_launches(da, db, g_roll_launch);   // (mppi_debug_rollout_launch below)
     return (a == "?" || b == "?") ? MPPI_ERR_INVALID_ARG : MPPI_OK;
+}
+
+// Diagnostic (no GPU): {block threads, grid.x, dynamic LDS bytes} of the two launches the calling
+// thread's last mppi_debug_rollout_kernels described, the full one then the quiet one.
+// tests/test_capi_launch_table_cpu.py.
+void mppi_debug_rollout_launch(int32_t* out6) {
+    if (out6) std::memcpy(out6, g_roll_launch, sizeof(g_roll_launch));
 }
 
 // Likewise the plan kernel (mppi_plan.hip; mppi_get_plan) -- g = {model, A, H, V, state_f64,
@@ -760,10 +758,8 @@ int32_t mppi_debug_plan_kernel(const int32_t* g, char* sym, int32_t len) {
     PlanParams pp;
     std::memset(&pp, 0, sizeof(pp));
     LaunchDesc d{};
-    mppi_aql::set_capture(&d);
-    const int rc = mppi_launch_plan(&p, &pp, nullptr);
-    mppi_aql::set_capture(nullptr);
-    if (rc != 0) return MPPI_ERR_INVALID_ARG;
+    {   const mppi_aql::Capture c(&d);
+        if (mppi_launch_plan(&p, &pp, nullptr) != 0) return MPPI_ERR_INVALID_ARG; }
     snprintf(sym, (size_t)len, "%s grid %u block %u", d.symbol, d.grid[0], d.block[0]);
     return MPPI_OK;
 }
@@ -774,9 +770,16 @@ mppi_status mppi_synchronize(mppi_engine* e) {
     // The last finalised step's completion flag is polled first (mapped host memory, a
     // few hundred ns behind the kernel); hipStreamSynchronize alone wakes the host
     // microseconds after the stream drains, which a short timed batch pays in full.
-    if (e->out_pending && !e->event_wait && !e->aql_out) {
-        mppi_status st = wait_outputs(e);
-        if (st != MPPI_OK) return st;
+    switch (e->pending) {
+    case Pending::Hip:
+    case Pending::Call:
+        if (!e->event_wait) {
+            mppi_status st = wait_outputs(e);
+            if (st != MPPI_OK) return st;
+        }
+        break;
+    case Pending::None:
+    case Pending::Batch: break;   // (a batch: use_device above has joined it)
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (e->peer)

@@ -1,6 +1,6 @@
 """Native dispatch, CPU side (csrc/mppi_aql.cpp): the build writes one gfx950 code object per
 kernel unit next to the library, and the symbols the launchers name for native dispatch
-(mppi_rollout.h rollout_symbol, the finalize and quadrotor launchers) are in them.  The GPU
+(mppi_device.h go(): each kernel handle's own dynamic symbol) are in them.  The GPU
 side -- packets, parity with the HIP launches -- is tests/test_gpu_aql.py."""
 import os
 import struct

@@ -4,7 +4,11 @@
 
 Disassembles every kernel unit's gfx950 code object next to each library
 (<stem>.<unit>.co, the objects native dispatch loads; build.py KERNEL_UNITS) with llvm-objdump and
-compares the instruction text.  Exit status 0 when every unit is identical.  Used in round 6 to
+compares the instruction text, and with it -- what native dispatch reads besides the code -- the
+kernel descriptors (.rodata), the kernels' metadata (.note: argument layouts, register and LDS
+budgets) and the symbol table (names, sizes, addresses; the compilation unit id
+__hip_cuid_<hash>, a hash over the source path, left out).  Exit status 0 when every unit is
+identical.  Used in round 6 to
 show that source edits which only add experiment knobs (off by default) leave the production
 kernels bit for bit as the build the round's GPU evidence was taken on.
 """
@@ -23,6 +27,13 @@ def isa(co: str) -> list:
     return [ln for ln in out.splitlines()[3:]]   # (the first lines name the file)
 
 
+def tables(co: str) -> list:
+    out = [ln for sec in (".rodata", ".note") for ln in
+           subprocess.run([OBJDUMP, "-s", "-j", sec, co], capture_output=True, text=True, check=True).stdout.splitlines()[3:]]
+    syms = subprocess.run([OBJDUMP, "-t", co], capture_output=True, text=True, check=True).stdout.splitlines()[3:]
+    return out + sorted(ln for ln in syms if "__hip_cuid_" not in ln)
+
+
 def main() -> int:
     a, b = sys.argv[1], sys.argv[2]
     same = True
@@ -34,8 +45,10 @@ def main() -> int:
             continue
         la, lb = isa(ca), isa(cb)
         nd = sum(1 for x, y in zip(la, lb) if x != y) + abs(len(la) - len(lb))
-        same &= nd == 0
-        print(f"{unit:28s} {len(lb):7d} lines  {'identical' if nd == 0 else f'{nd} lines differ'}")
+        ta, tb = tables(ca), tables(cb)
+        same &= nd == 0 and ta == tb
+        print(f"{unit:28s} {len(lb):7d} lines  {'identical' if nd == 0 else f'{nd} lines differ'}"
+              f"; descriptors, metadata, symbols {'identical' if ta == tb else 'DIFFER'}")
     print("identical GPU code" if same else "GPU code differs")
     return 0 if same else 1
 
