@@ -16,7 +16,7 @@ using namespace mppi;
 
 namespace mppi_host {
 
-FinTail tail_of(const FinParams& f, int32_t mode) {
+static FinTail tail_of(const FinParams& f, int32_t mode) {
     FinTail t;
     std::memset(&t, 0, sizeof(t));
     t.coef = f.coef; t.dt = f.dt; t.dt2 = f.dt2;
@@ -39,30 +39,75 @@ void pack_fields(const mppi_engine* e, FinParams& f) {
     f.xbase = e->d_exchange; f.xslot = (int64_t)slot;
     f.nslots = e->cfg.shard_count; f.myslot = e->cfg.shard_rank;
 }
-mppi_status upload_pack_tail(mppi_engine* e) {
-    FinParams f = e->fp;
-    pack_fields(e, f);
-    const FinTail t = tail_of(f, 1);
-    // a PACK of an earlier step may still be reading the old tail on the engine's stream
-    // (a non-blocking torch stream: the blocking copy below is not ordered against it)
+
+Tails tails_of(const mppi_engine* e) {
+    Tails r;
+    // FINAL, the step's: it stores no readback copies of w_eps (mppi_get_weighted_noise recomputes
+    // them from the last step's records, READBACK), so the step's tail carries no extra stores
+    FinTail& fin = r.t[kTailFinal] = tail_of(e->fp, 0);
+    fin.wraw = nullptr;
+    fin.wsmooth = nullptr;
+    FinParams pk = e->fp;
+    pack_fields(e, pk);
+    r.t[kTailPack] = tail_of(pk, 1);
+    // SCRATCH: FINAL with its outputs and its sticky word in device scratch (mppi_kernel_timing, probes)
+    FinTail& scr = r.t[kTailScratch] = fin;
+    bind_outputs(scr, e->d_out, e);
+    scr.xerr = (uint32_t*)(e->d_out + off_xerr(e));
+    r.t[kTailReadback] = tail_of(e->fp, 2);
+    return r;
+}
+
+mppi_status upload_tails(mppi_engine* e, unsigned slots) {
+    const Tails r = tails_of(e);
+    // a finalize of an earlier step may still be reading the old tail on the engine's stream
+    // (a non-blocking torch stream: the blocking copies below are not ordered against it)
     HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(e->d_tail + kTailPack, &t, sizeof(t), hipMemcpyHostToDevice));
+    for (int k = 0; k < kTailSlots; ++k)
+        if (slots >> k & 1u) HIP_TRY(hipMemcpy(e->d_tail + k, &r.t[k], sizeof(FinTail), hipMemcpyHostToDevice));
     return MPPI_OK;
 }
 
-// Trajectory planes: k_rollout rows (one rollout's H steps) are padded to 64 B, hp = H
-// rounded up to 16 floats, and written whole.  With H = 100 the unpadded rows left partial
-// 64 B sectors at both ends of every wave store, which the write-through stores hand to HBM
-// as masked writes: arm K=4096 rollout 20.3 us at H = 100 vs 13.4 at H = 128
-// (profiles/r02/ab_traj_row_pitch.txt).  k_rollout_quad writes t-major (C,H,Kp) planes,
-// its rows (one step's K samples) padded the same way: Kp = K rounded up to 16.
-int traj_pitch(const mppi_engine* e) {
-    return e->cfg.model == MPPI_MODEL_QUADROTOR ? (e->K + 15) & ~15 : (e->H + 15) & ~15;
+mppi_status download(mppi_engine* e, void* dst, const void* src, size_t bytes) {
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return MPPI_OK;
 }
-size_t traj_floats(const mppi_engine* e) {   // all vehicles' planes
-    const size_t plane = e->cfg.model == MPPI_MODEL_QUADROTOR ? (size_t)traj_pitch(e) * e->H
-                                                               : (size_t)e->K * traj_pitch(e);
-    return (size_t)e->V * e->C * plane;
+
+// The FinParams of a FINAL into device scratch (the mapped buffer's layout; the SCRATCH tail) on
+// the throughput path (no completion flag): a pending read_outputs / get_weighted_noise still
+// returns the last real step.  On a shard the finalize combines the exchange slots as they stand
+// (no collective).  xerr stays at the mapped buffer.
+static FinParams scratch_final(const mppi_engine* e) {
+    FinParams f = e->fp;
+    f.mode = 0;
+    f.seq = 0u;
+    final_records(e, f);
+    bind_outputs(f, e->d_out, e);
+    f.wraw = nullptr;
+    f.wsmooth = nullptr;
+    f.tail = e->d_tail + kTailScratch;
+    return f;
+}
+
+// n steps out of SoA planes (channel stride `plane` floats; step i at offset at(i) of each) into
+// rows of mppi_traj_channels floats: the state channels, then (ARM, WHOLEBODY) the EE's twelve
+// stored entries with the row 0 0 0 1 appended
+template <class At>
+static void planes_to_rows(const mppi_engine* e, const float* planes, size_t plane, size_t n, At at, float* rows) {
+    const int Cr = mppi_traj_channels(&e->cfg);
+    const bool has_ee = e->cfg.model == MPPI_MODEL_ARM || e->cfg.model == MPPI_MODEL_WHOLEBODY;
+    const int nstate = has_ee ? e->A : e->C;
+    for (size_t i = 0; i < n; ++i) {
+        float* dst = rows + i * Cr;
+        const float* src = planes + at(i);
+        for (int c = 0; c < nstate; ++c) dst[c] = src[c * plane];
+        if (has_ee) {
+            float* ee = dst + nstate;
+            for (int r = 0; r < 12; ++r) ee[r] = src[(nstate + r) * plane];
+            ee[12] = 0.0f; ee[13] = 0.0f; ee[14] = 0.0f; ee[15] = 1.0f;
+        }
+    }
 }
 
 // Native batches are not ordered with the engine's HIP stream: every entry point that touches
@@ -198,6 +243,91 @@ mppi_status drain_timing(mppi_engine* e) {
     return MPPI_OK;
 }
 
+// ---- mppi_create's device stages (a failure leaves a half-built engine for mppi_destroy)
+static mppi_status allocate(mppi_engine* e) {
+    const mppi_config& c = e->cfg;
+    const size_t VHA = (size_t)e->V * e->H * e->A, VK = (size_t)e->V * e->K, nb = e->dp.nb;
+    HIP_TRY(hipSetDevice(c.device));
+    HIP_TRY(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
+    e->stream = e->own_stream;
+    HIP_TRY(hipEventCreateWithFlags(&e->ev_vc, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&e->ev_out, hipEventDisableTiming));
+    HIP_TRY(hipMalloc(&e->d_joints, sizeof(JointDev) * kMaxJ));
+    HIP_TRY(hipMalloc(&e->d_vc, sizeof(VehicleConst) * e->V));
+    HIP_TRY(hipMalloc(&e->d_u_prev, sizeof(float) * VHA));
+    HIP_TRY(hipMalloc(&e->d_S, sizeof(float) * VK));
+    HIP_TRY(hipMalloc(&e->d_w, sizeof(float) * VK));
+    HIP_TRY(hipMalloc(&e->d_hdr, sizeof(float) * e->V * nb * 4));
+    HIP_TRY(hipMalloc(&e->d_rdata, sizeof(float) * e->V * e->A * nb * e->H));
+    HIP_TRY(hipMalloc(&e->d_wraw, sizeof(float) * VHA));
+    HIP_TRY(hipMalloc(&e->d_wsmooth, sizeof(float) * VHA));
+    if (c.store_trajectory) HIP_TRY(hipMalloc(&e->d_traj, sizeof(float) * traj_floats(e)));
+    if (c.store_noise) HIP_TRY(hipMalloc(&e->d_noise_out, sizeof(float) * VK * e->H * e->A));
+    HIP_TRY(hipMalloc(&e->d_out, e->out_bytes));
+    HIP_TRY(hipHostMalloc((void**)&e->h_out, e->out_bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(hipHostGetDevicePointer((void**)&e->h_out_dev, e->h_out, 0));
+    HIP_TRY(hipMalloc(&e->d_sigma, sizeof(float) * kMaxA * kMaxA));
+    if (c.cost_terms) {   // Sigma^-1, gamma^t, tracking target
+        HIP_TRY(hipMalloc(&e->d_sinv, sizeof(float) * e->A * e->A));
+        HIP_TRY(hipMalloc(&e->d_gamma, sizeof(float) * e->H));
+        HIP_TRY(hipMalloc(&e->d_jtraj, sizeof(float) * (size_t)e->V * e->H * std::max(1, e->nq)));
+    }
+    HIP_TRY(hipHostMalloc((void**)&e->h_vc, sizeof(VehicleConst) * e->V, hipHostMallocDefault));
+#ifdef MPPI_STAMPS
+    if (getenv("MPPI_STAMPS")) {   // (diagnostics: an engine that cannot have them runs without)
+        const size_t nwaves = (size_t)e->V * nb * (e->threads / 64);
+        if (hipMalloc(&e->d_stamps, nwaves * kStamps * 8) != hipSuccess) e->d_stamps = nullptr;
+        e->stamp_sum.assign(kStamps, 0.0);
+        // FINAL's blocks, then a shard's PACK blocks (mppi_debug_fstamps)
+        if (hipMalloc(&e->d_fstamps, 2 * (size_t)e->V * e->A * ((e->H + 7) / 8) * kStamps * 8) != hipSuccess)
+            e->d_fstamps = nullptr;
+        e->fstamp_sum.assign(kStamps, 0.0);
+    }
+#endif
+    if (e->overlap) HIP_TRY(hipMalloc(&e->d_ovl, (size_t)e->V * e->A * e->fin_ts * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&e->d_tail, sizeof(FinTail) * kTailSlots));
+    return MPPI_OK;
+}
+
+// the device pointers of dp and fp (layout_of left them null)
+static void bind(mppi_engine* e) {
+    DevParams& p = e->dp;
+    p.sigma = e->d_sigma; p.joints = e->d_joints;
+    p.sinv = e->d_sinv; p.gamma_t = e->d_gamma; p.jtraj = e->d_jtraj;
+    p.vc = e->d_vc; p.u_prev = e->d_u_prev;
+    p.traj = e->d_traj; p.noise_out = e->d_noise_out; p.S = e->d_S; p.hdr = e->d_hdr; p.rdata = e->d_rdata;
+    p.stamps = e->d_stamps;
+    FinParams& f = e->fp;
+    f.u_prev = e->d_u_prev; f.vc = e->d_vc;
+    bind_outputs(f, e->h_out_dev, e);
+    f.xerr = (uint32_t*)(e->h_out_dev + off_xerr(e));
+    f.wraw = e->d_wraw; f.wsmooth = e->d_wsmooth;
+    f.stamps = e->d_fstamps;
+    if (e->overlap) {   // the finalize blocks' step counters, and their count per vehicle
+        f.xovl = e->d_ovl;
+        p.ovl = e->d_ovl;
+        p.ovl_n = e->A * e->fin_ts;
+    }
+    f.tail = e->d_tail + kTailFinal;
+}
+
+static mppi_status upload(mppi_engine* e) {
+    const mppi_config& c = e->cfg;
+    std::memset(e->h_out, 0, e->out_bytes);
+    HIP_TRY(hipMemcpy(e->d_sigma, c.sigma, sizeof(float) * e->A * e->A, hipMemcpyHostToDevice));
+    if (c.cost_terms) {
+        HIP_TRY(hipMemcpy(e->d_sinv, e->sinv.data(), sizeof(float) * e->sinv.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->d_gamma, e->gamma_t.data(), sizeof(float) * e->gamma_t.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(e->d_jtraj, 0, sizeof(float) * (size_t)e->V * e->H * std::max(1, e->nq)));
+    }
+    if (e->d_ovl) HIP_TRY(hipMemset(e->d_ovl, 0, (size_t)e->V * e->A * e->fin_ts * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(e->d_joints, e->joints, sizeof(e->joints), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(e->d_u_prev, 0, sizeof(float) * e->V * e->H * e->A, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_out, 0, e->out_bytes, e->stream));
+    // the finalize's tail parameters, one device copy per launch kind (after the stream's memsets)
+    return upload_tails(e, (1u << kTailSlots) - 1u);
+}
+
 }  // namespace mppi_host
 
 using namespace mppi_host;
@@ -213,301 +343,35 @@ mppi_status mppi_create(const mppi_config* cfg, mppi_engine** out) {
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (cfg->device < 0 || cfg->device >= ndev)
         return fail(MPPI_ERR_INVALID_ARG, "device %d not present (%d HIP devices)", cfg->device, ndev);
+    EngineLayout lay{};
+    if ((st = layout_of(*cfg, lay)) != MPPI_OK) return st;
 
     mppi_engine* e = new mppi_engine();
-    e->cfg = *cfg;
-    if (e->cfg.model == MPPI_MODEL_WHOLEBODY) e->cfg.state_f64 = 0;
+    static_cast<EngineLayout&>(*e) = std::move(lay);
     const mppi_config& c = e->cfg;
-    e->K = c.n_samples; e->H = c.n_horizon; e->A = c.n_action; e->V = c.n_vehicles;
-    e->nq = nq_of(c);
-    e->qoff = (c.model == MPPI_MODEL_WHOLEBODY) ? 3 : 0;
-    e->state_dim = mppi_state_dim(&c);
-    e->out_dim = mppi_output_dim(&c);
-    e->C = (c.model == MPPI_MODEL_DRONE) ? 3 : (c.model == MPPI_MODEL_QUADROTOR) ? 6 : e->A + 12;
     e->tpos.assign((size_t)3 * e->V, 0.0f);
-    e->fk_O.assign((size_t)16 * std::max(0, (int)e->cfg.n_joints), 0.0f);
-    e->fk_ax.assign((size_t)3 * std::max(0, (int)e->cfg.n_joints), 0.0f);
-    fk_consts(e->cfg.joints, e->cfg.n_joints, e->fk_O.data(), e->fk_ax.data());
+    e->fk_O.assign((size_t)16 * std::max(0, (int)c.n_joints), 0.0f);
+    e->fk_ax.assign((size_t)3 * std::max(0, (int)c.n_joints), 0.0f);
+    fk_consts(c.joints, c.n_joints, e->fk_O.data(), e->fk_ax.data());
     e->tquat.assign((size_t)4 * e->V, 0.0f);
     for (int v = 0; v < e->V; ++v) e->tquat[4 * v + 3] = 1.0f;
     e->state.assign((size_t)e->state_dim * e->V, 0.0);
-
-    // ---- geometry
-    const int H = e->H;
-    const int L = (H > 32) ? 64 : 32;
-    const int nch = (H + 63) / 64;
-    if (nch != 1 && nch != 2 && nch != 4) {
-        delete e;
-        return fail(MPPI_ERR_INVALID_ARG, "H=%d: supported horizons are <= 128 or 193..256", H);
-    }
-    const int R = 64 / L;
-    e->threads = c.block_threads ? c.block_threads : 512;
-    const int nw = e->threads / 64;
-    const int groups = (e->K + nw * R - 1) / (nw * R);
-    int nb = c.blocks_per_vehicle;
-    // auto: one block per group (iters == 1: the single-group kernel) while the grid is at
-    // most 512 blocks (2 per CU); above that >= 2 groups per block (the looping kernel; the
-    // prologue and the block combine are amortised, fewer records for the finalize),
-    // capped at 1024 blocks in total.  Re-measured on MI355X in round 5 (tools/probes.py geom,
-    // profiles/r05/geom): WB K=8192 step pair 17.6 us at 512 looping blocks vs 19.5-20.7 at 1024
-    // single-group blocks (whose finalize also reads twice the records) and 18.3 at 256; K=65536
-    // best at 1024 (85.2-86.1 us pairs vs 87.6-92.9 at 512, 89.1+ with 256-thread blocks).
-    if (nb <= 0) {
-        nb = (groups * e->V <= 512) ? groups : std::min(std::max(1, groups / 2), std::max(1, 1024 / e->V));
-    }
-    nb = std::min(nb, groups);
-    int iters = (groups + nb - 1) / nb;
-    // a block's cost run (iters * nw * R samples) is staged in LDS for one write-through store
-    // (k_rollout): at most kMaxCostRun floats, more blocks otherwise
-    iters = std::min(iters, std::max(1, kMaxCostRun / cost_run_stride(nw * R)));
-    nb = (groups + iters - 1) / iters;
-    if (c.model == MPPI_MODEL_QUADROTOR) {   // k_rollout_quad: 16 rollouts (4 lanes each) per dynamics
-        e->threads = 256;                     // wave; 1 dynamics wave per block up to 1024 blocks, else 4
-        iters = ((e->K + 15) / 16 * e->V <= 1024) ? 1 : 4;   // (carried in DevParams::iters)
-        nb = (e->K + 16 * iters - 1) / (16 * iters);
-    }
-    if (nb > 4096) { delete e; return fail(MPPI_ERR_INVALID_ARG, "too many rollout blocks (%d)", nb); }
-    const int P = (kHdr + e->A * H + 3) & ~3;
-    // the rollout kernels address one vehicle's trajectory planes through a buffer
-    // resource (32-bit byte offsets) and the record bodies with 32-bit indices
-    if (c.store_trajectory && (uint64_t)e->C * ((e->K + 15) & ~15) * ((H + 15) & ~15) * sizeof(float) > 0xFFFFFFFFull) {
-        const int C = e->C, K = e->K;
-        delete e;
-        return fail(MPPI_ERR_INVALID_ARG, "trajectory of one vehicle (C=%d x K=%d x H=%d floats) exceeds 4 GiB: "
-                    "disable store_trajectory or shard the samples", C, K, H);
-    }
-    if ((uint64_t)e->V * e->A * nb * H >= 0x80000000ull) {
-        const int V = e->V, A = e->A;
-        delete e;
-        return fail(MPPI_ERR_INVALID_ARG, "record bodies (V=%d x A=%d x %d blocks x H=%d = %llu floats) exceed 2^31",
-                    V, A, nb, H, (unsigned long long)V * A * nb * H);
-    }
-
-    if (savgol_taps(c.savgol_window, c.savgol_order, e->sg_taps) != 0) {
-        delete e;
-        return fail(MPPI_ERR_INVALID_ARG, "bad SavGol window/order");
-    }
-
-#define CREATE_TRY(expr)                                                                  \
-    do {                                                                                  \
-        hipError_t _e = (expr);                                                           \
-        if (_e != hipSuccess) {                                                           \
-            fail(MPPI_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));            \
-            mppi_destroy(e);                                                              \
-            return MPPI_ERR_HIP;                                                          \
-        }                                                                                 \
-    } while (0)
-
-    CREATE_TRY(hipSetDevice(c.device));
-    CREATE_TRY(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
-    e->stream = e->own_stream;
-    CREATE_TRY(hipEventCreateWithFlags(&e->ev_vc, hipEventDisableTiming));
-    CREATE_TRY(hipEventCreateWithFlags(&e->ev_out, hipEventDisableTiming));
-    const size_t KH = (size_t)e->V * e->K * H;
-    CREATE_TRY(hipMalloc(&e->d_joints, sizeof(JointDev) * kMaxJ));
-    CREATE_TRY(hipMalloc(&e->d_vc, sizeof(VehicleConst) * e->V));
-    CREATE_TRY(hipMalloc(&e->d_u_prev, sizeof(float) * e->V * H * e->A));
-    CREATE_TRY(hipMalloc(&e->d_S, sizeof(float) * e->V * e->K));
-    CREATE_TRY(hipMalloc(&e->d_w, sizeof(float) * e->V * e->K));
-    CREATE_TRY(hipMalloc(&e->d_hdr, sizeof(float) * (size_t)e->V * nb * 4));
-    CREATE_TRY(hipMalloc(&e->d_rdata, sizeof(float) * (size_t)e->V * e->A * nb * H));
-    CREATE_TRY(hipMalloc(&e->d_wraw, sizeof(float) * e->V * H * e->A));
-    CREATE_TRY(hipMalloc(&e->d_wsmooth, sizeof(float) * e->V * H * e->A));
-    if (c.store_trajectory) CREATE_TRY(hipMalloc(&e->d_traj, sizeof(float) * traj_floats(e)));
-    if (c.store_noise) CREATE_TRY(hipMalloc(&e->d_noise_out, sizeof(float) * KH * e->A));
-    e->out_bytes = (int64_t)(off_xerr(e) + 16);
-    CREATE_TRY(hipMalloc(&e->d_out, e->out_bytes));
-    CREATE_TRY(hipHostMalloc((void**)&e->h_out, e->out_bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    CREATE_TRY(hipHostGetDevicePointer((void**)&e->h_out_dev, e->h_out, 0));
-    std::memset(e->h_out, 0, e->out_bytes);
-    CREATE_TRY(hipMalloc(&e->d_sigma, sizeof(float) * kMaxA * kMaxA));
-    CREATE_TRY(hipMemcpy(e->d_sigma, c.sigma, sizeof(float) * e->A * e->A, hipMemcpyHostToDevice));
-    if (c.cost_terms) {   // Sigma^-1 (covar_cost.py:21), gamma^t (action_cost.py:21), tracking target
-        std::vector<double> m(e->A * 2 * e->A, 0.0);
-        const int A = e->A, W2 = 2 * A;
-        for (int i = 0; i < A; ++i) {
-            for (int j = 0; j < A; ++j) m[i * W2 + j] = c.sigma[i * A + j];
-            m[i * W2 + A + i] = 1.0;
-        }
-        for (int col = 0; col < A; ++col) {   // Gauss-Jordan, partial pivoting, fp64
-            int piv = col;
-            for (int r = col + 1; r < A; ++r)
-                if (std::fabs(m[r * W2 + col]) > std::fabs(m[piv * W2 + col])) piv = r;
-            if (std::fabs(m[piv * W2 + col]) < 1e-30) { mppi_destroy(e); return fail(MPPI_ERR_INVALID_ARG, "Sigma is singular"); }
-            for (int j = 0; j < W2; ++j) std::swap(m[col * W2 + j], m[piv * W2 + j]);
-            const double d = m[col * W2 + col];
-            for (int j = 0; j < W2; ++j) m[col * W2 + j] /= d;
-            for (int r = 0; r < A; ++r)
-                if (r != col) {
-                    const double f2 = m[r * W2 + col];
-                    for (int j = 0; j < W2; ++j) m[r * W2 + j] -= f2 * m[col * W2 + j];
-                }
-        }
-        std::vector<float> sinv(A * A), gam(H);
-        for (int i = 0; i < A; ++i)
-            for (int j = 0; j < A; ++j) sinv[i * A + j] = (float)m[i * W2 + A + j];
-        for (int t = 0; t < H; ++t) gam[t] = std::pow(c.cost_gamma, (float)t);
-        CREATE_TRY(hipMalloc(&e->d_sinv, sizeof(float) * A * A));
-        CREATE_TRY(hipMalloc(&e->d_gamma, sizeof(float) * H));
-        CREATE_TRY(hipMalloc(&e->d_jtraj, sizeof(float) * (size_t)e->V * H * std::max(1, e->nq)));
-        CREATE_TRY(hipMemcpy(e->d_sinv, sinv.data(), sizeof(float) * A * A, hipMemcpyHostToDevice));
-        CREATE_TRY(hipMemcpy(e->d_gamma, gam.data(), sizeof(float) * H, hipMemcpyHostToDevice));
-        CREATE_TRY(hipMemset(e->d_jtraj, 0, sizeof(float) * (size_t)e->V * H * std::max(1, e->nq)));
-    }
-    CREATE_TRY(hipHostMalloc((void**)&e->h_vc, sizeof(VehicleConst) * e->V, hipHostMallocDefault));
-    CREATE_TRY(hipMemsetAsync(e->d_u_prev, 0, sizeof(float) * e->V * H * e->A, e->stream));
-    CREATE_TRY(hipMemsetAsync(e->d_out, 0, e->out_bytes, e->stream));
-
-    std::vector<JointDev> jd(kMaxJ);
-    for (int j = 0; j < c.n_joints; ++j) bake_joint(c.joints[j], jd[j]);
-    // fold the leading fixed joints of the chain into the per-vehicle base transform
-    const float I12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    std::memcpy(e->fixedM, I12, sizeof(I12));
-    int j0 = 0;
-    while (c.model != MPPI_MODEL_DRONE && j0 < c.n_joints && jd[j0].type == MPPI_JOINT_FIXED) {
-        mul34(e->fixedM, jd[j0].O, e->fixedM);
-        ++j0;
-    }
-    CREATE_TRY(hipMemcpy(e->d_joints, jd.data(), sizeof(JointDev) * kMaxJ, hipMemcpyHostToDevice));
-    CREATE_TRY(hipStreamSynchronize(e->stream));
-#undef CREATE_TRY
-
-    DevParams& p = e->dp;
-    std::memset(&p, 0, sizeof(p));
-    p.model = c.model; p.V = e->V; p.K = e->K; p.H = H; p.A = e->A;
-    p.L = L; p.R = R; p.nch = nch; p.nb = nb; p.iters = iters;
-    p.nq = e->nq; p.qoff = e->qoff; p.nj = c.n_joints;
-    // (the vehicle offset in the high half: the rollouts' fleet-wide Philox vehicle key)
-    p.noise_mode = c.noise_mode | (c.vehicle_offset << 16); p.state_f64 = c.state_f64;
-    p.store_traj = c.store_trajectory; p.store_noise = c.store_noise;
-    bool diag = true;
-    for (int a = 0; a < e->A; ++a)
-        for (int b = 0; b < e->A; ++b) {
-            if (a == b) p.sdiag[a] = c.sigma[a * e->A + b];
-            else if (c.sigma[a * e->A + b] != 0.0f) diag = false;
-        }
-    p.sigma_diag = diag;
-    p.sigma = e->d_sigma;
-    p.j0 = j0;
-    {   // fast FK path: the unfolded chain is exactly nq revolute-z joints in q order
-        bool fast = c.model != MPPI_MODEL_DRONE && (c.n_joints - j0) == e->nq;
-        for (int j = j0; fast && j < c.n_joints; ++j)
-            fast = jd[j].type == MPPI_JOINT_REVOLUTE && jd[j].axis_z && jd[j].q_index == j - j0;
-        p.chain_fast = fast;
-        if (fast && e->nq == 7 && c.n_joints - j0 == 7) {   // Kinova origin table (mppi_dev.h kKinova)
-            bool kin = true;
-            for (int j = 0; kin && j < 7; ++j) {
-                const float* O = jd[j0 + j].O;
-                const KinOrigin& k = kKinova[j];
-                for (int col = 0; kin && col < 3; ++col)
-                    for (int row = 0; kin && row < 3; ++row) {
-                        const float want = (row == k.p[col]) ? (float)k.s[col] : 0.0f;
-                        kin = std::fabs(O[4 * row + col] - want) <= 1e-6f;
-                    }
-                for (int d = 0; kin && d < 3; ++d) kin = ((k.tmask >> d) & 1) ? true : (O[4 * d + 3] == 0.0f);
-            }
-            if (kin && !getenv("MPPI_NO_KINOVA_PATH")) p.chain_fast = 2;
-        }
-    }
-    p.P = P; p.C = e->C; p.hp = traj_pitch(e);
-    p.seed_lo = (uint32_t)c.seed; p.seed_hi = (uint32_t)(c.seed >> 32);
-    p.k_offset = (int64_t)c.shard_rank * e->K;
-    p.dt = (float)c.dt; p.dt2 = (float)(c.dt * c.dt); p.dt_d = c.dt;
-    p.coef = (float)(-1.0 / c.lambda_);
-    p.w_sp = c.w_stage_pos; p.w_so = c.w_stage_ori; p.w_tp = c.w_term_pos; p.w_to = c.w_term_ori;
-    p.joints = e->d_joints;
-    p.cost_terms = c.cost_terms;
-    p.w_cov = (float)((double)c.w_covar * (c.lambda_ * (1.0 - (double)c.cost_alpha)));   // covar_cost.py:15,24
-    p.w_cen = c.w_center; p.w_jt = c.w_joint_track; p.w_act = c.w_action; p.lim_pen = c.joint_limit_penalty;
-    p.sinv = e->d_sinv; p.gamma_t = e->d_gamma; p.jtraj = e->d_jtraj;
-    p.q_inv_m = (float)(1.0 / (double)c.quad_mass);   // 1/self.m as a Python float, used in fp32
-    for (int d = 0; d < 3; ++d) p.q_iinv[d] = (float)(1.0 / (double)c.quad_inertia[d]);
-    p.q_kd = c.quad_kd; p.q_g = c.quad_gravity; p.q_literal_jinv = c.quad_literal_jinv ? 1 : 0;
-    p.vc = e->d_vc; p.u_prev = e->d_u_prev;
-    p.traj = e->d_traj; p.noise_out = e->d_noise_out; p.S = e->d_S; p.hdr = e->d_hdr; p.rdata = e->d_rdata;
-#ifdef MPPI_STAMPS
-    if (getenv("MPPI_STAMPS")) {
-        const size_t nwaves = (size_t)e->V * nb * (e->threads / 64);
-        if (hipMalloc(&e->d_stamps, nwaves * kStamps * 8) == hipSuccess) p.stamps = e->d_stamps;
-        e->stamp_sum.assign(kStamps, 0.0);
-        // FINAL's blocks, then a shard's PACK blocks (mppi_debug_fstamps)
-        (void)hipMalloc(&e->d_fstamps, 2 * (size_t)e->V * e->A * ((H + 7) / 8) * kStamps * 8);
-        e->fstamp_sum.assign(kStamps, 0.0);
-    }
-#endif
-
-    FinParams& f = e->fp;
-    std::memset(&f, 0, sizeof(f));
-    f.model = c.model; f.V = e->V; f.H = H; f.A = e->A; f.nq = e->nq; f.qoff = e->qoff;
-    f.state_f64 = c.state_f64; f.P = P;
-    // (diagnostics: MPPI_FIN_TSZ = t per finalize slice, for the slice-count / fetch trade-off
-    // measured in profiles/r05/finalize_fetch; 8 is the measured best)
-    if (const char* z = getenv("MPPI_FIN_TSZ")) {
-        const int tz = atoi(z);
-        if (tz >= 1 && tz + 2 * (c.savgol_window / 2) <= 64) e->fin_tsz = tz;
-    }
-    f.tsz = e->fin_tsz; f.ts = e->fin_ts = (H + e->fin_tsz - 1) / e->fin_tsz;
-    f.window = c.savgol_window; f.half = c.savgol_window / 2;
-    for (int j = 0; j < c.savgol_window; ++j) f.sg[j] = e->sg_taps[c.savgol_window - 1 - j];
-    f.coef = p.coef; f.dt = p.dt; f.dt2 = p.dt2; f.dt_d = c.dt;
-    f.u_prev = e->d_u_prev; f.vc = e->d_vc;
-    f.out = (double*)e->h_out_dev;
-    f.u0 = (float*)(e->h_out_dev + off_u0(e));
-    f.stats = (float*)(e->h_out_dev + off_stats(e));
-    f.flags = (uint32_t*)(e->h_out_dev + off_flags(e));
-    f.xerr = (uint32_t*)(e->h_out_dev + off_xerr(e));
-    f.wraw = e->d_wraw; f.wsmooth = e->d_wsmooth; f.out_dim = e->out_dim;
-    if (const char* dbg = getenv("MPPI_FIN_DEBUG")) f.dbg = atoi(dbg);
-    if (const char* g = getenv("MPPI_GENERIC_KERNELS"))   // 1: all of them; one part by name (A/B of the parts)
-        e->generic = !strcmp(g, "finalize") ? 1 : !strcmp(g, "quiet") ? 2 : !strcmp(g, "rollout") ? 4
-                     : !strcmp(g, "quiet_rollout") ? 8 : atoi(g) != 0 ? kGenericAll : 0;
-    f.kern = (e->generic & 1) ? kFinKernGeneric : 0;
-    p.kern = (e->generic & 4) ? kRollKernGeneric : 0;   // (kRollKernQuiet: per launch, mppi_step.cpp)
+    // the run-time switches (the ones that change the layout: layout_of)
+    if (const char* dbg = getenv("MPPI_FIN_DEBUG")) e->fp.dbg = atoi(dbg);
     e->event_wait = getenv("MPPI_EVENT_WAIT") && atoi(getenv("MPPI_EVENT_WAIT")) != 0;
     e->no_flag_dbg = e->event_wait && getenv("MPPI_DEBUG_NO_FLAG") && atoi(getenv("MPPI_DEBUG_NO_FLAG")) != 0;
     e->out_dbg = getenv("MPPI_DEBUG_OUT") ? atoi(getenv("MPPI_DEBUG_OUT")) : 0;
     if (const char* d = getenv("MPPI_DISPATCH")) e->aql_mode = !strcmp(d, "hip") ? 0 : !strcmp(d, "aql") ? 1 : 2;
-    f.stamps = e->d_fstamps;
     // experiment (MPPI_OVERLAP=1): overlapped native batches; k_rollout only (k_rollout_quad does not wait)
     e->overlap = getenv("MPPI_OVERLAP") && atoi(getenv("MPPI_OVERLAP")) != 0 && c.model != MPPI_MODEL_QUADROTOR;
-    if (e->overlap) {
-        const size_t n = (size_t)e->V * e->A * e->fin_ts;
-        if (hipMalloc(&e->d_ovl, n * sizeof(uint32_t)) != hipSuccess || hipMemset(e->d_ovl, 0, n * sizeof(uint32_t)) != hipSuccess) {
-            fail(MPPI_ERR_HIP, "overlap counters");
-            mppi_destroy(e);
-            return MPPI_ERR_HIP;
-        }
-        f.xovl = e->d_ovl;
-        p.ovl = e->d_ovl;
-        p.ovl_n = e->A * e->fin_ts;
+
+    if ((st = allocate(e)) == MPPI_OK) {
+        bind(e);
+        st = upload(e);
     }
-    {   // the finalize's tail parameters, one device copy per launch kind (constant for the
-        // engine's life): the control step's FINAL, a shard's PACK, and FINAL into the device
-        // scratch outputs (mppi_kernel_timing, probes)
-        FinTail t[kTailSlots];
-        t[kTailFinal] = tail_of(f, 0);
-        t[kTailPack] = tail_of(f, 1);
-        t[kTailScratch] = tail_of(f, 0);
-        t[kTailScratch].out = (double*)e->d_out;
-        t[kTailScratch].u0 = (float*)(e->d_out + off_u0(e));
-        t[kTailScratch].stats = (float*)(e->d_out + off_stats(e));
-        t[kTailScratch].flags = (uint32_t*)(e->d_out + off_flags(e));
-        t[kTailScratch].xerr = (uint32_t*)(e->d_out + off_xerr(e));
-        t[kTailScratch].wraw = nullptr;
-        t[kTailScratch].wsmooth = nullptr;
-        // the step's FINAL stores no readback copies of w_eps: mppi_get_weighted_noise recomputes
-        // them from the last step's records (READBACK), so the step's tail carries no extra stores
-        t[kTailFinal].wraw = nullptr;
-        t[kTailFinal].wsmooth = nullptr;
-        t[kTailReadback] = tail_of(f, 2);
-        hipError_t te = hipMalloc(&e->d_tail, sizeof(t));
-        if (te == hipSuccess) te = hipMemcpy(e->d_tail, t, sizeof(t), hipMemcpyHostToDevice);
-        if (te != hipSuccess) {
-            fail(MPPI_ERR_HIP, "finalize tail parameters: %s", hipGetErrorString(te));
-            mppi_destroy(e);
-            return MPPI_ERR_HIP;
-        }
-        f.tail = e->d_tail + kTailFinal;
+    if (st != MPPI_OK) {   // (mppi_destroy leaves the error message as it is)
+        mppi_destroy(e);
+        return st;
     }
     *out = e;
     return MPPI_OK;
@@ -594,9 +458,7 @@ mppi_status mppi_set_u_prev(mppi_engine* e, const float* u) {
 mppi_status mppi_get_u_prev(mppi_engine* e, float* u) {
     if (!e || !u) return fail(MPPI_ERR_INVALID_ARG, "null argument");
     if (use_device(e)) return MPPI_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(u, e->d_u_prev, sizeof(float) * e->V * e->H * e->A, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return MPPI_OK;
+    return download(e, u, e->d_u_prev, sizeof(float) * e->V * e->H * e->A);
 }
 
 mppi_status mppi_set_state(mppi_engine* e, const double* state) {
@@ -640,21 +502,9 @@ mppi_status mppi_kernel_timing_ex(mppi_engine* e, int32_t n, double* rollout_us,
     DevParams p = e->dp;
     p.vc0 = e->h_vc[0];
     p.step_ctr = e->step_ctr;
-    FinParams f = e->fp;
-    f.mode = 0;
-    f.seq = 0u;   // the throughput path's finalize (no completion flag)
-    final_records(e, f);
-    // the timing loop's outputs go to device scratch (same layout as the mapped host
-    // buffer), so a pending read_outputs / get_weighted_noise still returns the last
-    // real step; u_prev is restored below (the trajectory and S are overwritten).  On a
-    // shard the finalize combines the exchange slots as they stand (no collective here).
-    f.out = (double*)e->d_out;
-    f.u0 = (float*)(e->d_out + off_u0(e));
-    f.stats = (float*)(e->d_out + off_stats(e));
-    f.flags = (uint32_t*)(e->d_out + off_flags(e));
-    f.wraw = nullptr;
-    f.wsmooth = nullptr;
-    f.tail = e->d_tail + kTailScratch;   // (the same outputs, from the kernel's device-resident copy)
+    // the timing loop's outputs go to device scratch; u_prev is restored below (the trajectory
+    // and S are overwritten)
+    FinParams f = scratch_final(e);
     if (e->out_dbg == 2) f.tail = e->d_tail + kTailFinal;   // diagnostic: outputs into mapped host memory
     float ms0 = 0.0f, ms1 = 0.0f, ms2 = 0.0f;
     int rc = 0;
@@ -706,12 +556,7 @@ extern "C" mppi_status mppi_probe_sequence(mppi_engine* e, int32_t n, int32_t mo
     p.step_ctr = e->step_ctr;
     DevParams p1 = p;
     p1.nb = 1;
-    FinParams f = e->fp;
-    f.mode = 0; f.seq = 0u;
-    final_records(e, f);
-    f.out = (double*)e->d_out; f.u0 = (float*)(e->d_out + off_u0(e)); f.stats = (float*)(e->d_out + off_stats(e));
-    f.flags = (uint32_t*)(e->d_out + off_flags(e)); f.wraw = nullptr; f.wsmooth = nullptr;
-    f.tail = e->d_tail + kTailScratch;
+    const FinParams f = scratch_final(e);
     const int fb = 8 * ((e->A + 7) / 8) * ((e->H + 7) / 8) * e->V;
     hipEvent_t a, b;
     (void)hipEventCreate(&a); (void)hipEventCreate(&b);
@@ -739,9 +584,7 @@ mppi_status mppi_kernel_timing(mppi_engine* e, int32_t n, double* rollout_us, do
 mppi_status mppi_get_costs(mppi_engine* e, float* S) {
     if (!e || !S) return fail(MPPI_ERR_INVALID_ARG, "null argument");
     if (use_device(e)) return MPPI_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(S, e->d_S, sizeof(float) * e->V * e->K, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return MPPI_OK;
+    return download(e, S, e->d_S, sizeof(float) * e->V * e->K);
 }
 
 mppi_status mppi_get_weights(mppi_engine* e, float* w) {
@@ -749,19 +592,14 @@ mppi_status mppi_get_weights(mppi_engine* e, float* w) {
     if (use_device(e)) return MPPI_ERR_HIP;
     int rc = mppi_launch_weights(e->d_S, e->fp.stats, e->d_w, e->V, e->K, e->dp.coef, e->stream);
     if (rc) return fail(MPPI_ERR_HIP, "weights launch failed (%d)", rc);
-    HIP_TRY(hipMemcpyAsync(w, e->d_w, sizeof(float) * e->V * e->K, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return MPPI_OK;
+    return download(e, w, e->d_w, sizeof(float) * e->V * e->K);
 }
 
 mppi_status mppi_get_noise(mppi_engine* e, float* eps) {
     if (!e || !eps) return fail(MPPI_ERR_INVALID_ARG, "null argument");
     if (!e->d_noise_out) return fail(MPPI_ERR_STATE, "engine created without store_noise");
     if (use_device(e)) return MPPI_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(eps, e->d_noise_out, sizeof(float) * (size_t)e->V * e->K * e->H * e->A,
-                           hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return MPPI_OK;
+    return download(e, eps, e->d_noise_out, sizeof(float) * (size_t)e->V * e->K * e->H * e->A);
 }
 
 mppi_status mppi_get_trajectory(mppi_engine* e, float* traj) {
@@ -771,24 +609,13 @@ mppi_status mppi_get_trajectory(mppi_engine* e, float* traj) {
     const size_t KH = (size_t)e->K * e->H, n = traj_floats(e);
     const size_t hp = (size_t)traj_pitch(e), plane = n / ((size_t)e->V * e->C);   // padded plane
     std::vector<float> soa(n);
-    HIP_TRY(hipMemcpyAsync(soa.data(), e->d_traj, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const int Cr = mppi_traj_channels(&e->cfg);
-    const bool has_ee = e->cfg.model == MPPI_MODEL_ARM || e->cfg.model == MPPI_MODEL_WHOLEBODY;
-    const int nstate = has_ee ? e->A : e->C;
+    if (download(e, soa.data(), e->d_traj, n * sizeof(float))) return MPPI_ERR_HIP;
+    const size_t Cr = mppi_traj_channels(&e->cfg), H = e->H;
     const bool t_major = e->cfg.model == MPPI_MODEL_QUADROTOR;   // (V,C,H,K) planes (k_rollout_quad)
-    for (int v = 0; v < e->V; ++v)
-        for (size_t i = 0; i < KH; ++i) {
-            float* dst = traj + ((size_t)v * KH + i) * Cr;
-            const size_t ii = t_major ? (i % e->H) * hp + i / e->H : (i / e->H) * hp + i % e->H;
-            const float* src = soa.data() + (size_t)v * e->C * plane + ii;
-            for (int c = 0; c < nstate; ++c) dst[c] = src[c * plane];
-            if (has_ee) {
-                float* ee = dst + nstate;
-                for (int r = 0; r < 12; ++r) ee[r] = src[(nstate + r) * plane];
-                ee[12] = 0.0f; ee[13] = 0.0f; ee[14] = 0.0f; ee[15] = 1.0f;
-            }
-        }
+    for (size_t v = 0; v < (size_t)e->V; ++v)
+        planes_to_rows(e, soa.data() + v * e->C * plane, plane, KH,
+                       [&](size_t i) { return t_major ? (i % H) * hp + i / H : (i / H) * hp + i % H; },
+                       traj + v * KH * Cr);
     return MPPI_OK;
 }
 
@@ -807,8 +634,8 @@ mppi_status mppi_get_weighted_noise(mppi_engine* e, float* raw, float* smoothed)
     f.tail = e->d_tail + kTailReadback;
     const int rc = mppi_launch_finalize(&f, e->stream);
     if (rc != 0) return fail(MPPI_ERR_HIP, "weighted-noise readback launch failed (%d)", rc);
-    if (raw) HIP_TRY(hipMemcpyAsync(raw, e->d_wraw, n, hipMemcpyDeviceToHost, e->stream));
-    if (smoothed) HIP_TRY(hipMemcpyAsync(smoothed, e->d_wsmooth, n, hipMemcpyDeviceToHost, e->stream));
+    if (raw) HIP_TRY(hipMemcpyAsync(raw, e->d_wraw, n, hipMemcpyDeviceToHost, e->stream));   // (both under one synchronise)
+    if (smoothed) return download(e, smoothed, e->d_wsmooth, n);
     HIP_TRY(hipStreamSynchronize(e->stream));
     return MPPI_OK;
 }
@@ -849,22 +676,10 @@ mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos
     if (cost_t) std::memcpy(cost_t, e->h_plan + n_traj, n_vh * sizeof(float));
     if (pos_err) std::memcpy(pos_err, e->h_plan + n_traj + n_vh, n_vh * sizeof(float));
     if (S) std::memcpy(S, e->h_plan + n_traj + 2 * n_vh, V * sizeof(float));
-    if (traj) {   // planes (V,C,H) -> (V,H,Cr), the per-(t) layout of mppi_get_trajectory
-        const int Cr = mppi_traj_channels(&e->cfg);
-        const bool has_ee = e->cfg.model == MPPI_MODEL_ARM || e->cfg.model == MPPI_MODEL_WHOLEBODY;
-        const int nstate = has_ee ? e->A : e->C;
-        for (size_t v = 0; v < V; ++v)
-            for (size_t t = 0; t < H; ++t) {
-                float* dst = traj + (v * H + t) * Cr;
-                const float* src = e->h_plan + v * C * H + t;
-                for (int c = 0; c < nstate; ++c) dst[c] = src[(size_t)c * H];
-                if (has_ee) {
-                    float* ee = dst + nstate;
-                    for (int r = 0; r < 12; ++r) ee[r] = src[(size_t)(nstate + r) * H];
-                    ee[12] = 0.0f; ee[13] = 0.0f; ee[14] = 0.0f; ee[15] = 1.0f;
-                }
-            }
-    }
+    // planes (V,C,H) -> (V,H,Cr), the per-(t) layout of mppi_get_trajectory
+    for (size_t v = 0; traj && v < V; ++v)
+        planes_to_rows(e, e->h_plan + v * C * H, H, H, [](size_t t) { return t; },
+                       traj + v * H * mppi_traj_channels(&e->cfg));
     return MPPI_OK;
 }
 

@@ -4,7 +4,11 @@
 // The host side of libmppi_hip.so is split by concern:
 //   mppi_host_math.cpp   error state, config defaults and validation, the reference's fp32 tensor
 //                        builders (joint origins, base and target rotations), SavGol taps, host FK
-//   mppi_engine.cpp      create / destroy, buffers, state and target uploads, readbacks, timing
+//   mppi_layout.cpp      layout_of: what create derives from a configuration without a device -- sizes,
+//                        launch geometry, Sigma^-1, the baked chain, the kernels' parameter structs
+//                        (mppi_layout.h; no HIP, so it runs and is tested without a GPU)
+//   mppi_engine.cpp      create (allocate, bind, upload) / destroy, the finalize tails, state and
+//                        target uploads, readbacks, timing
 //   mppi_step.cpp        the control step: rollout, finalize, outputs, native (AQL) batches and calls
 //   mppi_exchange.cpp    the sharded step's exchanges: the engine-owned RCCL communicator and the
 //                        peer exchange (regions, connect, probe, status, reset)
@@ -26,24 +30,15 @@
 #include <vector>
 
 #include "mppi_aql.h"
-#include "mppi_dev.h"
-
-// mppi_engine::generic with every part switched back (MPPI_GENERIC_KERNELS=1)
-constexpr int kGenericAll = 15;
+#include "mppi_layout.h"
 
 // Whose completion the pending outputs wait for: nothing to read; a HIP-launched read step (its
 // tagged records, ev_out as the backstop); a native batch (its completion signal); a native
 // control call (its records, tagged with a bit-31 sequence number).
 enum class Pending { None, Hip, Batch, Call };
 
-struct mppi_engine {
-    mppi_config cfg;
-    int K, H, A, V, nq, qoff, state_dim, out_dim, C, threads;
-    int64_t out_bytes;
-    mppi::DevParams dp;
-    mppi::FinParams fp;
-    float sg_taps[mppi::kMaxW];
-    float fixedM[12];                   // product of the leading fixed joints (folded into base)
+// The layout (cfg, the sizes, dp, fp, ...: mppi_layout.h) and the device state built on it.
+struct mppi_engine : mppi_host::EngineLayout {
     hipStream_t own_stream = nullptr, stream = nullptr;
     float* d_sigma = nullptr;
     mppi::JointDev* d_joints = nullptr;
@@ -67,11 +62,6 @@ struct mppi_engine {
     mppi::LaunchDesc batch_fin_quiet{}; // the quiet FINAL of the batch's steps before its last (the same
                                         // description as batch_fin where no quiet kernel applies)
     mppi::LaunchDesc batch_roll_quiet{};   // likewise the quiet rollout of those steps (or batch_roll's launch)
-    int generic = 0;                    // MPPI_GENERIC_KERNELS=1 (tests, A/B): the kernels as before the role and
-                                        // fixed-block ones.  Bits: 1 the finalize of every role with run-time
-                                        // geometry, 2 the full FINAL on every step, 4 the rollout of every block
-                                        // size, 8 the full rollout on every step ("finalize", "quiet",
-                                        // "rollout", "quiet_rollout" set one of them; 1 sets all: kGenericAll)
     // the kernels the last batch and the last control call ran (mppi_kernel_info)
     std::string kern_batch = "none", kern_call = "none";
     int kern_batch_state = 0;           // kern_batch describes the resident native batch: 1 one step, 2 several
@@ -91,7 +81,6 @@ struct mppi_engine {
     float* d_S = nullptr;
     float* d_hdr = nullptr;     // (V,nb,4) block record headers
     float* d_rdata = nullptr;   // (V,A,nb,H) block record bodies
-    int fin_ts = 1, fin_tsz = 8;   // finalize t-slices
     unsigned char* d_out = nullptr;   // device scratch in h_out's layout (mppi_kernel_timing's outputs)
     mppi::FinTail* d_tail = nullptr;  // [kTailSlots] the finalize's tail parameters per launch kind
     float* d_wraw = nullptr;
@@ -167,10 +156,6 @@ struct mppi_engine {
 
 namespace mppi_host {
 
-// ------------------------------------------------------------- errors (mppi_host_math.cpp)
-// Sets the calling thread's mppi_last_error string and returns st.
-mppi_status fail(mppi_status st, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t _e = (expr);                                                                    \
@@ -179,33 +164,29 @@ mppi_status fail(mppi_status st, const char* fmt, ...) __attribute__((format(pri
                                      hipGetErrorString(_e), __FILE__, __LINE__);                   \
     } while (0)
 
-// ------------------------------------------- reference fp32 builders (mppi_host_math.cpp)
-int nq_of(const mppi_config& c);
-mppi_status validate(const mppi_config& c);
-void rpy_to_R(float r, float p, float y, float* R);
-void joint_origin(const mppi_joint& j, float* T16);
-void unit_axis(const mppi_joint& j, float* a);
-void base_from_xyzquat(const double* b, bool f64, float* T16);
-void quat_xyzw_to_R(const float* q, float* R);
-void euler_zyx(const float* m, float* ypr);
-int savgol_taps(int window, int order, float* c);
-void bake_joint(const mppi_joint& j, mppi::JointDev& d);
-void mul34(const float* A, const float* B, float* C);
-void fk_consts(const mppi_joint* joints, int nj, float* O16s, float* axes);
-void host_fk_c(const mppi_joint* joints, int nj, const float* O16s, const float* axes, const double* q,
-               const double* xyzquat, bool f64, float* out16);
-void host_fk(const mppi_joint* joints, int nj, const double* q, const double* xyzquat, bool f64, float* out16);
-
 // ------------------------------------------------------------ engine (mppi_engine.cpp)
 // the step goes through the exchange slots: several shards, or an engine-owned communicator (a
 // one-rank communicator runs the same pack -> all-reduce -> combine).  A shard connected by the
 // peer exchange steps like an unsharded engine: its finalize does the exchange.
 inline bool sharded(const mppi_engine* e) { return (e->cfg.shard_count > 1 || e->comm) && !e->peer; }
-mppi::FinTail tail_of(const mppi::FinParams& f, int32_t mode);
 void pack_fields(const mppi_engine* e, mppi::FinParams& f);
-mppi_status upload_pack_tail(mppi_engine* e);
-int traj_pitch(const mppi_engine* e);
-size_t traj_floats(const mppi_engine* e);
+// out, u0, stats and flags of a FinParams or FinTail over an output buffer in h_out's layout
+template <class X>
+inline void bind_outputs(X& x, unsigned char* base, const mppi_engine* e) {
+    x.out = (double*)base;
+    x.u0 = (float*)(base + off_u0(e));
+    x.stats = (float*)(base + off_stats(e));
+    x.flags = (uint32_t*)(base + off_flags(e));
+}
+// The finalize's tail parameters, one device copy per launch kind (d_tail[kTailSlots]); each kind
+// is derived from e->fp as it stands, and written again when a member it carries changes.
+struct Tails { mppi::FinTail t[mppi::kTailSlots]; };
+Tails tails_of(const mppi_engine* e);
+// synchronises the engine's stream, then copies the given kinds' tails (a bit per kTail* slot)
+mppi_status upload_tails(mppi_engine* e, unsigned slots);
+inline mppi_status upload_pack_tail(mppi_engine* e) { return upload_tails(e, 1u << mppi::kTailPack); }
+// async copy to the host on the engine's stream, then synchronise
+mppi_status download(mppi_engine* e, void* dst, const void* src, size_t bytes);
 mppi_status aql_join(mppi_engine* e);
 mppi_status use_device(mppi_engine* e);
 mppi_status build_vehicle_consts(mppi_engine* e);
@@ -214,19 +195,6 @@ mppi_status upload_consts(mppi_engine* e);
 hipEvent_t pool_event(mppi_engine* e);
 mppi_status drain_timing(mppi_engine* e);
 
-// mapped output buffer layout (h_out): outputs, u0, stats, then the tagged records of a read step
-// (k_finalize): per vehicle, 2 per dim -- (o1, u0, seq), (o2, nan flag, seq) -- and one
-// (rho, eta, ess, seq), 16 B each, each written by ONE store; the host polls their tags and takes
-// the values from the records themselves
-inline size_t off_u0(const mppi_engine* e) { return ((size_t)e->V * e->out_dim * sizeof(double) + 15) & ~size_t(15); }
-inline size_t off_stats(const mppi_engine* e) {
-    return (off_u0(e) + (size_t)e->V * e->A * sizeof(float) + 15) & ~size_t(15);
-}
-inline size_t off_flags(const mppi_engine* e) { return off_stats(e) + (size_t)e->V * 16; }
-inline size_t rec_count(const mppi_engine* e) { return (size_t)e->V * (2 * e->A + 1); }
-// the peer exchange's sticky timeout word (16 B after the records): the step tag of a finalize
-// block that gave a step up, written by that block, cleared only by the host (mppi_peer_reset)
-inline size_t off_xerr(const mppi_engine* e) { return off_flags(e) + rec_count(e) * 16; }
 inline uint32_t sticky_timeout(const mppi_engine* e) {
     return e->h_out ? *(const volatile uint32_t*)(e->h_out + off_xerr(e)) : 0u;
 }

@@ -229,11 +229,10 @@ static mppi_status peer_bind(mppi_engine* e, std::vector<unsigned long long*> pt
     }
     FinParams& f = e->fp;
     f.xpeers = e->d_xpeers; f.xlocal = xdata(e); f.xn = n; f.xme = me; f.xdec = e->d_xdec;
-    FinTail t[2] = {tail_of(f, 0), tail_of(f, 2)};
-    t[0].wraw = t[0].wsmooth = nullptr;   // (as at create: the step's FINAL stores no readback copies)
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(e->d_tail + kTailFinal, &t[0], sizeof(FinTail), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->d_tail + kTailReadback, &t[1], sizeof(FinTail), hipMemcpyHostToDevice));
+    // (PACK and SCRATCH stay as create wrote them: a peer engine packs nothing, and the timing loop
+    // keeps running the finalize without the exchange)
+    mppi_status st = upload_tails(e, 1u << kTailFinal | 1u << kTailReadback);
+    if (st != MPPI_OK) return st;
     e->peer = true;
     e->call_cached = false;
     return MPPI_OK;
@@ -378,10 +377,8 @@ int32_t mppi_debug_peer_stall(mppi_engine* e, int32_t block, int32_t ms) {
     if (!e->d_xstall) {
         HIP_TRY(hipMalloc(&e->d_xstall, sizeof(uint32_t)));
         e->fp.xstall = e->d_xstall;
-        FinTail t = tail_of(e->fp, 0);
-        t.wraw = t.wsmooth = nullptr;   // (as at create)
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipMemcpy(e->d_tail + kTailFinal, &t, sizeof(FinTail), hipMemcpyHostToDevice));
+        mppi_status st = upload_tails(e, 1u << kTailFinal);
+        if (st != MPPI_OK) return st;
         e->call_cached = e->batch_cached = false;
     }
     const uint32_t w = ms ? ((uint32_t)ms << 16) | (uint32_t)block : 0u;

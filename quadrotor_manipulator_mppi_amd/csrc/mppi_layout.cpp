@@ -1,0 +1,236 @@
+// mppi_layout.cpp -- layout_of: the launch geometry, the baked tables and the kernels' parameter
+// structs of a configuration, as far as they do not depend on a device address.  Pure host code (no
+// HIP), so every decision that picks a kernel can be replayed without a GPU: mppi_debug_layout below
+// reports them, with a hash over the two structs.  mppi_create (mppi_engine.cpp) allocates, binds the
+// device pointers and uploads.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <utility>
+
+#include "mppi_layout.h"
+
+using namespace mppi;
+
+namespace mppi_host {
+
+// L, R, nch, nb, iters and the block size into l.dp / l.threads
+static mppi_status geometry(EngineLayout& l) {
+    const mppi_config& c = l.cfg;
+    const int H = l.H;
+    const int L = (H > 32) ? 64 : 32;
+    const int nch = (H + 63) / 64;
+    if (nch != 1 && nch != 2 && nch != 4)
+        return fail(MPPI_ERR_INVALID_ARG, "H=%d: supported horizons are <= 128 or 193..256", H);
+    const int R = 64 / L;
+    l.threads = c.block_threads ? c.block_threads : 512;
+    const int nw = l.threads / 64;
+    const int groups = (l.K + nw * R - 1) / (nw * R);
+    int nb = c.blocks_per_vehicle;
+    // auto: one block per group (iters == 1: the single-group kernel) while the grid is at
+    // most 512 blocks (2 per CU); above that >= 2 groups per block (the looping kernel; the
+    // prologue and the block combine are amortised, fewer records for the finalize),
+    // capped at 1024 blocks in total.  Re-measured on MI355X in round 5 (tools/probes.py geom,
+    // profiles/r05/geom): WB K=8192 step pair 17.6 us at 512 looping blocks vs 19.5-20.7 at 1024
+    // single-group blocks (whose finalize also reads twice the records) and 18.3 at 256; K=65536
+    // best at 1024 (85.2-86.1 us pairs vs 87.6-92.9 at 512, 89.1+ with 256-thread blocks).
+    if (nb <= 0) {
+        nb = (groups * l.V <= 512) ? groups : std::min(std::max(1, groups / 2), std::max(1, 1024 / l.V));
+    }
+    nb = std::min(nb, groups);
+    int iters = (groups + nb - 1) / nb;
+    // a block's cost run (iters * nw * R samples) is staged in LDS for one write-through store
+    // (k_rollout): at most kMaxCostRun floats, more blocks otherwise
+    iters = std::min(iters, std::max(1, kMaxCostRun / cost_run_stride(nw * R)));
+    nb = (groups + iters - 1) / iters;
+    if (c.model == MPPI_MODEL_QUADROTOR) {   // k_rollout_quad: 16 rollouts (4 lanes each) per dynamics
+        l.threads = 256;                      // wave; 1 dynamics wave per block up to 1024 blocks, else 4
+        iters = ((l.K + 15) / 16 * l.V <= 1024) ? 1 : 4;   // (carried in DevParams::iters)
+        nb = (l.K + 16 * iters - 1) / (16 * iters);
+    }
+    if (nb > 4096) return fail(MPPI_ERR_INVALID_ARG, "too many rollout blocks (%d)", nb);
+    // the rollout kernels address one vehicle's trajectory planes through a buffer
+    // resource (32-bit byte offsets) and the record bodies with 32-bit indices
+    if (c.store_trajectory && (uint64_t)l.C * ((l.K + 15) & ~15) * ((H + 15) & ~15) * sizeof(float) > 0xFFFFFFFFull)
+        return fail(MPPI_ERR_INVALID_ARG, "trajectory of one vehicle (C=%d x K=%d x H=%d floats) exceeds 4 GiB: "
+                    "disable store_trajectory or shard the samples", l.C, l.K, H);
+    if ((uint64_t)l.V * l.A * nb * H >= 0x80000000ull)
+        return fail(MPPI_ERR_INVALID_ARG, "record bodies (V=%d x A=%d x %d blocks x H=%d = %llu floats) exceed 2^31",
+                    l.V, l.A, nb, H, (unsigned long long)l.V * l.A * nb * H);
+    l.dp.L = L; l.dp.R = R; l.dp.nch = nch; l.dp.nb = nb; l.dp.iters = iters;
+    return MPPI_OK;
+}
+
+// Sigma^-1 (covar_cost.py:21) and gamma^t (action_cost.py:21)
+static mppi_status cost_tables(EngineLayout& l) {
+    const mppi_config& c = l.cfg;
+    const int A = l.A, W2 = 2 * A;
+    std::vector<double> m(A * W2, 0.0);
+    for (int i = 0; i < A; ++i) {
+        for (int j = 0; j < A; ++j) m[i * W2 + j] = c.sigma[i * A + j];
+        m[i * W2 + A + i] = 1.0;
+    }
+    for (int col = 0; col < A; ++col) {   // Gauss-Jordan, partial pivoting, fp64
+        int piv = col;
+        for (int r = col + 1; r < A; ++r)
+            if (std::fabs(m[r * W2 + col]) > std::fabs(m[piv * W2 + col])) piv = r;
+        if (std::fabs(m[piv * W2 + col]) < 1e-30) return fail(MPPI_ERR_INVALID_ARG, "Sigma is singular");
+        for (int j = 0; j < W2; ++j) std::swap(m[col * W2 + j], m[piv * W2 + j]);
+        const double d = m[col * W2 + col];
+        for (int j = 0; j < W2; ++j) m[col * W2 + j] /= d;
+        for (int r = 0; r < A; ++r)
+            if (r != col) {
+                const double f2 = m[r * W2 + col];
+                for (int j = 0; j < W2; ++j) m[r * W2 + j] -= f2 * m[col * W2 + j];
+            }
+    }
+    l.sinv.resize(A * A);
+    l.gamma_t.resize(l.H);
+    for (int i = 0; i < A; ++i)
+        for (int j = 0; j < A; ++j) l.sinv[i * A + j] = (float)m[i * W2 + A + j];
+    for (int t = 0; t < l.H; ++t) l.gamma_t[t] = std::pow(c.cost_gamma, (float)t);
+    return MPPI_OK;
+}
+
+// the baked joint table, the leading fixed joints folded into fixedM (dp.j0), and the FK path
+// the unfolded chain allows (dp.chain_fast)
+static void chain(EngineLayout& l) {
+    const mppi_config& c = l.cfg;
+    JointDev* jd = l.joints;
+    std::memset(jd, 0, sizeof(l.joints));
+    for (int j = 0; j < c.n_joints; ++j) bake_joint(c.joints[j], jd[j]);
+    // fold the leading fixed joints of the chain into the per-vehicle base transform
+    const float I12[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    std::memcpy(l.fixedM, I12, sizeof(I12));
+    int j0 = 0;
+    while (c.model != MPPI_MODEL_DRONE && j0 < c.n_joints && jd[j0].type == MPPI_JOINT_FIXED) {
+        mul34(l.fixedM, jd[j0].O, l.fixedM);
+        ++j0;
+    }
+    l.dp.j0 = j0;
+    // fast FK path: the unfolded chain is exactly nq revolute-z joints in q order
+    bool fast = c.model != MPPI_MODEL_DRONE && (c.n_joints - j0) == l.nq;
+    for (int j = j0; fast && j < c.n_joints; ++j)
+        fast = jd[j].type == MPPI_JOINT_REVOLUTE && jd[j].axis_z && jd[j].q_index == j - j0;
+    l.dp.chain_fast = fast;
+    if (fast && l.nq == 7 && c.n_joints - j0 == 7) {   // Kinova origin table (mppi_dev.h kKinova)
+        bool kin = true;
+        for (int j = 0; kin && j < 7; ++j) {
+            const float* O = jd[j0 + j].O;
+            const KinOrigin& k = kKinova[j];
+            for (int col = 0; kin && col < 3; ++col)
+                for (int row = 0; kin && row < 3; ++row) {
+                    const float want = (row == k.p[col]) ? (float)k.s[col] : 0.0f;
+                    kin = std::fabs(O[4 * row + col] - want) <= 1e-6f;
+                }
+            for (int d = 0; kin && d < 3; ++d) kin = ((k.tmask >> d) & 1) ? true : (O[4 * d + 3] == 0.0f);
+        }
+        if (kin && !getenv("MPPI_NO_KINOVA_PATH")) l.dp.chain_fast = 2;
+    }
+}
+
+mppi_status layout_of(const mppi_config& cfg, EngineLayout& l) {
+    l.cfg = cfg;
+    if (l.cfg.model == MPPI_MODEL_WHOLEBODY) l.cfg.state_f64 = 0;
+    const mppi_config& c = l.cfg;
+    l.K = c.n_samples; l.H = c.n_horizon; l.A = c.n_action; l.V = c.n_vehicles;
+    l.nq = nq_of(c);
+    l.qoff = (c.model == MPPI_MODEL_WHOLEBODY) ? 3 : 0;
+    l.state_dim = mppi_state_dim(&c);
+    l.out_dim = mppi_output_dim(&c);
+    l.C = (c.model == MPPI_MODEL_DRONE) ? 3 : (c.model == MPPI_MODEL_QUADROTOR) ? 6 : l.A + 12;
+    l.out_bytes = (int64_t)(off_xerr(&l) + 16);
+    const int H = l.H, P = (kHdr + l.A * H + 3) & ~3;
+
+    DevParams& p = l.dp;
+    std::memset(&p, 0, sizeof(p));
+    mppi_status st = geometry(l);
+    if (st != MPPI_OK) return st;
+    if (savgol_taps(c.savgol_window, c.savgol_order, l.sg_taps) != 0)
+        return fail(MPPI_ERR_INVALID_ARG, "bad SavGol window/order");
+    l.sinv.clear();
+    l.gamma_t.clear();
+    if (c.cost_terms && (st = cost_tables(l)) != MPPI_OK) return st;
+    chain(l);
+
+    p.model = c.model; p.V = l.V; p.K = l.K; p.H = H; p.A = l.A;
+    p.nq = l.nq; p.qoff = l.qoff; p.nj = c.n_joints;
+    // (the vehicle offset in the high half: the rollouts' fleet-wide Philox vehicle key)
+    p.noise_mode = c.noise_mode | (c.vehicle_offset << 16); p.state_f64 = c.state_f64;
+    p.store_traj = c.store_trajectory; p.store_noise = c.store_noise;
+    bool diag = true;
+    for (int a = 0; a < l.A; ++a)
+        for (int b = 0; b < l.A; ++b) {
+            if (a == b) p.sdiag[a] = c.sigma[a * l.A + b];
+            else if (c.sigma[a * l.A + b] != 0.0f) diag = false;
+        }
+    p.sigma_diag = diag;
+    p.P = P; p.C = l.C; p.hp = traj_pitch(&l);
+    p.seed_lo = (uint32_t)c.seed; p.seed_hi = (uint32_t)(c.seed >> 32);
+    p.k_offset = (int64_t)c.shard_rank * l.K;
+    p.dt = (float)c.dt; p.dt2 = (float)(c.dt * c.dt); p.dt_d = c.dt;
+    p.coef = (float)(-1.0 / c.lambda_);
+    p.w_sp = c.w_stage_pos; p.w_so = c.w_stage_ori; p.w_tp = c.w_term_pos; p.w_to = c.w_term_ori;
+    p.cost_terms = c.cost_terms;
+    p.w_cov = (float)((double)c.w_covar * (c.lambda_ * (1.0 - (double)c.cost_alpha)));   // covar_cost.py:15,24
+    p.w_cen = c.w_center; p.w_jt = c.w_joint_track; p.w_act = c.w_action; p.lim_pen = c.joint_limit_penalty;
+    p.q_inv_m = (float)(1.0 / (double)c.quad_mass);   // 1/self.m as a Python float, used in fp32
+    for (int d = 0; d < 3; ++d) p.q_iinv[d] = (float)(1.0 / (double)c.quad_inertia[d]);
+    p.q_kd = c.quad_kd; p.q_g = c.quad_gravity; p.q_literal_jinv = c.quad_literal_jinv ? 1 : 0;
+
+    FinParams& f = l.fp;
+    std::memset(&f, 0, sizeof(f));
+    f.model = c.model; f.V = l.V; f.H = H; f.A = l.A; f.nq = l.nq; f.qoff = l.qoff;
+    f.state_f64 = c.state_f64; f.P = P;
+    // (diagnostics: MPPI_FIN_TSZ = t per finalize slice, for the slice-count / fetch trade-off
+    // measured in profiles/r05/finalize_fetch; 8 is the measured best)
+    l.fin_tsz = 8;
+    if (const char* z = getenv("MPPI_FIN_TSZ")) {
+        const int tz = atoi(z);
+        if (tz >= 1 && tz + 2 * (c.savgol_window / 2) <= 64) l.fin_tsz = tz;
+    }
+    f.tsz = l.fin_tsz; f.ts = l.fin_ts = (H + l.fin_tsz - 1) / l.fin_tsz;
+    f.window = c.savgol_window; f.half = c.savgol_window / 2;
+    for (int j = 0; j < c.savgol_window; ++j) f.sg[j] = l.sg_taps[c.savgol_window - 1 - j];
+    f.coef = p.coef; f.dt = p.dt; f.dt2 = p.dt2; f.dt_d = c.dt;
+    f.out_dim = l.out_dim;
+    l.generic = 0;
+    if (const char* g = getenv("MPPI_GENERIC_KERNELS"))   // 1: all of them; one part by name (A/B of the parts)
+        l.generic = !strcmp(g, "finalize") ? 1 : !strcmp(g, "quiet") ? 2 : !strcmp(g, "rollout") ? 4
+                    : !strcmp(g, "quiet_rollout") ? 8 : atoi(g) != 0 ? kGenericAll : 0;
+    f.kern = (l.generic & 1) ? kFinKernGeneric : 0;
+    p.kern = (l.generic & 4) ? kRollKernGeneric : 0;   // (kRollKernQuiet: per launch, mppi_step.cpp)
+    return MPPI_OK;
+}
+
+}  // namespace mppi_host
+
+using namespace mppi_host;
+
+// Diagnostic (not part of the public header): the layout of a configuration without a device.
+// out[0..27]: threads, L, R, nch, nb, iters, P, C, hp, fin_tsz, fin_ts, j0, chain_fast, sigma_diag,
+// nq, qoff, state_dim, out_dim, generic; the output buffer's offsets of u0, stats, flags and xerr and
+// its size; the trajectory's float count (low, high word); a 64-bit FNV-1a over the bytes of the
+// layout's DevParams, then its FinParams (low, high word).  Returns validate's or layout_of's
+// status (the message in mppi_last_error).
+extern "C" int32_t mppi_debug_layout(const mppi_config* cfg, int32_t* out, int32_t n) {
+    constexpr int kWords = 28;
+    if (!cfg || !out || n < kWords) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_layout: bad arguments");
+    mppi_status st = validate(*cfg);
+    if (st != MPPI_OK) return st;
+    EngineLayout l;
+    if ((st = layout_of(*cfg, l)) != MPPI_OK) return st;
+    uint64_t h = 0xCBF29CE484222325ull;
+    for (const auto& [b, nb] : {std::pair<const void*, size_t>{&l.dp, sizeof(l.dp)}, {&l.fp, sizeof(l.fp)}})
+        for (size_t i = 0; i < nb; ++i) h = (h ^ ((const unsigned char*)b)[i]) * 0x100000001B3ull;
+    const uint64_t tf = traj_floats(&l);
+    const int32_t w[kWords] = {l.threads, l.dp.L, l.dp.R, l.dp.nch, l.dp.nb, l.dp.iters, l.dp.P, l.C, l.dp.hp,
+                               l.fin_tsz, l.fin_ts, l.dp.j0, l.dp.chain_fast, l.dp.sigma_diag, l.nq, l.qoff,
+                               l.state_dim, l.out_dim, l.generic,
+                               (int32_t)off_u0(&l), (int32_t)off_stats(&l), (int32_t)off_flags(&l), (int32_t)off_xerr(&l),
+                               (int32_t)l.out_bytes, (int32_t)(uint32_t)tf, (int32_t)(uint32_t)(tf >> 32),
+                               (int32_t)(uint32_t)h, (int32_t)(uint32_t)(h >> 32)};
+    std::memcpy(out, w, sizeof(w));
+    return MPPI_OK;
+}

@@ -1,0 +1,91 @@
+// mppi_layout.h -- everything mppi_create derives from a configuration before it touches the
+// device (mppi_layout.cpp), with the error function and the host math it is built from.  No HIP:
+// the layout of any configuration can be computed, and checked, on a machine without a GPU
+// (mppi_debug_layout; tests/test_capi_layout_cpu.py).  Internal: not part of the public ABI.
+#pragma once
+#include <vector>
+
+#include "mppi_dev.h"
+
+// mppi_engine::generic with every part switched back (MPPI_GENERIC_KERNELS=1)
+constexpr int kGenericAll = 15;
+
+namespace mppi_host {
+
+// ------------------------------------------------------------- errors (mppi_host_math.cpp)
+// Sets the calling thread's mppi_last_error string and returns st.
+mppi_status fail(mppi_status st, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// ------------------------------------------- reference fp32 builders (mppi_host_math.cpp)
+int nq_of(const mppi_config& c);
+mppi_status validate(const mppi_config& c);
+void rpy_to_R(float r, float p, float y, float* R);
+void joint_origin(const mppi_joint& j, float* T16);
+void unit_axis(const mppi_joint& j, float* a);
+void base_from_xyzquat(const double* b, bool f64, float* T16);
+void quat_xyzw_to_R(const float* q, float* R);
+void euler_zyx(const float* m, float* ypr);
+int savgol_taps(int window, int order, float* c);
+void bake_joint(const mppi_joint& j, mppi::JointDev& d);
+void mul34(const float* A, const float* B, float* C);
+void fk_consts(const mppi_joint* joints, int nj, float* O16s, float* axes);
+void host_fk_c(const mppi_joint* joints, int nj, const float* O16s, const float* axes, const double* q,
+               const double* xyzquat, bool f64, float* out16);
+void host_fk(const mppi_joint* joints, int nj, const double* q, const double* xyzquat, bool f64, float* out16);
+
+// ------------------------------------------------------------ layout (mppi_layout.cpp)
+// The engine's sizes, launch geometry, baked tables and kernel parameters.  The launch geometry (L,
+// R, nch, nb, iters), P, hp, j0, chain_fast, sigma_diag and sdiag are dp's; dp and fp are zeroed
+// (padding included) and then filled in every member that is not a device pointer -- those, and
+// ovl_n, dbg and the per-launch members, mppi_create and the step set.
+struct EngineLayout {
+    mppi_config cfg;                    // as given, but WHOLEBODY without state_f64
+    int K = 0, H = 0, A = 0, V = 0, nq = 0, qoff = 0, state_dim = 0, out_dim = 0, C = 0, threads = 0;
+    int64_t out_bytes = 0;              // the mapped output buffer (off_xerr + 16)
+    mppi::DevParams dp;
+    mppi::FinParams fp;
+    float sg_taps[mppi::kMaxW];
+    float fixedM[12];                   // product of the leading fixed joints (folded into base)
+    mppi::JointDev joints[mppi::kMaxJ]; // the baked chain table
+    std::vector<float> sinv, gamma_t;   // cost_terms: Sigma^-1 (A,A) and gamma^t (H), else empty
+    int fin_ts = 1, fin_tsz = 8;        // finalize t-slices
+    int generic = 0;                    // MPPI_GENERIC_KERNELS=1 (tests, A/B): the kernels as before the role and
+                                        // fixed-block ones.  Bits: 1 the finalize of every role with run-time
+                                        // geometry, 2 the full FINAL on every step, 4 the rollout of every block
+                                        // size, 8 the full rollout on every step ("finalize", "quiet",
+                                        // "rollout", "quiet_rollout" set one of them; 1 sets all: kGenericAll)
+};
+// Reads MPPI_FIN_TSZ, MPPI_NO_KINOVA_PATH and MPPI_GENERIC_KERNELS, the switches that change the
+// layout.  `c` has passed validate(); a configuration past a limit fails with its status and message.
+mppi_status layout_of(const mppi_config& c, EngineLayout& l);
+
+// mapped output buffer layout (h_out): outputs, u0, stats, then the tagged records of a read step
+// (k_finalize): per vehicle, 2 per dim -- (o1, u0, seq), (o2, nan flag, seq) -- and one
+// (rho, eta, ess, seq), 16 B each, each written by ONE store; the host polls their tags and takes
+// the values from the records themselves
+inline size_t off_u0(const EngineLayout* l) { return ((size_t)l->V * l->out_dim * sizeof(double) + 15) & ~size_t(15); }
+inline size_t off_stats(const EngineLayout* l) {
+    return (off_u0(l) + (size_t)l->V * l->A * sizeof(float) + 15) & ~size_t(15);
+}
+inline size_t off_flags(const EngineLayout* l) { return off_stats(l) + (size_t)l->V * 16; }
+inline size_t rec_count(const EngineLayout* l) { return (size_t)l->V * (2 * l->A + 1); }
+// the peer exchange's sticky timeout word (16 B after the records): the step tag of a finalize
+// block that gave a step up, written by that block, cleared only by the host (mppi_peer_reset)
+inline size_t off_xerr(const EngineLayout* l) { return off_flags(l) + rec_count(l) * 16; }
+
+// Trajectory planes: k_rollout rows (one rollout's H steps) are padded to 64 B, hp = H
+// rounded up to 16 floats, and written whole.  With H = 100 the unpadded rows left partial
+// 64 B sectors at both ends of every wave store, which the write-through stores hand to HBM
+// as masked writes: arm K=4096 rollout 20.3 us at H = 100 vs 13.4 at H = 128
+// (profiles/r02/ab_traj_row_pitch.txt).  k_rollout_quad writes t-major (C,H,Kp) planes,
+// its rows (one step's K samples) padded the same way: Kp = K rounded up to 16.
+inline int traj_pitch(const EngineLayout* l) {
+    return l->cfg.model == MPPI_MODEL_QUADROTOR ? (l->K + 15) & ~15 : (l->H + 15) & ~15;
+}
+inline size_t traj_floats(const EngineLayout* l) {   // all vehicles' planes
+    const size_t plane = l->cfg.model == MPPI_MODEL_QUADROTOR ? (size_t)traj_pitch(l) * l->H
+                                                               : (size_t)l->K * traj_pitch(l);
+    return (size_t)l->V * l->C * plane;
+}
+
+}  // namespace mppi_host

@@ -258,12 +258,11 @@ static mppi_status wait_outputs(mppi_engine* e) {
 // (qdes/vdes or x/v per dim, u0, stats).  The plain arrays are the base (the quadrotor's
 // outputs are formed on the host from u0).
 static mppi_status assemble_records(mppi_engine* e) {
-    const int V = e->V, A = e->A, od = e->out_dim, model = e->cfg.model;
+    const int V = e->V, A = e->A, od = e->out_dim, model = e->cfg.model, qoff = e->qoff, nq = e->nq;
     const uint32_t want = e->out_seq;
     e->rec_out.assign((const double*)e->h_out, (const double*)e->h_out + (size_t)V * od);
     e->rec_u0.resize((size_t)V * A);
     e->rec_stats.resize((size_t)V * 4);
-    const int qoff = (model == MPPI_MODEL_WHOLEBODY) ? 3 : 0, nq = A - qoff;
     uint32_t w[4];
     for (int v = 0; v < V; ++v) {
         const size_t r0 = (size_t)v * (2 * A + 1);

@@ -68,7 +68,8 @@ def assert_stream(eps_gpu, seed, step, vehicle, k_global, H, A, sigma, what=""):
 
 
 def geometry(model, K, H, V=1, block_threads=0, blocks_per_vehicle=0):
-    """The rollout launch geometry mppi_create derives (csrc/mppi_engine.cpp, "geometry"), restated:
+    """The rollout launch geometry mppi_create derives (csrc/mppi_layout.cpp, geometry), restated
+    (tests/test_capi_layout_cpu.py holds it to the library over a sweep):
     lane segment L, 64-step chunks nch, rollouts per wave R, waves per block nw, rollout groups,
     blocks per vehicle nb and groups per block iters (iters == 1 with nch == 1 and the common
     kernel: the single-group instantiation; else the looping one)."""
