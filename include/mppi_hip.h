@@ -425,6 +425,26 @@ mppi_status mppi_get_weighted_noise(mppi_engine* e, float* raw, float* smoothed)
  * the control step: nothing the step reads or writes is touched. */
 mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos_err, float* S);
 
+#define MPPI_MAX_ELITES 64
+/* The n lowest-cost samples of the last rollout of every vehicle, best first (synchronous).
+ *   idx  (V,n) int32   sample index within this engine's K (a shard: local; global = shard_rank*K + idx)
+ *   S    (V,n)         their costs: mppi_get_costs()[v, idx]
+ *   w    (V,n)         their softmin weights: mppi_get_weights()[v, idx]
+ *   traj (V,n,H,C)     their rollouts in mppi_get_trajectory's row layout (C = mppi_traj_channels)  [store_trajectory]
+ * Any output pointer may be NULL.
+ * Order: a total order, so every result is unique -- ascending in (cost, index), where -0 counts as
+ * +0, +inf comes after every finite cost, every NaN (any sign or payload) after +inf, and equal
+ * costs go by the lower index first: numpy's argsort(S[v], kind="stable")[:n].
+ * Valid as mppi_get_costs / mppi_get_trajectory are: after mppi_step that call's samples, after
+ * mppi_run_steps the batch's last step, after mppi_rollout that rollout; w uses the rho and eta
+ * mppi_get_weights uses.
+ * Errors: n < 1, n > MPPI_MAX_ELITES or n > K: MPPI_ERR_INVALID_ARG; traj on an engine created
+ * without store_trajectory: MPPI_ERR_STATE (idx, S and w work on such an engine).
+ * Two or three small launches on the engine's stream (select per share of the costs, select and
+ * sort, gather the rows) and one copy, outside the control step: nothing the step reads or writes
+ * is touched.  The buffers are allocated at the first call, for MPPI_MAX_ELITES. */
+mppi_status mppi_get_elites(mppi_engine* e, int32_t n, int32_t* idx, float* S, float* w, float* traj);
+
 /* Kernel timing with HIP events on the engine stream (bench / roofline). */
 mppi_status mppi_enable_timing(mppi_engine* e, int32_t enable);
 mppi_status mppi_get_timing(mppi_engine* e, double* rollout_ms_total, double* finalize_ms_total,

@@ -23,6 +23,7 @@ OK, ERR_INVALID_ARG, ERR_HIP, ERR_NONFINITE, ERR_STATE, ERR_COMM, ERR_PEER_TIMEO
 COST_COVAR, COST_CENTER, COST_JOINT_TRACK, COST_ACTION, COST_JOINT_LIMIT = 1, 2, 4, 8, 16
 ABI_VERSION = 10
 MAX_PEERS = 8
+MAX_ELITES = 64
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 64
 
@@ -127,6 +128,7 @@ PROTOTYPES = {
     "mppi_get_trajectory": (_ST, [_P, _F]),
     "mppi_get_weighted_noise": (_ST, [_P, _F, _F]),
     "mppi_get_plan": (_ST, [_P, _F, _F, _F, _F]),
+    "mppi_get_elites": (_ST, [_P, C.c_int32, _I32, _F, _F, _F]),
     "mppi_enable_timing": (_ST, [_P, C.c_int32]),
     "mppi_get_timing": (_ST, [_P, _D, _D, _I64, _I64]),
     "mppi_kernel_timing": (_ST, [_P, C.c_int32, _D, _D]),

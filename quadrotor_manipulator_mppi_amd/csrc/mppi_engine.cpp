@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "mppi_elites.h"
 #include "mppi_engine.h"
 
 using namespace mppi;
@@ -405,11 +406,12 @@ void mppi_destroy(mppi_engine* e) {
     void* dev[] = {e->d_xregion, e->d_xpeers, e->d_sigma, e->d_joints, e->d_vc, e->d_u_prev, e->d_noise_in, e->d_traj, e->d_noise_out,
                    e->d_S, e->d_hdr, e->d_rdata, e->d_out, e->d_wraw, e->d_wsmooth, e->d_w,
                    e->d_sinv, e->d_gamma, e->d_jtraj, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec,
-                   e->d_plan_vc, e->d_plan};
+                   e->d_plan_vc, e->d_plan, e->d_elite_cand, e->d_elites};
     for (void* p : dev) if (p) (void)hipFree(p);
     if (e->h_out) (void)hipHostFree(e->h_out);
     if (e->h_vc) (void)hipHostFree(e->h_vc);
     if (e->h_plan) (void)hipHostFree(e->h_plan);
+    if (e->h_elites) (void)hipHostFree(e->h_elites);
     if (e->ev_vc) (void)hipEventDestroy(e->ev_vc);
     if (e->ev_out) (void)hipEventDestroy(e->ev_out);
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -680,6 +682,51 @@ mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos
     for (size_t v = 0; traj && v < V; ++v)
         planes_to_rows(e, e->h_plan + v * C * H, H, H, [](size_t t) { return t; },
                        traj + v * H * mppi_traj_channels(&e->cfg));
+    return MPPI_OK;
+}
+
+// The elites: the selection, sort and gather kernels (mppi_elites.hip) on the engine's stream, ordered
+// like the plan's launch above (use_device joins a native batch first), then ONE copy of the output
+// block -- idx, S, w and, when asked for, the rows, contiguous for this n -- into pinned memory, one
+// synchronise, and the hand-out.  The buffers are sized for MPPI_MAX_ELITES at the first call.
+mppi_status mppi_get_elites(mppi_engine* e, int32_t n, int32_t* idx, float* S, float* w, float* traj) {
+    if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
+    if (n < 1 || n > MPPI_MAX_ELITES || n > e->K)
+        return fail(MPPI_ERR_INVALID_ARG, "n = %d elites: 1 .. min(MPPI_MAX_ELITES = %d, K = %d)", n, MPPI_MAX_ELITES, e->K);
+    if (traj && !e->d_traj) return fail(MPPI_ERR_STATE, "engine created without store_trajectory");
+    if (use_device(e)) return MPPI_ERR_HIP;
+    const size_t V = (size_t)e->V, H = (size_t)e->H, Cr = (size_t)mppi_traj_channels(&e->cfg);
+    const size_t row = H * Cr;   // floats of one rollout
+    if (!e->h_elites) {
+        const size_t cap = V * MPPI_MAX_ELITES * (3 + (e->d_traj ? row : 0));
+        int B;
+        int64_t share;
+        elite_split(e->K, &B, &share);
+        if (!e->d_elite_cand) HIP_TRY(hipMalloc(&e->d_elite_cand, sizeof(unsigned long long) * V * (size_t)B * MPPI_MAX_ELITES));
+        if (!e->d_elites) HIP_TRY(hipMalloc(&e->d_elites, sizeof(float) * cap));
+        HIP_TRY(hipHostMalloc((void**)&e->h_elites, sizeof(float) * cap, hipHostMallocDefault));
+    }
+    const size_t vn = V * (size_t)n;
+    const bool has_ee = e->cfg.model == MPPI_MODEL_ARM || e->cfg.model == MPPI_MODEL_WHOLEBODY;
+    EliteParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.S = e->d_S; p.stats = e->fp.stats; p.planes = traj ? e->d_traj : nullptr; p.cand = e->d_elite_cand;
+    p.idx = (int32_t*)e->d_elites; p.So = e->d_elites + vn; p.w = e->d_elites + 2 * vn;
+    p.rows = traj ? e->d_elites + 3 * vn : nullptr;
+    p.V = e->V; p.K = e->K; p.H = e->H; p.n = n;
+    p.C = e->C; p.nstate = has_ee ? e->A : e->C; p.has_ee = has_ee; p.Cr = (int32_t)Cr;
+    p.pitch = traj_pitch(e); p.t_major = e->cfg.model == MPPI_MODEL_QUADROTOR;
+    p.coef = e->dp.coef;
+    const int rc = mppi_launch_elites(&p, e->stream);
+    if (rc != 0) return fail(MPPI_ERR_HIP, "elites launch failed (%d: %s)", rc,
+                             rc > 0 ? hipGetErrorString((hipError_t)rc) : "no kernel for these shapes");
+    const size_t n_all = 3 * vn + (traj ? vn * row : 0);
+    HIP_TRY(hipMemcpyAsync(e->h_elites, e->d_elites, n_all * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (idx) std::memcpy(idx, e->h_elites, vn * sizeof(int32_t));
+    if (S) std::memcpy(S, e->h_elites + vn, vn * sizeof(float));
+    if (w) std::memcpy(w, e->h_elites + 2 * vn, vn * sizeof(float));
+    if (traj) std::memcpy(traj, e->h_elites + 3 * vn, vn * row * sizeof(float));
     return MPPI_OK;
 }
 

@@ -95,6 +95,12 @@ struct mppi_engine : mppi_host::EngineLayout {
     mppi::VehicleConst* d_plan_vc = nullptr;
     float* d_plan = nullptr;
     float* h_plan = nullptr;
+    // mppi_get_elites' buffers (allocated at its first call, for MPPI_MAX_ELITES): stage A's candidate
+    // keys (V,B,64); the output block idx, S, w (V,n each) and rows (V,n,H,Cr; with store_trajectory),
+    // contiguous for the n of the call, and its pinned host copy
+    unsigned long long* d_elite_cand = nullptr;
+    float* d_elites = nullptr;
+    float* h_elites = nullptr;
     ncclComm_t comm = nullptr;          // engine-owned RCCL communicator (mppi_comm_init)
     float* d_xown = nullptr;            // its exchange buffer (shard_count * V * P floats)
     bool peer = false;                  // peer exchange connected (mppi_peer_connect): no PACK, no collective

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "mppi_elites.h"
 #include "mppi_engine.h"
 
 using namespace mppi;
@@ -760,6 +761,54 @@ int32_t mppi_debug_plan_kernel(const int32_t* g, char* sym, int32_t len) {
     {   const mppi_aql::Capture c(&d);
         if (mppi_launch_plan(&p, &pp, nullptr) != 0) return MPPI_ERR_INVALID_ARG; }
     snprintf(sym, (size_t)len, "%s grid %u block %u", d.symbol, d.grid[0], d.block[0]);
+    return MPPI_OK;
+}
+
+// Likewise the elite readback's launches (mppi_elites.hip; mppi_get_elites) -- g = {model, K, H, V, n}:
+// "<symbol> grid <x>x<y> block <threads>" per launch, joined by "; ", the selection over the shares
+// (when K takes more than one block) first.  tests/test_capi_elites_cpu.py.
+int32_t mppi_debug_elite_kernel(const int32_t* g, char* sym, int32_t len) {
+    if (!g || !sym || len <= 0) return MPPI_ERR_INVALID_ARG;
+    EliteParams p;
+    std::memset(&p, 0, sizeof(p));
+    const int model = g[0];
+    const bool has_ee = model == MPPI_MODEL_ARM || model == MPPI_MODEL_WHOLEBODY;
+    p.K = g[1]; p.H = g[2]; p.V = g[3]; p.n = g[4];
+    p.nstate = model == MPPI_MODEL_DRONE ? 3 : model == MPPI_MODEL_QUADROTOR ? 6 : model == MPPI_MODEL_ARM ? 7 : 10;
+    p.has_ee = has_ee; p.C = p.nstate + (has_ee ? 12 : 0); p.Cr = p.nstate + (has_ee ? 16 : 0);
+    p.t_major = model == MPPI_MODEL_QUADROTOR;
+    p.pitch = ((p.t_major ? p.K : p.H) + 15) & ~15;
+    static const float nowhere = 0.0f;   // the launches are described, not run: any non-null planes and rows
+    p.planes = &nowhere; p.rows = const_cast<float*>(&nowhere);
+    std::string all;
+    for (int stage = 0; stage < 3; ++stage) {
+        LaunchDesc d{};
+        int rc;
+        {   const mppi_aql::Capture c(&d);
+            rc = mppi_launch_elites_stage(&p, stage, nullptr); }
+        if (rc == 1) continue;
+        if (rc != 0) return MPPI_ERR_INVALID_ARG;
+        char one[256];
+        snprintf(one, sizeof(one), "%s%s grid %ux%u block %u", all.empty() ? "" : "; ", d.symbol, d.grid[0], d.grid[1], d.block[0]);
+        all += one;
+    }
+    if ((int)all.size() >= len) return MPPI_ERR_INVALID_ARG;
+    snprintf(sym, (size_t)len, "%s", all.c_str());
+    return MPPI_OK;
+}
+
+// The host twin of the elites' order: the n first sample indices of S (K) under mppi_elites.h's key,
+// the one the kernels select and sort by.  tests/test_capi_elites_cpu.py.
+int32_t mppi_debug_elite_order(const float* S, int32_t K, int32_t n, int32_t* idx) {
+    if (!S || !idx || K < 1 || n < 1 || n > K) return MPPI_ERR_INVALID_ARG;
+    std::vector<unsigned long long> keys((size_t)K);
+    for (int32_t k = 0; k < K; ++k) {
+        uint32_t bits;
+        std::memcpy(&bits, S + k, sizeof(bits));
+        keys[(size_t)k] = elite_key(bits, (uint32_t)k);
+    }
+    std::partial_sort(keys.begin(), keys.begin() + n, keys.end());
+    for (int32_t j = 0; j < n; ++j) idx[j] = (int32_t)(uint32_t)keys[(size_t)j];
     return MPPI_OK;
 }
 

@@ -45,7 +45,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .engine import Engine, make_config
+from .engine import Elites, Engine, make_config
 
 HDR = 4   # partial record header: rho, eta, eta2, nan-flag
 
@@ -130,6 +130,31 @@ def combine_slots(slots: np.ndarray, lam: float, H: int, A: int) -> np.ndarray:
     eta = float((f * slots[:, 1]).sum())
     N = (f[:, None] * slots[:, HDR:HDR + A * H].astype(np.float64)).sum(0)
     return (N / eta).reshape(A, H).T
+
+
+def merge_elites(parts, n: int) -> Elites:
+    """The global best n of the ranks' elites (``Engine.get_elites``), whose ``idx`` have been made
+    global (``rank * K + idx``): ascending in (cost, global index) under the engine's order -- -0 as
+    +0, NaN after +inf, equal costs by the lower global index.  Pure (no collective, no engine)."""
+    idx = np.concatenate([p.idx for p in parts], axis=-1).astype(np.int64)
+    S = np.concatenate([p.S for p in parts], axis=-1)
+    w = np.concatenate([p.w for p in parts], axis=-1)
+    has_traj = all(p.traj is not None for p in parts)
+    traj = np.concatenate([p.traj for p in parts], axis=idx.ndim - 1) if has_traj else None
+    has_path = all(p.ee_path is not None for p in parts)
+    path = np.concatenate([p.ee_path for p in parts], axis=idx.ndim - 1) if has_path else None
+    if n < 1 or n > idx.shape[-1]:
+        raise ValueError(f"n = {n} elites out of {idx.shape[-1]} candidates")
+    by_idx = np.argsort(idx, axis=-1, kind="stable")
+    # NaN sorts last and -0 == +0 in numpy's order as in the engine's; the stable sort keeps the index order
+    order = np.take_along_axis(by_idx, np.argsort(np.take_along_axis(S, by_idx, -1) + np.float32(0.0), axis=-1,
+                                                  kind="stable"), -1)[..., :n]
+
+    def pick(a):
+        if a is None:
+            return None
+        return np.take_along_axis(a, order.reshape(order.shape + (1,) * (a.ndim - order.ndim)), order.ndim - 1)
+    return Elites(pick(idx), pick(S), pick(w), pick(traj), pick(path))
 
 
 def setup_peer_exchange(rank: int, world: int, group, device: int, engine: Engine) -> Optional[str]:
@@ -384,6 +409,19 @@ class ShardedEngine:
         """The nominal plan (``Engine.get_plan``): the warm start is the same on every rank, so each
         rank's engine returns the same plan; no collective."""
         return self.engine.get_plan()
+
+    def get_elites(self, n: int = 16, traj: bool = True) -> Elites:
+        """The n lowest-cost samples of the last step over ALL ranks' samples, ``idx`` global
+        (``rank * K + local``).  Sample-sharded modes: collective -- every rank's local elites are
+        all-gathered (objects) and merged (``merge_elites``); ``w`` needs no correction, rho and eta
+        being global after the exchange.  ``mode="vehicles"``: this rank's own vehicles, no collective."""
+        local = self.engine.get_elites(n, traj)
+        if self.mode == "vehicles" or self.world == 1:
+            return local
+        local.idx = local.idx.astype(np.int64) + self.rank * self.engine.K
+        parts = [None] * self.world
+        dist.all_gather_object(parts, local, group=self.group)
+        return merge_elites(parts, n)
 
     def __getattr__(self, name):
         if name == "engine":

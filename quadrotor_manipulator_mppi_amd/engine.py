@@ -52,6 +52,22 @@ class Plan:
         return Plan(self.traj[v], self.cost_t[v], self.pos_err[v], self.S[v], self.ee_path[v])
 
 
+@dataclass(slots=True)
+class Elites:
+    """The n lowest-cost sampled rollouts of the last step (``Engine.get_elites``), best first:
+    ascending in (cost, index) -- ``np.argsort(S[v], kind="stable")[:n]``.  Arrays are per vehicle,
+    ``(V, n, ...)``; ``vehicle(v)`` drops that axis."""
+    idx: np.ndarray                 # (V, n) int32: sample index within the engine's K
+    S: np.ndarray                   # (V, n): get_costs()[v, idx]
+    w: np.ndarray                   # (V, n): get_weights()[v, idx]
+    traj: Optional[np.ndarray]      # (V, n, H, C): get_trajectory()[v, idx]; None when not asked for
+    ee_path: Optional[np.ndarray]   # (V, n, H, 3): the EE (arm, whole-body) or vehicle positions
+
+    def vehicle(self, v: int = 0) -> "Elites":
+        return Elites(self.idx[v], self.S[v], self.w[v], None if self.traj is None else self.traj[v],
+                      None if self.ee_path is None else self.ee_path[v])
+
+
 def fill_joints(cfg: capi.Config, chain: Sequence[Dict]) -> None:
     if len(chain) > capi.MAX_JOINTS:
         raise ValueError(f"chain has {len(chain)} joints (max {capi.MAX_JOINTS})")
@@ -439,6 +455,26 @@ class Engine:
         else:
             ee_path = traj[..., :3].copy()
         return Plan(traj, cost_t, pos_err, S, ee_path)
+
+    def _ee_path(self, traj: np.ndarray) -> np.ndarray:
+        """(..., H, 3) positions out of (..., H, C) rows: the EE matrix's translation column (arm,
+        whole-body) or the vehicle's position."""
+        if self.cfg.model in (capi.MODEL_ARM, capi.MODEL_WHOLEBODY):
+            return traj[..., self.A:].reshape(*traj.shape[:-1], 4, 4)[..., :3, 3].copy()
+        return traj[..., :3].copy()
+
+    def get_elites(self, n: int = 16, traj: bool = True) -> Elites:
+        """The n lowest-cost samples of the last rollout of every vehicle with their costs, weights
+        and (``traj``; needs store_trajectory) rollouts (mppi_get_elites): selected, sorted and
+        gathered on the device, one copy, outside the control step."""
+        n = int(n)
+        idx = np.empty((self.V, max(n, 0)), np.int32)
+        S = np.empty(idx.shape, np.float32)
+        w = np.empty(idx.shape, np.float32)
+        rows = np.empty((self.V, max(n, 0), self.H, self.traj_channels), np.float32) if traj else None
+        capi.check(self._L.mppi_get_elites(self._h, n, idx.ctypes.data_as(C.POINTER(C.c_int32)), capi.fptr(S),
+                                           capi.fptr(w), capi.fptr(rows)), "get_elites")
+        return Elites(idx, S, w, rows, None if rows is None else self._ee_path(rows))
 
     # ---------------------------------------------------------------- timing
     def enable_timing(self, on: bool = True):

@@ -124,5 +124,10 @@ class MPPI(LazyU):
         vehicle 0: traj (H,6), cost_t (H), pos_err (H), S, ee_path (H,3), first_reach(tol))."""
         return self._engine.get_plan().vehicle(0)
 
+    def get_elites(self, n=16):
+        """The n lowest-cost sampled rollouts of the last step, best first (engine.Elites of vehicle 0:
+        idx (n), S (n), w (n), traj (n,H,C) in get_trajectory()'s layout, ee_path (n,H,3))."""
+        return self._engine.get_elites(n).vehicle(0)
+
     def get_costs(self) -> np.ndarray:
         return self._engine.get_costs()[0]

@@ -22,6 +22,9 @@ probes:
   noise_src [model] [K] [H] [n]  rollout with device Philox vs noise read from HBM (run under a kernel trace)
   geom [model] [K] [H] [bpvs] [threads]
                                  rollout / finalize / pair times per blocks-per-vehicle choice
+  elites [calls] [slow_calls] [shapes]
+                                 mppi_get_elites' wall time (n = 1, 16, 64; arm C3, whole-body, drone K=65536, the
+                                 fleet) against get_costs + get_weights + get_trajectory + argsort in the same process
   peer_soak [model] [K] [H] [G] [batches] [steps]
                                  G in-process peer-exchange ranks for batches x steps: no timeout, ranks
                                  bit-identical after every batch
@@ -734,7 +737,75 @@ def probe_noise_src(model="arm", K="4096", H="32", n="2000"):
         e.close()
 
 
-PROBES = {"timeline": probe_timeline, "noise_src": probe_noise_src, "peer_soak": probe_peer_soak, "geom": probe_geom, "batch": probe_batch, "fences": probe_fences, "calls": probe_calls,
+def probe_elites(calls="200", slow_calls="20", which="0,1,2,3"):
+    """Wall time of mppi_get_elites (the C-ABI call, outputs allocated once; 20 warm-ups) for n = 1,
+    16, 64 against, in the same process, the route without it to the same information:
+    get_costs + get_weights + get_trajectory + a host argsort and gather (2 warm-ups; left out at the
+    fleet, which has no stored trajectories).  Run once more under `rocprofv3 --kernel-trace --stats`
+    for the kernels' own times."""
+    from quadrotor_manipulator_mppi_amd import _capi as capi
+    calls, slow_calls = int(calls), int(slow_calls)
+    I32 = C.POINTER(C.c_int32)
+
+    def stats(us):
+        us = np.asarray(us)
+        return f"mean {us.mean():9.1f} us  median {np.median(us):9.1f}  p95 {np.percentile(us, 95):9.1f}"
+
+    shapes = [("arm C3 (K=4096 H=32 fp64)", "arm", 4096, 32, {}),
+              ("whole-body K=8192 H=64", "wholebody", 8192, 64, {}),
+              ("drone K=65536 H=32", "drone", 65536, 32, {}),
+              ("fleet V=64 K=8192 H=64, no planes", "wholebody", 8192, 64, dict(n_vehicles=64, store_trajectory=False))]
+    for name, model, K, H, kw in [shapes[int(i)] for i in which.split(",")]:   # (a kernel trace: one shape per run)
+        from quadrotor_manipulator_mppi_amd.engine import Engine, make_config
+        e = Engine(make_config(model, device=0, n_samples=K, n_horizon=H, state_f64=(model == "arm"), **kw))
+        V = e.V
+        for v in range(V):
+            e.set_target(*ARM_T, vehicle=v)
+        e.set_state(np.tile(np.array(STATES[model], np.float64), (V, 1)))
+        e.step()
+        e.synchronize()
+        with_traj = bool(e.cfg.store_trajectory)
+        medians = {}
+        for n in (1, 16, 64):
+            idx = np.empty((V, n), np.int32)
+            S, w = np.empty((V, n), np.float32), np.empty((V, n), np.float32)
+            rows = np.empty((V, n, H, e.traj_channels), np.float32) if with_traj else None
+            args = (e._h, n, idx.ctypes.data_as(I32), capi.fptr(S), capi.fptr(w), capi.fptr(rows))
+            us = []
+            for i in range(20 + calls):
+                t0 = time.perf_counter()
+                rc = e._L.mppi_get_elites(*args)
+                t1 = time.perf_counter()
+                capi.check(rc, "get_elites")
+                if i >= 20:
+                    us.append((t1 - t0) * 1e6)
+            copied = 12 * V * n + (rows.nbytes if rows is not None else 0)
+            medians[n] = float(np.median(us))
+            print(f"{name:36s} get_elites n={n:2d}{'' if with_traj else ' (traj=NULL)'}  {stats(us)}   ({copied} B copied)",
+                  flush=True)
+        if with_traj:
+            us = []
+            for i in range(2 + slow_calls):
+                t0 = time.perf_counter()
+                Sall, wall, tall = e.get_costs(), e.get_weights(), e.get_trajectory()
+                order = np.argsort(Sall, axis=1, kind="stable")[:, :16]
+                got = (order, np.take_along_axis(Sall, order, 1), np.take_along_axis(wall, order, 1),
+                       np.stack([tall[v, order[v]] for v in range(V)]))
+                t1 = time.perf_counter()
+                if i >= 2:
+                    us.append((t1 - t0) * 1e6)
+            el = e.get_elites(16)
+            same = (np.array_equal(el.idx, got[0]) and el.S.tobytes() == got[1].tobytes()
+                    and el.w.tobytes() == got[2].tobytes() and el.traj.tobytes() == got[3].tobytes())
+            m = float(np.median(us))
+            print(f"{name:36s} costs+weights+trajectory+argsort (n=16)  {stats(us)}   "
+                  f"({Sall.nbytes + wall.nbytes + tall.nbytes} B copied)", flush=True)
+            print(f"{name:36s} get_elites n=16 median / that route's median = {medians[16] / m:.4f} "
+                  f"(1/{m / medians[16]:.0f}); same result bit for bit: {same}", flush=True)
+        e.close()
+
+
+PROBES = {"elites": probe_elites, "timeline": probe_timeline, "noise_src": probe_noise_src, "peer_soak": probe_peer_soak, "geom": probe_geom, "batch": probe_batch, "fences": probe_fences, "calls": probe_calls,
           "sequence": probe_sequence, "stamps": probe_stamps, "latency": probe_latency,
           "ramp": probe_ramp, "peer_ranks": probe_peer_ranks, "rate": probe_rate, "rate_split": probe_rate_split, "rate_prewarm": probe_rate_prewarm,
           "store_floor": probe_store_floor}
