@@ -151,6 +151,11 @@ PROTOTYPES = {
                                   C.c_int32, C.c_int32, _F, _U32]),
 }
 
+# diagnostics entry points that are not in the header (csrc/mppi_debug.cpp); their users bind them
+DEBUG_PROTOTYPES = {
+    "mppi_debug_step_launches": (C.c_int32, [_CFG, _I32, C.c_char_p, C.c_int32]),
+}
+
 _lib = None
 _lock = threading.Lock()
 

@@ -11,6 +11,9 @@
 #pragma once
 #include <stdint.h>
 
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
 #include <mutex>
 #include <string>
 
@@ -79,6 +82,41 @@ int step_error(Step* s);
 // Until every dispatched pair has completed.  -1 on a queue error or after timeout_ms.
 int step_wait(Step* s, int timeout_ms, std::string* err);
 bool step_busy(Step* s);
+
+// Diagnostics (MPPI_AQL_PROFILE): the host phases of one call site, averaged over its passes and
+// printed to stderr every `period` of them as "<head> <name> <us>  <name> <us> ...".  A site holds
+// one (static) clock; with the variable unset each member costs one predictable branch.
+struct PhaseClock {
+    using clock = std::chrono::steady_clock;
+    const char* head;
+    const char* names[4];
+    int phases;
+    long period;
+    const bool on = getenv("MPPI_AQL_PROFILE") != nullptr;
+    double acc[4] = {0, 0, 0, 0};
+    long n = 0;
+    int next = 0;
+    clock::time_point t{};
+    void start() { if (on) { t = clock::now(); next = 0; } }
+    // the time since start or the last mark is the next phase's
+    void mark() { if (on) acc[next++] += lap(); }
+    // ... the next two phases': first_us of it the first's, the rest the second's
+    void mark_split(double first_us) { if (on) { acc[next++] += first_us; acc[next++] += lap() - first_us; } }
+    void done() {
+        if (!on || ++n % period != 0) return;
+        char line[256];
+        int k = snprintf(line, sizeof line, "%s", head);
+        for (int i = 0; i < phases; ++i)
+            k += snprintf(line + k, sizeof line - k, "%s%s %.2f", i ? "  " : " ", names[i], acc[i] / n);
+        fprintf(stderr, "%s\n", line);
+    }
+    double lap() {
+        const clock::time_point t1 = clock::now();
+        const double us = std::chrono::duration<double, std::micro>(t1 - t).count();
+        t = t1;
+        return us;
+    }
+};
 
 // Install (or, with nullptr, remove) the calling thread's capture target: the launchers then
 // describe their launch into it instead of launching (mppi_device.h go()).

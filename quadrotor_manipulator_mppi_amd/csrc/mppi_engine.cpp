@@ -75,22 +75,6 @@ mppi_status download(mppi_engine* e, void* dst, const void* src, size_t bytes) {
     return MPPI_OK;
 }
 
-// The FinParams of a FINAL into device scratch (the mapped buffer's layout; the SCRATCH tail) on
-// the throughput path (no completion flag): a pending read_outputs / get_weighted_noise still
-// returns the last real step.  On a shard the finalize combines the exchange slots as they stand
-// (no collective).  xerr stays at the mapped buffer.
-static FinParams scratch_final(const mppi_engine* e) {
-    FinParams f = e->fp;
-    f.mode = 0;
-    f.seq = 0u;
-    final_records(e, f);
-    bind_outputs(f, e->d_out, e);
-    f.wraw = nullptr;
-    f.wsmooth = nullptr;
-    f.tail = e->d_tail + kTailScratch;
-    return f;
-}
-
 // n steps out of SoA planes (channel stride `plane` floats; step i at offset at(i) of each) into
 // rows of mppi_traj_channels floats: the state channels, then (ARM, WHOLEBODY) the EE's twelve
 // stored entries with the row 0 0 0 1 appended
@@ -501,12 +485,11 @@ mppi_status mppi_kernel_timing_ex(mppi_engine* e, int32_t n, double* rollout_us,
     float* saved = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     mppi_status st = MPPI_OK;
-    DevParams p = e->dp;
-    p.vc0 = e->h_vc[0];
+    DevParams p = rollout_params(e, StepPath::Hip, nullptr, false);
     p.step_ctr = e->step_ctr;
     // the timing loop's outputs go to device scratch; u_prev is restored below (the trajectory
     // and S are overwritten)
-    FinParams f = scratch_final(e);
+    FinParams f = finalize_params(e, FinKind::Scratch);
     if (e->out_dbg == 2) f.tail = e->d_tail + kTailFinal;   // diagnostic: outputs into mapped host memory
     float ms0 = 0.0f, ms1 = 0.0f, ms2 = 0.0f;
     int rc = 0;
@@ -553,12 +536,11 @@ done:
 extern "C" int mppi_launch_boundary(float* scratch, int blocks, void* stream);
 extern "C" mppi_status mppi_probe_sequence(mppi_engine* e, int32_t n, int32_t mode, double* us) {
     if (use_device(e)) return MPPI_ERR_HIP;
-    DevParams p = e->dp;
-    p.vc0 = e->h_vc[0];
+    DevParams p = rollout_params(e, StepPath::Hip, nullptr, false);
     p.step_ctr = e->step_ctr;
     DevParams p1 = p;
     p1.nb = 1;
-    const FinParams f = scratch_final(e);
+    const FinParams f = finalize_params(e, FinKind::Scratch);
     const int fb = 8 * ((e->A + 7) / 8) * ((e->H + 7) / 8) * e->V;
     hipEvent_t a, b;
     (void)hipEventCreate(&a); (void)hipEventCreate(&b);
@@ -629,11 +611,7 @@ mppi_status mppi_get_weighted_noise(mppi_engine* e, float* raw, float* smoothed)
     // shard's all-reduced exchange slots): k_finalize in READBACK mode, which writes only these.
     // The step's own finalize stores no readback copies (no stores that only a readback needs on
     // the latency path, and none left dirty in an XCD's L2 across a native batch).
-    FinParams f = e->fp;
-    f.mode = 2;
-    f.seq = 0u;
-    final_records(e, f);
-    f.tail = e->d_tail + kTailReadback;
+    const FinParams f = finalize_params(e, FinKind::Readback);
     const int rc = mppi_launch_finalize(&f, e->stream);
     if (rc != 0) return fail(MPPI_ERR_HIP, "weighted-noise readback launch failed (%d)", rc);
     if (raw) HIP_TRY(hipMemcpyAsync(raw, e->d_wraw, n, hipMemcpyDeviceToHost, e->stream));   // (both under one synchronise)
@@ -752,10 +730,6 @@ mppi_status mppi_get_timing(mppi_engine* e, double* rms, double* fms, int64_t* r
     if (fn) *fn = e->fin_n;
     return MPPI_OK;
 }
-
-// Diagnostic (MPPI_STAMPS builds; not part of the public header): the raw per-wave stamps
-// of the last rollout launch, kStamps uint64 per wave.  Returns the wave count (0 when the
-// engine has no stamps) or a negative status.
 
 mppi_status mppi_philox_normals(uint64_t seed, uint32_t step, int32_t vehicle, int64_t k0, int32_t K, int32_t H,
                                 int32_t A, int32_t device, float* z, uint32_t* raw) {

@@ -9,7 +9,12 @@
 //                        (mppi_layout.h; no HIP, so it runs and is tested without a GPU)
 //   mppi_engine.cpp      create (allocate, bind, upload) / destroy, the finalize tails, state and
 //                        target uploads, readbacks, timing
+//   mppi_launches.cpp    the launch-parameter builders (rollout_params, finalize_params: every
+//                        launch's DevParams / FinParams and the quiet rule), launches described
+//                        instead of made, the native paths' description cache (DescCache)
 //   mppi_step.cpp        the control step: rollout, finalize, outputs, native (AQL) batches and calls
+//   mppi_debug.cpp       the diagnostics entry points (mppi_debug_*: described launches, stamps, the
+//                        native queue's probes), none of them on the step's path
 //   mppi_exchange.cpp    the sharded step's exchanges: the engine-owned RCCL communicator and the
 //                        peer exchange (regions, connect, probe, status, reset)
 //   mppi_prewarm.cpp     the opt-in prewarm thread (mppi_set_prewarm)
@@ -37,6 +42,32 @@
 // control call (its records, tagged with a bit-31 sequence number).
 enum class Pending { None, Hip, Batch, Call };
 
+// A native path's launch descriptions and the parameters they were made from.  The capture formats
+// both kernels' symbol names and packs ~2 KB of arguments (~0.4 us), so a batch or a control call
+// reuses them while its parameters match.  roll_quiet and fin_quiet are the launches of a batch's
+// steps before its last (the same descriptions as roll and fin where no quiet kernel applies); a
+// control call has none.
+struct DescCache {
+    bool valid = false;
+    int threads = 0;
+    mppi::DevParams p{};
+    mppi::FinParams f{};
+    mppi::LaunchDesc roll{}, fin{}, roll_quiet{}, fin_quiet{};
+    // ignore_vc0: the vehicle constants (the state) may differ -- a control call patches them in
+    bool matches(const mppi::DevParams& p, const mppi::FinParams& f, int threads, bool ignore_vc0) const;
+    // describes (p, f) and, where given, the quiet pair; the launchers' status (0: valid again)
+    int refresh(const mppi::DevParams& p, const mppi::FinParams& f, int threads,
+                const mppi::DevParams* p_quiet = nullptr, const mppi::FinParams* f_quiet = nullptr);
+};
+// The rollout's last argument is its DevParams by value: where the vehicle constants, and the
+// sequence word in them (VehicleConst::_pad[0], kSeqFromVc), lie in a description's argument block.
+inline uint32_t roll_vc0_off(const mppi::LaunchDesc& roll) {
+    return roll.arg_bytes - (uint32_t)sizeof(mppi::DevParams) + (uint32_t)offsetof(mppi::DevParams, vc0);
+}
+inline uint32_t roll_seq_off(const mppi::LaunchDesc& roll) {
+    return roll_vc0_off(roll) + (uint32_t)offsetof(mppi::VehicleConst, _pad);
+}
+
 // The layout (cfg, the sizes, dp, fp, ...: mppi_layout.h) and the device state built on it.
 struct mppi_engine : mppi_host::EngineLayout {
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -47,21 +78,9 @@ struct mppi_engine : mppi_host::EngineLayout {
     float* d_noise_in = nullptr;
     uint32_t step_ctr = 0;              // Philox counter word; +1 per finalized step
     uint32_t out_seq = 0;               // completion-flag value of the step read_outputs waits for
-    // a native control call's launch descriptions, reused while only the state changes
-    bool call_cached = false;
-    int call_threads = 0;
-    mppi::DevParams call_p{};
-    mppi::FinParams call_f{};
-    mppi::LaunchDesc call_roll{}, call_fin{};
-    // a native batch's launch descriptions, reused while the step's parameters are unchanged
-    bool batch_cached = false;
-    int batch_threads = 0;
-    mppi::DevParams batch_p{};
-    mppi::FinParams batch_f{};
-    mppi::LaunchDesc batch_roll{}, batch_fin{};
-    mppi::LaunchDesc batch_fin_quiet{}; // the quiet FINAL of the batch's steps before its last (the same
-                                        // description as batch_fin where no quiet kernel applies)
-    mppi::LaunchDesc batch_roll_quiet{};   // likewise the quiet rollout of those steps (or batch_roll's launch)
+    // the native paths' launch descriptions (DescCache): a batch's, reused while the step's parameters
+    // are unchanged, and a control call's, reused while only the state changes
+    DescCache batch, call;
     // the kernels the last batch and the last control call ran (mppi_kernel_info)
     std::string kern_batch = "none", kern_call = "none";
     int kern_batch_state = 0;           // kern_batch describes the resident native batch: 1 one step, 2 several
@@ -207,11 +226,56 @@ inline uint32_t sticky_timeout(const mppi_engine* e) {
 // this rank's exchange region past its control words (mppi_dev.h kXCtl): the partials' base
 inline unsigned long long* xdata(const mppi_engine* e) { return e->d_xregion + mppi::kXCtl; }
 
+// ------------------------------------------------------ launches (mppi_launches.cpp)
+// The launch-parameter builders: every launch of the step's kernels takes its parameters from these
+// two.  What a single launch owns -- the HIP launches' step counter and fresh sequence number, the
+// MPPI_DEBUG_OUT tails, a batch's kNoiseOverlap -- its call site sets on what they return.
+// Hip: the HIP launches'.  Batch, Call: a native batch's or control call's description -- the step
+// counter relative to the dispatch id (kNoiseStepFromId; set by step_prepare / step_call),
+// completion by the batch's signal or by the flags whose sequence number rides in the vehicle
+// constants (kSeqFromVc).
+enum class StepPath { Hip, Batch, Call };
+// FINAL: the step's finalize.  PACK: a shard's block records folded into its exchange slot.
+// SCRATCH: a FINAL into device scratch (the mapped buffer's layout; the SCRATCH tail) with no
+// completion flag, so a pending read_outputs / get_weighted_noise still returns the last real step
+// (on a shard it combines the exchange slots as they stand; xerr stays at the mapped buffer).
+// READBACK: w_eps and its SavGol of the records the last step combined.
+enum class FinKind { Final, Pack, Scratch, Readback };
+// quiet: a step of a batch before its last (never read) asks for the quiet kernels and gets the full
+// parameters back where none applies, so "no quiet kernel" shows as the same symbol.
+mppi::DevParams rollout_params(const mppi_engine* e, StepPath path, const float* d_noise, bool quiet);
+mppi::FinParams finalize_params(const mppi_engine* e, FinKind kind, StepPath path = StepPath::Hip, bool quiet = false);
+// The quiet rule, on the switches as values (the builders; the engine-less mppi_debug_*_kernels).
+// A batch's steps before its last may run the quiet FINAL (mppi_finalize.hip kRoleQuiet: u_prev and
+// nothing else; the outputs of a batch are those of its last step).  diag: an engine with stamps,
+// timing or output diagnostics or the overlap experiment; it and MPPI_GENERIC_KERNELS (generic & 3)
+// keep the full kernel on every step; so does the launcher where no quiet kernel applies (the
+// geometry, a peer exchange).
+inline int32_t quiet_fin_kern(int32_t kern, int generic, bool diag) {
+    return (generic & 3) || diag ? kern : kern | mppi::kFinKernQuiet;
+}
+// Those steps' rollouts likewise run the quiet rollout (mppi_rollout.h rollout_body QUIET: the
+// records and nothing else), so a batch's trajectory planes, costs and handed-over vehicle
+// constants are its last step's.  Not on a peer engine (the exchange's tag rides in the handed-over
+// step word every step) or a shard (its PACK and collective are left as they are); the launcher
+// keeps the full kernel where no quiet one applies (stored or injected noise, the extended kernels,
+// other geometries).
+inline int32_t quiet_roll_kern(int32_t kern, int generic, bool diag, bool peer, bool shard) {
+    return (generic & 11) || diag || peer || shard ? kern : kern | mppi::kRollKernQuiet;
+}
+// a launch described into d instead of made (mppi_device.h go(); the launchers' status)
+int describe(const mppi::DevParams& p, int threads, mppi::LaunchDesc* d);
+int describe(const mppi::FinParams& f, mppi::LaunchDesc* d);
 // -------------------------------------------------------------- step (mppi_step.cpp)
-// the rollout's per-block partial records (DevParams::hdr / rdata layout)
-void block_records(const mppi_engine* e, mppi::FinParams& f);
-// the finalize's record source: the rollout blocks' records, or the exchange slots of a shard
-void final_records(const mppi_engine* e, mppi::FinParams& f);
+// why this engine's steps cannot go native (nullptr: they can).  A batch may carry the stamps /
+// no-flag diagnostics natively (the timeline build measures the native step that way); a control
+// call waits on the flags, so it may not.
+const char* aql_ineligible(const mppi_engine* e, bool batch = false);
+
+// ------------------------------------------------------- diagnostics (mppi_debug.cpp)
+// the symbol a launch would run, by the launchers' own description of it ("?": none)
+std::string fin_symbol(const mppi::FinParams& f, mppi::LaunchDesc* desc = nullptr);
+std::string roll_symbol(const mppi::DevParams& p, int threads, mppi::LaunchDesc* desc = nullptr);
 
 // ------------------------------------------------------ exchange (mppi_exchange.cpp)
 // RCCL, resolved at the first mppi_comm_* call (dlopen: the library loads and its single-GPU

@@ -234,7 +234,7 @@ static mppi_status peer_bind(mppi_engine* e, std::vector<unsigned long long*> pt
     mppi_status st = upload_tails(e, 1u << kTailFinal | 1u << kTailReadback);
     if (st != MPPI_OK) return st;
     e->peer = true;
-    e->call_cached = false;
+    e->call.valid = false;
     return MPPI_OK;
 }
 
@@ -379,7 +379,7 @@ int32_t mppi_debug_peer_stall(mppi_engine* e, int32_t block, int32_t ms) {
         e->fp.xstall = e->d_xstall;
         mppi_status st = upload_tails(e, 1u << kTailFinal);
         if (st != MPPI_OK) return st;
-        e->call_cached = e->batch_cached = false;
+        e->call.valid = e->batch.valid = false;
     }
     const uint32_t w = ms ? ((uint32_t)ms << 16) | (uint32_t)block : 0u;
     HIP_TRY(hipMemcpy(e->d_xstall, &w, sizeof(w), hipMemcpyHostToDevice));

@@ -195,13 +195,18 @@ mppi_status layout_of(const mppi_config& cfg, EngineLayout& l) {
     for (int j = 0; j < c.savgol_window; ++j) f.sg[j] = l.sg_taps[c.savgol_window - 1 - j];
     f.coef = p.coef; f.dt = p.dt; f.dt2 = p.dt2; f.dt_d = c.dt;
     f.out_dim = l.out_dim;
-    l.generic = 0;
+    int generic = 0;
     if (const char* g = getenv("MPPI_GENERIC_KERNELS"))   // 1: all of them; one part by name (A/B of the parts)
-        l.generic = !strcmp(g, "finalize") ? 1 : !strcmp(g, "quiet") ? 2 : !strcmp(g, "rollout") ? 4
-                    : !strcmp(g, "quiet_rollout") ? 8 : atoi(g) != 0 ? kGenericAll : 0;
-    f.kern = (l.generic & 1) ? kFinKernGeneric : 0;
-    p.kern = (l.generic & 4) ? kRollKernGeneric : 0;   // (kRollKernQuiet: per launch, mppi_step.cpp)
+        generic = !strcmp(g, "finalize") ? 1 : !strcmp(g, "quiet") ? 2 : !strcmp(g, "rollout") ? 4
+                  : !strcmp(g, "quiet_rollout") ? 8 : atoi(g) != 0 ? kGenericAll : 0;
+    set_generic(l, generic);
     return MPPI_OK;
+}
+
+void set_generic(EngineLayout& l, int generic) {
+    l.generic = generic;
+    l.fp.kern = (generic & 1) ? kFinKernGeneric : 0;
+    l.dp.kern = (generic & 4) ? kRollKernGeneric : 0;   // (the quiet bits: per launch, mppi_launches.cpp)
 }
 
 }  // namespace mppi_host

@@ -58,6 +58,8 @@ struct EngineLayout {
 // Reads MPPI_FIN_TSZ, MPPI_NO_KINOVA_PATH and MPPI_GENERIC_KERNELS, the switches that change the
 // layout.  `c` has passed validate(); a configuration past a limit fails with its status and message.
 mppi_status layout_of(const mppi_config& c, EngineLayout& l);
+// the MPPI_GENERIC_KERNELS bits (EngineLayout::generic) and what they set in dp and fp
+void set_generic(EngineLayout& l, int generic);
 
 // mapped output buffer layout (h_out): outputs, u0, stats, then the tagged records of a read step
 // (k_finalize): per vehicle, 2 per dim -- (o1, u0, seq), (o2, nan flag, seq) -- and one
