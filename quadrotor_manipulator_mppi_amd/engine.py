@@ -450,11 +450,7 @@ class Engine:
         S = np.empty(self.V, np.float32)
         capi.check(self._L.mppi_get_plan(self._h, capi.fptr(traj), capi.fptr(cost_t), capi.fptr(pos_err),
                                          capi.fptr(S)), "get_plan")
-        if self.cfg.model in (capi.MODEL_ARM, capi.MODEL_WHOLEBODY):   # the EE matrix's translation column
-            ee_path = traj[..., self.A:].reshape(self.V, self.H, 4, 4)[..., :3, 3].copy()
-        else:
-            ee_path = traj[..., :3].copy()
-        return Plan(traj, cost_t, pos_err, S, ee_path)
+        return Plan(traj, cost_t, pos_err, S, self._ee_path(traj))
 
     def _ee_path(self, traj: np.ndarray) -> np.ndarray:
         """(..., H, 3) positions out of (..., H, C) rows: the EE matrix's translation column (arm,

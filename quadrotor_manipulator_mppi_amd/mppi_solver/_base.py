@@ -1,0 +1,225 @@
+"""What the drop-in solver classes share: the engine's lifecycle, the warm start, the target
+write, the lazy ``u``, the readbacks (``SolverBase``); the drone-shaped class body
+(``VehicleSolver``: ``set_state`` and a control call returning device tensors); and the device
+copy of those return values (``OutputRing``).
+
+The reference drone solver returns its (x, v) as torch tensors on its device
+(``drone_mppi.py:169-176``; the node calls ``xdes.to('cpu').tolist()``, ``drone.py:240``).
+The engine's outputs land in host memory, so each call needs one host-to-device copy.
+``OutputRing`` makes it ONE non-blocking copy of all the outputs into a fresh device
+tensor per call, from a ring of pinned staging rows: a row is reused only after its copy
+has run (its event; by then a whole control step has passed, so the wait is a no-op).
+Two synchronous ``torch.tensor(..., device=cuda)`` copies per call used to sit on the
+control step's latency path.
+"""
+from __future__ import annotations
+
+import threading
+from typing import Optional
+
+import numpy as np
+import torch
+
+from ..engine import Engine, make_config
+
+
+class OutputRing:
+    def __init__(self, device: torch.device, width: int, depth: int = 8):
+        self.device, self.width = device, width
+        self._host = None
+        self._events = None
+        self._used = [False] * depth
+        self._depth = depth
+        self._i = 0
+
+    def to_device(self, row: np.ndarray) -> torch.Tensor:
+        """A fresh float32 tensor on ``device`` holding ``row`` (stream-ordered on the
+        current stream; CPU devices get a host tensor)."""
+        if self.device.type != "cuda":
+            return torch.tensor(np.asarray(row, np.float32))
+        if self._host is None:
+            self._host = torch.zeros((self._depth, self.width), dtype=torch.float32).pin_memory()
+            self._events = [torch.cuda.Event() for _ in range(self._depth)]
+        i = self._i
+        self._i = (i + 1) % self._depth
+        if self._used[i]:
+            self._events[i].synchronize()
+        self._host[i].numpy()[:] = row
+        t = torch.empty(self.width, dtype=torch.float32, device=self.device)
+        t.copy_(self._host[i], non_blocking=True)
+        self._events[i].record()
+        self._used[i] = True
+        return t
+
+
+class SolverBase:
+    """A class gives: ``_horizon_attr`` (the name of its horizon attribute), ``_config(key)`` (the
+    engine's config for a reuse key) and, in its control call, the reuse key itself: the engine is
+    rebuilt when the key differs from the one it was made for."""
+
+    _horizon_attr = "n_horizon"
+
+    def __init__(self, n_action: int, horizon: int, device: Optional[int], noise: str, seed: int,
+                 verbose: bool, prewarm_us: int):
+        self.device = torch.device(f"cuda:{device or 0}" if torch.cuda.is_available() else "cpu")
+        self._dev_index = device or 0
+        self.n_action = n_action
+        self.dt = 0.01
+        self.u = torch.zeros(n_action)
+        self.verbose = verbose
+        self._noise, self._seed = noise, seed
+        self._prewarm_us = int(prewarm_us)
+        self._lock = threading.Lock()
+        self._engine: Optional[Engine] = None
+        self._engine_key = None                # the reuse key _engine was made for
+        self._u_prev_host = np.zeros((horizon, n_action), np.float32)
+        self._last_target = None               # (engine, target bytes) last written (_sync_target)
+
+    # ------------------------------------------------------------------ u
+    # The reference's ``u`` attribute (``self.u = u[0].clone()``, mppi.py:155 /
+    # drone_mppi.py:163): a torch tensor, built on its first read after each call from the
+    # call's own u0 row, so a controller that never reads it does not pay a
+    # ``torch.from_numpy`` (~1 us) per control call.  Assigning ``u`` stores the tensor.
+    _u_t = None
+    _u_np = None
+
+    @property
+    def u(self):
+        t = self._u_t
+        if t is None:
+            t = self._u_t = torch.from_numpy(self._u_np)
+        return t
+
+    @u.setter
+    def u(self, value):
+        self._u_t = value
+        self._u_np = None
+
+    def _set_u0(self, row: np.ndarray) -> None:
+        """row: this call's u0 (a fresh array the engine returned, owned from here on)."""
+        self._u_np = row
+        self._u_t = None
+
+    def _after_step(self, u0, stats):
+        """What a control call keeps of eng.step's answer: u0 (as _set_u0) and the stats."""
+        self._u_np = u0[0]
+        self._u_t = None
+        st = self.last_stats = stats[0]
+        return st
+
+    # -------------------------------------------------------------- engine
+    def _ensure_engine(self, key) -> Engine:
+        """The engine made for ``key``: the one at hand, or a new one that takes over the warm
+        start (and the prewarm window, mppi_set_prewarm: for a loop ticking with idle gaps)."""
+        e = self._engine
+        if e is not None and key == self._engine_key:
+            return e
+        u = self._u_prev_host if e is None else e.get_u_prev()[0]
+        if e is not None:
+            e.close()
+        cfg = self._config(key)
+        e = self._engine = Engine(cfg)
+        self._engine_key = key
+        e.set_u_prev(u)
+        if self._prewarm_us:
+            e.set_prewarm(self._prewarm_us)
+        return e
+
+    @property
+    def u_prev(self) -> torch.Tensor:
+        if self._engine is None:
+            return torch.from_numpy(self._u_prev_host.copy())
+        return torch.from_numpy(self._engine.get_u_prev()[0])
+
+    @u_prev.setter
+    def u_prev(self, value):
+        u = np.ascontiguousarray(torch.as_tensor(value).detach().cpu().numpy(), np.float32)
+        self._u_prev_host = u.reshape(getattr(self, self._horizon_attr), self.n_action).copy()
+        if self._engine is not None:
+            self._engine.set_u_prev(self._u_prev_host)
+
+    def _sync_target(self, eng: Engine, pos: np.ndarray, quat: Optional[np.ndarray] = None) -> None:
+        """The target into the engine when its bytes changed since the last call (the control
+        call's host time: a target write rebuilds the vehicle constants through one more C call)."""
+        key = pos.tobytes() if quat is None else pos.tobytes() + quat.tobytes()
+        last = self._last_target
+        if last is None or last[0] is not eng or last[1] != key:
+            eng.set_target(pos, quat)
+            self._last_target = (eng, key)
+
+    def compute_weights(self, S: torch.Tensor, _lambda) -> torch.Tensor:
+        """mppi.py:173-193 / drone_mppi.py:111-130 (host helper; the engine computes the same
+        weights on device)."""
+        rho = S.min()
+        scaled_S = (-1.0 / _lambda) * (S - rho)
+        return torch.exp(scaled_S) / torch.exp(scaled_S).sum()
+
+    # ------------------------------------------------------- build extras
+    def get_trajectory(self) -> np.ndarray:
+        """(K,H,C) of the last step: the arm's q_samples (7) and EE 4x4 (16); the drone's xyz; the
+        quadrotor's xyz, rpy (the commented loop's trajectory)."""
+        return self._engine.get_trajectory()[0]
+
+    def get_plan(self):
+        """The nominal plan: the zero-noise rollout of u_prev from the last state (engine.Plan of
+        vehicle 0: traj (H,C), cost_t (H), pos_err (H), S, ee_path (H,3), first_reach(tol))."""
+        return self._engine.get_plan().vehicle(0)
+
+    def get_elites(self, n=16):
+        """The n lowest-cost sampled rollouts of the last step, best first (engine.Elites of vehicle 0:
+        idx (n), S (n), w (n), traj (n,H,C) in get_trajectory()'s layout, ee_path (n,H,3))."""
+        return self._engine.get_elites(n).vehicle(0)
+
+    def get_costs(self) -> np.ndarray:
+        return self._engine.get_costs()[0]
+
+
+class VehicleSolver(SolverBase):
+    """The drone solver's body for a state (x, v) of ``width`` numbers each; the class's
+    ``_config(key)`` names its model (``_vehicle_config``)."""
+
+    _horizon_attr = "n_timestep"
+
+    def __init__(self, width: int, sigma: torch.Tensor, n_samples: int, n_timestep: int, *base_args):
+        super().__init__(sigma.shape[0], n_timestep, *base_args)
+        self.n_samples = n_samples
+        self.n_timestep = n_timestep
+        self.x_prev = torch.zeros(width)
+        self.v_prev = torch.zeros(width)
+        self.sigma = sigma
+        self.param_lambda = 0.1
+        self.target = [1.0, 2.0, 3.4]          # drone_mppi.py:141
+        self._width = width
+        self._row = np.zeros(2 * width, np.float64)        # x + v of the control call
+        self._out_ring = OutputRing(self.device, 2 * width)   # (x, v): one async H2D copy per call
+
+    def _vehicle_config(self, model: str, key, **extra):
+        return make_config(model, n_samples=self.n_samples, n_horizon=self.n_timestep, dt=self.dt,
+                           lam=self.param_lambda, sigma=self.sigma.numpy(), seed=self._seed,
+                           noise="injected" if key[0] else self._noise, device=self._dev_index,
+                           **extra)
+
+    def set_state(self, x, v):
+        """drone_mppi.py:179-183 (stored as float32 like the reference)."""
+        with self._lock:
+            self.x_prev = torch.tensor(np.asarray(x, np.float64), dtype=torch.float32)
+            self.v_prev = torch.tensor(np.asarray(v, np.float64), dtype=torch.float32)
+
+    def compute_control_input(self, noise: Optional[np.ndarray] = None):
+        row, w = self._row, self._width   # x, v into one preallocated fp64 row (the engine copies it)
+        with self._lock:
+            row[:w] = self.x_prev.numpy()
+            row[w:] = self.v_prev.numpy()
+        # the reuse key: unlike the arm's, it holds the sizes, so assigning n_samples or n_timestep
+        # after construction rebuilds the engine at the next call
+        eng = self._ensure_engine((noise is not None or self._noise == "injected", self.n_samples, self.n_timestep))
+        self._sync_target(eng, np.asarray(self.target, np.float32))
+        out, u0, stats = eng.step(row, noise)
+        st = self._after_step(u0, stats)   # (u: the tensor is made on first read)
+        if self.verbose:
+            print("Rho :", torch.tensor(st.rho))
+        t = self._out_ring.to_device(out[0])   # (the engine's row is x, v: mppi_output_dim)
+        return t[:w], t[w:]
+
+    def compute_weights(self, S: torch.Tensor) -> torch.Tensor:
+        return super().compute_weights(S, self.param_lambda)

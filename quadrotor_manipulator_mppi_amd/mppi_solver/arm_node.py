@@ -24,15 +24,8 @@ from typing import Optional
 import numpy as np
 
 from ..robot.dynamics import RobotDynamics
+from ..utils.pose import _quat_R
 from .mppi import MPPI
-
-
-def _quat_R(x, y, z, w):
-    n = np.sqrt(x * x + y * y + z * z + w * w)
-    x, y, z, w = x / n, y / n, z / n, w / n
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
 class ArmTorqueNode:

@@ -18,16 +18,15 @@ while the main loop reads them (kinova.py:106-116 vs :182).
 """
 from __future__ import annotations
 
-import threading
 from typing import Optional
 
 import numpy as np
 import torch
 
-from ..engine import Engine, host_fk, make_config
+from ..engine import host_fk, make_config
 from ..robot.urdf_chain import load_chain, parse_urdf_chain
 from ..utils.pose import Pose
-from ._outputs import LazyU
+from ._base import SolverBase
 
 
 def _is_f64(x) -> bool:
@@ -52,7 +51,7 @@ def _host_view(x, dtype) -> np.ndarray:
     return np.asarray(x, dtype=dtype)
 
 
-class MPPI(LazyU):
+class MPPI(SolverBase):
     def __init__(self, n_samples: int = 100, n_horizon: int = 32, device: Optional[int] = None,
                  noise: str = "philox", seed: int = 0x5EED, urdf_path: Optional[str] = None,
                  root_link: str = "base", end_link: str = "j2s7s300_link_7", verbose: bool = True,
@@ -63,72 +62,37 @@ class MPPI(LazyU):
         weights (defaults: cost_manager.py:21-43).  ``prewarm_us`` > 0: the engine's queue
         prewarm with that window (mppi_set_prewarm), for a node ticking with idle gaps such as
         kinova.py:101's rospy.Rate(100); results are unchanged."""
-        self.device = torch.device(f"cuda:{device or 0}" if torch.cuda.is_available() else "cpu")
-        self._dev_index = device or 0
+        super().__init__(7, n_horizon, device, noise, seed, verbose, prewarm_us)
         # mppi.py:37-42
-        self.n_action = 7
         self.n_manipulator_dof = 7
         self.n_mobile_dof = 0
         self.n_samples = n_samples
         self.n_horizon = n_horizon
-        self.dt = 0.01
         self._lambda = 0.1
-        self._noise, self._seed = noise, seed
         self._cost_terms, self._cost_weights = cost_terms, cost_weights
-        self._prewarm_us = int(prewarm_us)
-        self.verbose = verbose
         self.chain = parse_urdf_chain(urdf_path, root_link, end_link) if urdf_path else load_chain()
         # mppi.py:45-58
         self._q = np.zeros(7, np.float32)
         self._qdot = np.zeros(7, np.float32)
         self.base_pose = np.zeros(7, np.float32)
         self._f64 = False
-        self.u = torch.zeros(self.n_action)
         self.qdes = None
         self.vdes = None
         # mppi.py:70-72
         self.target_pose = Pose()
         self.target_pose.pose = torch.tensor([0.1029, 0.4055, 1.6498])
         self.target_pose.orientation = torch.tensor([-0.5, -0.5, 0.5, -0.5])
-        self._lock = threading.Lock()
-        self._engine: Optional[Engine] = None
-        self._u_prev_host = np.zeros((self.n_horizon, self.n_action), np.float32)
         self.cnt = 0
         self._row = np.zeros(21, np.float64)   # base xyzquat(7) + q(7) + qdot(7)
-        self._last_target = None               # (engine, target bytes) last written (_sync_target)
         self._target_views = None              # (pose tensor, quat tensor, their numpy views)
 
-    # -------------------------------------------------------------- engine
-    def _ensure_engine(self, f64: bool, noise: Optional[str] = None) -> Engine:
-        noise = noise or self._noise
-        e = self._engine
-        if e is not None and bool(e.cfg.state_f64) == f64 and (e.cfg.noise_mode == 1) == (noise == "injected"):
-            return e
-        u = self._u_prev_host if e is None else e.get_u_prev()[0]
-        if e is not None:
-            e.close()
-        cfg = make_config("arm", n_samples=self.n_samples, n_horizon=self.n_horizon, dt=self.dt,
-                          lam=self._lambda, chain=self.chain, noise=noise, seed=self._seed,
-                          device=self._dev_index, state_f64=f64, check_reach=True,
-                          cost_terms=self._cost_terms, cost_weights=self._cost_weights)
-        self._engine = Engine(cfg)
-        self._engine.set_u_prev(u)
-        if self._prewarm_us:
-            self._engine.set_prewarm(self._prewarm_us)
-        return self._engine
-
-    @property
-    def u_prev(self) -> torch.Tensor:
-        if self._engine is None:
-            return torch.from_numpy(self._u_prev_host.copy())
-        return torch.from_numpy(self._engine.get_u_prev()[0])
-
-    @u_prev.setter
-    def u_prev(self, value):
-        u = np.ascontiguousarray(torch.as_tensor(value).detach().cpu().numpy(), np.float32)
-        self._u_prev_host = u.reshape(self.n_horizon, self.n_action).copy()
-        if self._engine is not None:
-            self._engine.set_u_prev(self._u_prev_host)
+    def _config(self, key):
+        # key = (fp64 state, injected noise) and not the sizes: unlike the drone's, this class does
+        # not rebuild its engine when n_samples or n_horizon are assigned after construction
+        return make_config("arm", n_samples=self.n_samples, n_horizon=self.n_horizon, dt=self.dt,
+                           lam=self._lambda, chain=self.chain, noise="injected" if key[1] else self._noise,
+                           seed=self._seed, device=self._dev_index, state_f64=key[0], check_reach=True,
+                           cost_terms=self._cost_terms, cost_weights=self._cost_weights)
 
     # ------------------------------------------------------------ reference API
     def update_joint(self, q_full, v_full):
@@ -155,43 +119,28 @@ class MPPI(LazyU):
         row[14:21] = qd
         return row
 
-    def _sync_target(self, eng: Engine) -> None:
-        """The target into the engine when it changed since the last call (the control call's
-        host time: a target write rebuilds the vehicle constants through one more C call).
-        The tensors' numpy views are cached per tensor object and their bytes compared, so an
-        unchanged target costs ~1 us instead of two .numpy() calls and two array_equal."""
-        pt, qt = self.target_pose.pose, self.target_pose.orientation
-        views = self._target_views
-        if views is None or views[0] is not pt or views[1] is not qt:
-            views = self._target_views = (pt, qt, pt.numpy(), qt.numpy())
-        key = views[2].tobytes() + views[3].tobytes()
-        last = self._last_target
-        if last is None or last[0] is not eng or last[1] != key:
-            eng.set_target(views[2], views[3])
-            self._last_target = (eng, key)
-
     def compute_control_input(self, noise: Optional[np.ndarray] = None):
         """mppi.py:122-169.  ``noise`` (K,H,A) switches to injected-noise mode
         (parity with the reference's torch.randn draws)."""
         q, qd, base, f64 = self._snapshot()
-        eng = self._ensure_engine(f64, "injected" if noise is not None else None)
-        self._sync_target(eng)
+        eng = self._ensure_engine((f64, noise is not None or self._noise == "injected"))
+        # the target tensors' numpy views are cached per tensor object and their bytes compared
+        # (_sync_target), so an unchanged target costs ~1 us instead of two .numpy() calls and two
+        # array_equal
+        pt, qt = self.target_pose.pose, self.target_pose.orientation
+        views = self._target_views
+        if views is None or views[0] is not pt or views[1] is not qt:
+            views = self._target_views = (pt, qt, pt.numpy(), qt.numpy())
+        self._sync_target(eng, views[2], views[3])
         out, u0, stats = eng.step(self._state_row(q, qd, base), noise)
         dt = np.float64 if f64 else np.float32
         self.qdes = out[0, :7].astype(dt)
         self.vdes = out[0, 7:14].astype(dt)
-        self._set_u0(u0[0])   # the tensor is made on first read (LazyU)
-        self.last_stats = stats[0]
+        st = self._after_step(u0, stats)   # (u: the tensor is made on first read)
         self.cnt += 1
-        if stats[0].reach and self.verbose:   # mppi.py:165-167
+        if st.reach and self.verbose:   # mppi.py:165-167
             print("Reach !")
         return self.qdes.copy(), self.vdes.copy()
-
-    def compute_weights(self, S: torch.Tensor, _lambda) -> torch.Tensor:
-        """mppi.py:173-193 (host helper; the engine computes the same weights on device)."""
-        rho = S.min()
-        scaled_S = (-1.0 / _lambda) * (S - rho)
-        return torch.exp(scaled_S) / torch.exp(scaled_S).sum()
 
     def check_reach(self, q_full=None) -> bool:
         """mppi.py:95-120: host FK at qdes, L1 position error < 0.005."""
@@ -201,21 +150,3 @@ class MPPI(LazyU):
         T = host_fk(self.chain, self.qdes, base, f64)
         err = float(np.abs(T[:3, 3] - self.target_pose.pose.numpy()).sum())
         return err < 0.005
-
-    # ------------------------------------------------------- build extras
-    def get_trajectory(self) -> np.ndarray:
-        """(K,H,7+16): q_samples and the EE 4x4 per (k,t) of the last step."""
-        return self._engine.get_trajectory()[0]
-
-    def get_plan(self):
-        """The nominal plan: the zero-noise rollout of u_prev from the last joint state (engine.Plan
-        of vehicle 0: traj (H,7+16), cost_t (H), pos_err (H), S, ee_path (H,3), first_reach(tol))."""
-        return self._engine.get_plan().vehicle(0)
-
-    def get_elites(self, n=16):
-        """The n lowest-cost sampled rollouts of the last step, best first (engine.Elites of vehicle 0:
-        idx (n), S (n), w (n), traj (n,H,C) in get_trajectory()'s layout, ee_path (n,H,3))."""
-        return self._engine.get_elites(n).vehicle(0)
-
-    def get_costs(self) -> np.ndarray:
-        return self._engine.get_costs()[0]

@@ -30,6 +30,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ..utils.pose import _quat_R
+
 N_POSITION = 14   # controller.cpp:306
 N_VELOCITY = 13   # controller.cpp:307
 N_EFFORT = 7      # controller.cpp:661, kinova.py:190
@@ -208,14 +210,6 @@ def plugin_drone_target(msg: Float64MultiArray) -> Tuple[float, float, float]:
 
 
 # ------------------------------------------------------------- node loops
-def _quat_R(x, y, z, w):
-    n = np.sqrt(x * x + y * y + z * z + w * w)
-    x, y, z, w = x / n, y / n, z / n, w / n
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-
-
 class DroneNode:
     """The drone node's MPPI loop on wire payloads (``drone.py``).
 
