@@ -159,7 +159,10 @@ typedef enum {
     MPPI_COST_CENTER = 2,
     MPPI_COST_JOINT_TRACK = 4,
     MPPI_COST_ACTION = 8,
-    MPPI_COST_JOINT_LIMIT = 16
+    MPPI_COST_JOINT_LIMIT = 16,
+    /* Not a CostManager term: the pose target moves along the horizon (mppi_set_target_trajectory).
+     * Accepted on every model; bits 1..16 stay ARM / WHOLEBODY only. */
+    MPPI_COST_TARGET_TRACK = 32
 } mppi_cost_term;
 
 /* Per-vehicle statistics of the last finalised step. */
@@ -202,6 +205,25 @@ mppi_status mppi_set_joint_trajectory(mppi_engine* e, int32_t vehicle, const flo
 
 /* Goal per vehicle: position (3) and orientation quaternion xyzw (4; ignored by DRONE). */
 mppi_status mppi_set_target(mppi_engine* e, int32_t vehicle, const float* pos3, const float* quat_xyzw4);
+
+/* Target trajectory of one vehicle, for an engine created with MPPI_COST_TARGET_TRACK in
+ * cfg.cost_terms (else MPPI_ERR_STATE; vehicle out of range: MPPI_ERR_INVALID_ARG).  H rows: row t
+ * is the pose wanted at horizon index t, the state after t + 1 integration steps, (t + 1) dt from
+ * now -- a position (pos_h3, (H,3)) and an orientation quaternion xyzw (quat_h4, (H,4); ignored by
+ * DRONE and QUADROTOR; rows need not be unit, mppi_target_rotation divides by |q|^2).
+ *   ARM, WHOLEBODY   S_k = sum_{t<H-1} [w_sp |p_kt - p*_t| + w_so |eulerZYX(R_kt^-1 R*_t)|]
+ *                          + w_tp |p_k,H-1 - p*_H-1| + w_to |eulerZYX(R_k,H-1^-1 R*_H-1)|
+ *                          + the enabled extra terms (pose_cost.py:24-63 with the row for its constant)
+ *   DRONE, QUADROTOR S_k = 100 sum_{t<H-1} |p_t - p*_t|^2 + 20 |p_H-1 - p*_H-1|^2 (drone_mppi.py:87-107)
+ * quat_h4 NULL: every orientation row is the vehicle's fixed target orientation.  pos_h3 NULL
+ * clears the table: every row is the vehicle's fixed target (mppi_set_target) again, which is also
+ * the state of an engine never given a table; mppi_set_target refills the rows of a clear vehicle.
+ * The arm's check_reach measures against row 0 (qdes is the state one step ahead); mppi_get_plan
+ * measures cost_t[t] and pos_err[t] against row t.  A batch (mppi_run_steps(n)) uses one table for
+ * all n steps: the table changes only through this call, between steps, like the state.  The rows
+ * are copied into the engine's staging memory (the caller's arrays are free on return) and uploaded
+ * on the engine's stream, ordered before the next step on either dispatch path. */
+mppi_status mppi_set_target_trajectory(mppi_engine* e, int32_t vehicle, const float* pos_h3, const float* quat_h4);
 
 /* Warm start (V,H,A) -- reference attribute u_prev (mppi.py:58, drone_mppi.py:29). */
 mppi_status mppi_set_u_prev(mppi_engine* e, const float* u_prev);

@@ -21,6 +21,7 @@ NOISE_PHILOX, NOISE_INJECTED = 0, 1
 JOINT_FIXED, JOINT_REVOLUTE, JOINT_PRISMATIC, JOINT_FLOATING = 0, 1, 2, 3
 OK, ERR_INVALID_ARG, ERR_HIP, ERR_NONFINITE, ERR_STATE, ERR_COMM, ERR_PEER_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
 COST_COVAR, COST_CENTER, COST_JOINT_TRACK, COST_ACTION, COST_JOINT_LIMIT = 1, 2, 4, 8, 16
+COST_TARGET_TRACK = 32   # the pose target moves along the horizon (mppi_set_target_trajectory)
 ABI_VERSION = 10
 MAX_PEERS = 8
 MAX_ELITES = 64
@@ -91,6 +92,7 @@ PROTOTYPES = {
     "mppi_set_stream": (_ST, [_P, _P]),
     "mppi_set_joint_trajectory": (_ST, [_P, C.c_int32, _F]),
     "mppi_set_target": (_ST, [_P, C.c_int32, _F, _F]),
+    "mppi_set_target_trajectory": (_ST, [_P, C.c_int32, _F, _F]),
     "mppi_set_u_prev": (_ST, [_P, _F]),
     "mppi_get_u_prev": (_ST, [_P, _F]),
     "mppi_set_state": (_ST, [_P, _D]),

@@ -22,9 +22,9 @@ std::string fin_symbol(const FinParams& f, LaunchDesc* desc) {
     if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
-std::string roll_symbol(const DevParams& p, int threads, LaunchDesc* desc) {
+std::string roll_symbol(const DevParams& p, int threads, LaunchDesc* desc, const float* ttab) {
     LaunchDesc d{};
-    const int rc = describe(p, threads, &d);
+    const int rc = describe(p, threads, &d, ttab);
     if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
@@ -257,6 +257,7 @@ int32_t mppi_debug_step_launches(const mppi_config* cfg, const int32_t* sw, char
         e->fp.xdec = (unsigned long long*)stand_in(0x4000);
     }
     if (sharded(e)) e->d_exchange = (float*)stand_in(0x100000);
+    if (e->cfg.cost_terms & MPPI_COST_TARGET_TRACK) e->d_ttab = (float*)stand_in(0x6000);
     std::vector<VehicleConst> vc((size_t)e->V);
     e->h_vc = vc.data();
     e->tpos.assign((size_t)3 * e->V, 0.0f);
@@ -294,7 +295,7 @@ int32_t mppi_debug_step_launches(const mppi_config* cfg, const int32_t* sw, char
         const StepPath sp = path < 2 ? StepPath::Hip : path == 2 ? StepPath::Batch : StepPath::Call;
         DevParams p = rollout_params(e, sp, noise, !last);
         if (sp == StepPath::Hip) p.step_ctr = (uint32_t)i;   // (rollout_impl: the launch's own)
-        report(last, "rollout", describe(p, e->threads, &d), d);
+        report(last, "rollout", describe(p, e->threads, &d, e->d_ttab), d);
         if (sp == StepPath::Hip && sharded(e)) {
             const FinParams f = finalize_params(e, FinKind::Pack);
             report(last, "pack", describe(f, &d), d);

@@ -265,6 +265,8 @@ struct PlanParams {
     float* cost_t;           // (V,H) the step's share of S
     float* pos_err;          // (V,H) L1 distance of the EE / vehicle position to the target
     float* S;                // (V)
+    const float* ttab;       // (V,H,12) the target table of a tracking engine (row t: p*, R*), else null:
+                             //   cost_t, pos_err and S against the vehicle's fixed target
 };
 
 // Finalize / pack kernel parameters.
@@ -319,6 +321,13 @@ int mppi_launch_rollout_arm64_h32(const mppi::DevParams* p, int block_threads, v
 int mppi_launch_rollout_arm32(const mppi::DevParams* p, int block_threads, void* stream);
 int mppi_launch_rollout_wb(const mppi::DevParams* p, int block_threads, void* stream);
 int mppi_launch_rollout_quad(const mppi::DevParams* p, int block_threads, void* stream);
+// the tracking rollouts (cost_terms & MPPI_COST_TARGET_TRACK): ttab = the target table (V, H, 12)
+int mppi_launch_rollout_track(const mppi::DevParams* p, const float* ttab, int block_threads, void* stream);
+int mppi_launch_rollout_arm64_tt(const mppi::DevParams* p, const float* ttab, int block_threads, void* stream);
+int mppi_launch_rollout_arm64_h32_tt(const mppi::DevParams* p, const float* ttab, int block_threads, void* stream);
+int mppi_launch_rollout_arm32_tt(const mppi::DevParams* p, const float* ttab, int block_threads, void* stream);
+int mppi_launch_rollout_wb_tt(const mppi::DevParams* p, const float* ttab, int block_threads, void* stream);
+int mppi_launch_rollout_quad_tt(const mppi::DevParams* p, const float* ttab, int block_threads, void* stream);
 int mppi_launch_finalize(const mppi::FinParams* p, void* stream);
 int mppi_launch_plan(const mppi::DevParams* p, const mppi::PlanParams* pp, void* stream);
 int mppi_launch_peer_probe(unsigned long long* const* peers, unsigned long long* local, int n, int me,

@@ -187,6 +187,34 @@ void quad_outputs(const mppi_engine* e, const double* s, const float* u0, double
     out[11] = wz + dt * (p.q_iinv[2] * u0[3]);
 }
 
+mppi_status target_rows_begin(mppi_engine* e) {
+    if (e->tt_pending) {   // the previous copy out of the staging rows must be done
+        HIP_TRY(hipEventSynchronize(e->ev_tt));
+        e->tt_pending = false;
+    }
+    return MPPI_OK;
+}
+
+void target_rows_fixed(mppi_engine* e, int v) {
+    float row[12];
+    std::memcpy(row, &e->tpos[3 * v], 3 * sizeof(float));
+    quat_xyzw_to_R(&e->tquat[4 * v], row + 3);
+    for (int t = 0; t < e->H; ++t) std::memcpy(&e->h_ttab[((size_t)v * e->H + t) * 12], row, sizeof(row));
+}
+
+// (after use_device: no native batch in flight.  The copy is stream-ordered behind the HIP-launched
+// steps that still read the old rows; the next step -- a HIP launch on the stream, or a native
+// submission, which drains the stream first and whose first packet acquires at agent scope what the
+// stream wrote -- reads the new ones.)
+mppi_status upload_target_rows(mppi_engine* e, int v) {
+    const size_t n = (size_t)e->H * 12;
+    HIP_TRY(hipMemcpyAsync(e->d_ttab + (size_t)v * n, e->h_ttab + (size_t)v * n, n * sizeof(float), hipMemcpyHostToDevice,
+                           e->stream));
+    HIP_TRY(hipEventRecord(e->ev_tt, e->stream));
+    e->tt_pending = true;
+    return MPPI_OK;
+}
+
 mppi_status upload_consts(mppi_engine* e) {
     if (e->vc_pending) {   // the previous copy out of the staging buffer must be done
         HIP_TRY(hipEventSynchronize(e->ev_vc));
@@ -252,7 +280,12 @@ static mppi_status allocate(mppi_engine* e) {
     HIP_TRY(hipHostMalloc((void**)&e->h_out, e->out_bytes, hipHostMallocMapped | hipHostMallocCoherent));
     HIP_TRY(hipHostGetDevicePointer((void**)&e->h_out_dev, e->h_out, 0));
     HIP_TRY(hipMalloc(&e->d_sigma, sizeof(float) * kMaxA * kMaxA));
-    if (c.cost_terms) {   // Sigma^-1, gamma^t, tracking target
+    if (c.cost_terms & MPPI_COST_TARGET_TRACK) {   // the target table, its pinned staging copy and the uploads' event
+        HIP_TRY(hipMalloc(&e->d_ttab, sizeof(float) * (size_t)e->V * e->H * 12));
+        HIP_TRY(hipHostMalloc((void**)&e->h_ttab, sizeof(float) * (size_t)e->V * e->H * 12, hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&e->ev_tt, hipEventDisableTiming));
+    }
+    if (c.cost_terms & ~MPPI_COST_TARGET_TRACK) {   // Sigma^-1, gamma^t, tracking target
         HIP_TRY(hipMalloc(&e->d_sinv, sizeof(float) * e->A * e->A));
         HIP_TRY(hipMalloc(&e->d_gamma, sizeof(float) * e->H));
         HIP_TRY(hipMalloc(&e->d_jtraj, sizeof(float) * (size_t)e->V * e->H * std::max(1, e->nq)));
@@ -300,7 +333,13 @@ static mppi_status upload(mppi_engine* e) {
     const mppi_config& c = e->cfg;
     std::memset(e->h_out, 0, e->out_bytes);
     HIP_TRY(hipMemcpy(e->d_sigma, c.sigma, sizeof(float) * e->A * e->A, hipMemcpyHostToDevice));
-    if (c.cost_terms) {
+    if (e->d_ttab) {   // every vehicle's table clear: H copies of its fixed target
+        e->ttab_set.assign((size_t)e->V, 0);
+        for (int v = 0; v < e->V; ++v) target_rows_fixed(e, v);
+        HIP_TRY(hipMemcpy(e->d_ttab, e->h_ttab, sizeof(float) * (size_t)e->V * e->H * 12, hipMemcpyHostToDevice));
+        e->batch.ttab = e->call.ttab = e->d_ttab;
+    }
+    if (c.cost_terms & ~MPPI_COST_TARGET_TRACK) {
         HIP_TRY(hipMemcpy(e->d_sinv, e->sinv.data(), sizeof(float) * e->sinv.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(e->d_gamma, e->gamma_t.data(), sizeof(float) * e->gamma_t.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemset(e->d_jtraj, 0, sizeof(float) * (size_t)e->V * e->H * std::max(1, e->nq)));
@@ -389,12 +428,14 @@ void mppi_destroy(mppi_engine* e) {
     exchange_release(e);   // the communicator and the other ranks' mapped regions
     void* dev[] = {e->d_xregion, e->d_xpeers, e->d_sigma, e->d_joints, e->d_vc, e->d_u_prev, e->d_noise_in, e->d_traj, e->d_noise_out,
                    e->d_S, e->d_hdr, e->d_rdata, e->d_out, e->d_wraw, e->d_wsmooth, e->d_w,
-                   e->d_sinv, e->d_gamma, e->d_jtraj, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec,
+                   e->d_sinv, e->d_gamma, e->d_jtraj, e->d_ttab, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec,
                    e->d_plan_vc, e->d_plan, e->d_elite_cand, e->d_elites};
     for (void* p : dev) if (p) (void)hipFree(p);
     if (e->h_out) (void)hipHostFree(e->h_out);
     if (e->h_vc) (void)hipHostFree(e->h_vc);
     if (e->h_plan) (void)hipHostFree(e->h_plan);
+    if (e->h_ttab) (void)hipHostFree(e->h_ttab);
+    if (e->ev_tt) (void)hipEventDestroy(e->ev_tt);
     if (e->h_elites) (void)hipHostFree(e->h_elites);
     if (e->ev_vc) (void)hipEventDestroy(e->ev_vc);
     if (e->ev_out) (void)hipEventDestroy(e->ev_out);
@@ -412,7 +453,7 @@ mppi_status mppi_set_stream(mppi_engine* e, void* s) {
 
 mppi_status mppi_set_joint_trajectory(mppi_engine* e, int32_t v, const float* traj) {
     if (!e || v < 0 || v >= e->V) return fail(MPPI_ERR_INVALID_ARG, "mppi_set_joint_trajectory: bad arguments");
-    if (!e->d_jtraj) return fail(MPPI_ERR_STATE, "engine created without cost_terms");
+    if (!e->d_jtraj) return fail(MPPI_ERR_STATE, "engine created without CostManager cost_terms");
     if (use_device(e)) return MPPI_ERR_HIP;
     const size_t n = (size_t)e->H * e->nq;
     float* dst = e->d_jtraj + (size_t)v * n;
@@ -426,11 +467,37 @@ mppi_status mppi_set_target(mppi_engine* e, int32_t v, const float* pos, const f
     if (!e || !pos || v < 0 || v >= e->V) return fail(MPPI_ERR_INVALID_ARG, "mppi_set_target: bad arguments");
     std::memcpy(&e->tpos[3 * v], pos, 3 * sizeof(float));
     if (quat) std::memcpy(&e->tquat[4 * v], quat, 4 * sizeof(float));
+    if (e->d_ttab && !e->ttab_set[v]) {   // a tracking engine's clear table follows the fixed target
+        if (use_device(e)) return MPPI_ERR_HIP;
+        mppi_status st = target_rows_begin(e);
+        if (st != MPPI_OK) return st;
+        target_rows_fixed(e, v);
+        if ((st = upload_target_rows(e, v)) != MPPI_OK) return st;
+    }
     if (e->state_set) {
         if (use_device(e)) return MPPI_ERR_HIP;
         return upload_consts(e);
     }
     return MPPI_OK;
+}
+
+mppi_status mppi_set_target_trajectory(mppi_engine* e, int32_t v, const float* pos, const float* quat) {
+    if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
+    if (!e->d_ttab) return fail(MPPI_ERR_STATE, "engine created without MPPI_COST_TARGET_TRACK");
+    if (v < 0 || v >= e->V) return fail(MPPI_ERR_INVALID_ARG, "mppi_set_target_trajectory: vehicle %d of %d", v, e->V);
+    if (use_device(e)) return MPPI_ERR_HIP;
+    const mppi_status st = target_rows_begin(e);
+    if (st != MPPI_OK) return st;
+    target_rows_fixed(e, v);   // the clear state; the orientation rows of a NULL quat_h4
+    if (pos) {
+        float* rows = e->h_ttab + (size_t)v * e->H * 12;
+        for (int t = 0; t < e->H; ++t) {
+            std::memcpy(rows + 12 * t, pos + 3 * t, 3 * sizeof(float));
+            if (quat) quat_xyzw_to_R(quat + 4 * t, rows + 12 * t + 3);   // fp32, as the fixed target's tR
+        }
+    }
+    e->ttab_set[v] = pos != nullptr;
+    return upload_target_rows(e, v);
 }
 
 mppi_status mppi_set_u_prev(mppi_engine* e, const float* u) {
@@ -502,14 +569,14 @@ mppi_status mppi_kernel_timing_ex(mppi_engine* e, int32_t n, double* rollout_us,
     for (auto& x : ev) KT_TRY(hipEventCreate(&x));
     KT_TRY(hipMemcpyAsync(saved, e->d_u_prev, ub, hipMemcpyDeviceToDevice, e->stream));
     KT_TRY(hipEventRecord(ev[0], e->stream));
-    for (int i = 0; i < n && rc == 0; ++i) rc = mppi_launch_rollout(&p, e->threads, e->stream);
+    for (int i = 0; i < n && rc == 0; ++i) rc = launch_rollout(p, e->d_ttab, e->threads, e->stream);
     KT_TRY(hipEventRecord(ev[1], e->stream));
     for (int i = 0; i < n && rc == 0; ++i) rc = mppi_launch_finalize(&f, e->stream);
     KT_TRY(hipEventRecord(ev[2], e->stream));
     // the kernels as a control step runs them: rollout after finalize (u_prev and the
     // records just written, cold in the other XCDs' L2)
     for (int i = 0; i < n && rc == 0 && pair_us; ++i) {
-        rc = mppi_launch_rollout(&p, e->threads, e->stream);
+        rc = launch_rollout(p, e->d_ttab, e->threads, e->stream);
         if (rc == 0) rc = mppi_launch_finalize(&f, e->stream);
     }
     KT_TRY(hipEventRecord(ev[3], e->stream));
@@ -546,9 +613,9 @@ extern "C" mppi_status mppi_probe_sequence(mppi_engine* e, int32_t n, int32_t mo
     (void)hipEventCreate(&a); (void)hipEventCreate(&b);
     (void)hipEventRecord(a, e->stream);
     for (int i = 0; i < n; ++i) {
-        if (mode <= 2 || mode == 5) mppi_launch_rollout(&p, e->threads, e->stream);
+        if (mode <= 2 || mode == 5) launch_rollout(p, e->d_ttab, e->threads, e->stream);
         if (mode == 0 || mode == 3) mppi_launch_boundary((float*)e->d_out, fb, e->stream);
-        if (mode == 1 || mode == 4) mppi_launch_rollout(&p1, e->threads, e->stream);
+        if (mode == 1 || mode == 4) launch_rollout(p1, e->d_ttab, e->threads, e->stream);
         if (mode == 2) mppi_launch_finalize(&f, e->stream);
     }
     (void)hipEventRecord(b, e->stream);
@@ -641,6 +708,7 @@ mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos
     }
     PlanParams pp;
     pp.vc = e->d_plan_vc;
+    pp.ttab = e->d_ttab;
     pp.traj = e->d_plan; pp.cost_t = pp.traj + n_traj; pp.pos_err = pp.cost_t + n_vh; pp.S = pp.pos_err + n_vh;
     HIP_TRY(hipMemcpyAsync(e->d_plan_vc, e->h_vc, sizeof(VehicleConst) * V, hipMemcpyHostToDevice, e->stream));
     const int rc = mppi_launch_plan(&e->dp, &pp, e->stream);

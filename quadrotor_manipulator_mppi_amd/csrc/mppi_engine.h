@@ -53,6 +53,7 @@ struct DescCache {
     mppi::DevParams p{};
     mppi::FinParams f{};
     mppi::LaunchDesc roll{}, fin{}, roll_quiet{}, fin_quiet{};
+    const float* ttab = nullptr;   // a tracking engine's target table (its rollouts' extra argument; fixed per engine)
     // ignore_vc0: the vehicle constants (the state) may differ -- a control call patches them in
     bool matches(const mppi::DevParams& p, const mppi::FinParams& f, int threads, bool ignore_vc0) const;
     // describes (p, f) and, where given, the quiet pair; the launchers' status (0: valid again)
@@ -108,6 +109,15 @@ struct mppi_engine : mppi_host::EngineLayout {
     float* d_sinv = nullptr;      // extra cost terms: Sigma^-1 (A,A)
     float* d_gamma = nullptr;     //   gamma^t (H)
     float* d_jtraj = nullptr;     //   joint tracking target (V,H,nq)
+    // the target table of a tracking engine (cost_terms & MPPI_COST_TARGET_TRACK; else none): (V,H,12)
+    // rows p*(3), R*(9) on the device; its pinned host copy, the uploads' staging (what the device
+    // holds or is about to: check_reach reads row 0), ev_tt recorded behind the last upload; and per
+    // vehicle whether a table is set (clear: every row is the fixed target, mppi_set_target refills them)
+    float* d_ttab = nullptr;
+    float* h_ttab = nullptr;
+    hipEvent_t ev_tt = nullptr;
+    bool tt_pending = false;
+    std::vector<unsigned char> ttab_set;
     float* d_exchange = nullptr;
     // mppi_get_plan's buffers (allocated at its first call): the host's vehicle constants; the
     // planes (V,C,H), cost_t (V,H), pos_err (V,H) and S (V) in one block, and its pinned host copy
@@ -217,6 +227,14 @@ mppi_status use_device(mppi_engine* e);
 mppi_status build_vehicle_consts(mppi_engine* e);
 void quad_outputs(const mppi_engine* e, const double* s, const float* u0, double* out);
 mppi_status upload_consts(mppi_engine* e);
+// A tracking engine's table, as upload_consts moves the V > 1 vehicle constants: target_rows_begin
+// waits until the last copy out of the staging rows has run (they may then be rewritten),
+// target_rows_fixed sets vehicle v's staging rows to its fixed target, upload_target_rows copies them
+// to the device on the engine's stream (ordered before the next step on both dispatch paths: a HIP
+// launch follows it on the stream, a native submission drains the stream first).
+mppi_status target_rows_begin(mppi_engine* e);
+void target_rows_fixed(mppi_engine* e, int v);
+mppi_status upload_target_rows(mppi_engine* e, int v);
 hipEvent_t pool_event(mppi_engine* e);
 mppi_status drain_timing(mppi_engine* e);
 
@@ -264,7 +282,13 @@ inline int32_t quiet_roll_kern(int32_t kern, int generic, bool diag, bool peer, 
     return (generic & 11) || diag || peer || shard ? kern : kern | mppi::kRollKernQuiet;
 }
 // a launch described into d instead of made (mppi_device.h go(); the launchers' status)
-int describe(const mppi::DevParams& p, int threads, mppi::LaunchDesc* d);
+// The rollout's launch: the tracking kernels (cost_terms & MPPI_COST_TARGET_TRACK) take the engine's
+// target table as an extra argument; every other launch is mppi_launch_rollout's.
+inline int launch_rollout(const mppi::DevParams& p, const float* ttab, int threads, void* stream) {
+    return (p.cost_terms & MPPI_COST_TARGET_TRACK) ? mppi_launch_rollout_track(&p, ttab, threads, stream)
+                                                   : mppi_launch_rollout(&p, threads, stream);
+}
+int describe(const mppi::DevParams& p, int threads, mppi::LaunchDesc* d, const float* ttab = nullptr);
 int describe(const mppi::FinParams& f, mppi::LaunchDesc* d);
 // -------------------------------------------------------------- step (mppi_step.cpp)
 // why this engine's steps cannot go native (nullptr: they can).  A batch may carry the stamps /
@@ -275,7 +299,7 @@ const char* aql_ineligible(const mppi_engine* e, bool batch = false);
 // ------------------------------------------------------- diagnostics (mppi_debug.cpp)
 // the symbol a launch would run, by the launchers' own description of it ("?": none)
 std::string fin_symbol(const mppi::FinParams& f, mppi::LaunchDesc* desc = nullptr);
-std::string roll_symbol(const mppi::DevParams& p, int threads, mppi::LaunchDesc* desc = nullptr);
+std::string roll_symbol(const mppi::DevParams& p, int threads, mppi::LaunchDesc* desc = nullptr, const float* ttab = nullptr);
 
 // ------------------------------------------------------ exchange (mppi_exchange.cpp)
 // RCCL, resolved at the first mppi_comm_* call (dlopen: the library loads and its single-GPU

@@ -294,8 +294,8 @@ mppi_status validate(const mppi_config& c) {
     if (c.vehicle_offset < 0 || c.vehicle_offset + c.n_vehicles > 32768)
         return fail(MPPI_ERR_INVALID_ARG, "vehicle_offset %d: the fleet-wide vehicle index must stay below 32768",
                     c.vehicle_offset);
-    if (c.cost_terms & ~0x1F) return fail(MPPI_ERR_INVALID_ARG, "unknown cost_terms bits 0x%x", c.cost_terms);
-    if (c.cost_terms && (c.model == MPPI_MODEL_DRONE || c.model == MPPI_MODEL_QUADROTOR))
+    if (c.cost_terms & ~0x3F) return fail(MPPI_ERR_INVALID_ARG, "unknown cost_terms bits 0x%x", c.cost_terms);
+    if ((c.cost_terms & 0x1F) && (c.model == MPPI_MODEL_DRONE || c.model == MPPI_MODEL_QUADROTOR))
         return fail(MPPI_ERR_INVALID_ARG, "cost_terms apply to the ARM / WHOLEBODY CostManager (not DRONE)");
     if (c.block_threads && (c.block_threads % 64 || c.block_threads > 512))
         return fail(MPPI_ERR_INVALID_ARG, "block_threads must be a multiple of 64 <= 512");

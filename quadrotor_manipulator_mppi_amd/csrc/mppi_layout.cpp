@@ -151,7 +151,8 @@ mppi_status layout_of(const mppi_config& cfg, EngineLayout& l) {
         return fail(MPPI_ERR_INVALID_ARG, "bad SavGol window/order");
     l.sinv.clear();
     l.gamma_t.clear();
-    if (c.cost_terms && (st = cost_tables(l)) != MPPI_OK) return st;
+    // (the extra CostManager terms' tables; the tracking bit alone needs none)
+    if ((c.cost_terms & ~MPPI_COST_TARGET_TRACK) && (st = cost_tables(l)) != MPPI_OK) return st;
     chain(l);
 
     p.model = c.model; p.V = l.V; p.K = l.K; p.H = H; p.A = l.A;

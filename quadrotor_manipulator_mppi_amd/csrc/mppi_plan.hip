@@ -212,9 +212,19 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     // ---- FK, the step's cost and position error, the planes
     const bool term = (t == H - 1);
     float* const planes = pp.traj + (size_t)v * p.C * H;
+    // this step's target: row t of a tracking engine's table (PlanParams::ttab), else the fixed one
+    float tg[12];
+    if (pp.ttab) {
+        load_target_row<MODEL == MPPI_MODEL_DRONE>(pp.ttab + ((size_t)v * H + tc) * 12, tg);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tg[i] = vc.tpos[i];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) tg[3 + i] = vc.tR[i];
+    }
     float cost, perr;
     if (MODEL == MPPI_MODEL_DRONE) {
-        const float dx = posf[0] - vc.tpos[0], dy = posf[1] - vc.tpos[1], dz = posf[2] - vc.tpos[2];
+        const float dx = posf[0] - tg[0], dy = posf[1] - tg[1], dz = posf[2] - tg[2];
         cost = (term ? p.w_tp : p.w_sp) * (dx * dx + dy * dy + dz * dz);
         perr = fabsf(dx) + fabsf(dy) + fabsf(dz);
         if (val) {
@@ -224,15 +234,15 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     } else {
         Mat34 T;
         plan_fk<MODEL, NA, F64>(T, posf, posd, vc, jnt, p);
-        cost = pose_cost(T, vc, term ? p.w_tp : p.w_sp, term ? p.w_to : p.w_so);
-        perr = fabsf(T.m[3] - vc.tpos[0]) + fabsf(T.m[7] - vc.tpos[1]) + fabsf(T.m[11] - vc.tpos[2]);
+        cost = pose_cost_row(T, tg, term ? p.w_tp : p.w_sp, term ? p.w_to : p.w_so);
+        perr = fabsf(T.m[3] - tg[0]) + fabsf(T.m[7] - tg[1]) + fabsf(T.m[11] - tg[2]);
         if (val) {
 #pragma unroll
             for (int a = 0; a < NA; ++a) planes[(size_t)a * H + t] = posf[a];
 #pragma unroll
             for (int i = 0; i < 12; ++i) planes[(size_t)(NA + i) * H + t] = T.m[i];
         }
-        if (p.cost_terms) {   // the extra CostManager terms in the reference's order (cost_manager.py:83-87)
+        if (p.cost_terms & ~MPPI_COST_TARGET_TRACK) {   // the extra CostManager terms in the reference's order (cost_manager.py:83-87)
             const float g = p.gamma_t[tc];
             if (p.cost_terms & MPPI_COST_COVAR) cost += p.w_cov * covar_form<NA>(p, act);
             float sc = 0.0f, sj = 0.0f;
@@ -279,6 +289,7 @@ __global__ void __launch_bounds__(64) k_plan_quad(const float* __restrict__ u_pr
     const float dt = p.dt, im = p.q_inv_m, kd = p.q_kd;
     const float gj = (j >= 2) ? -p.q_g : 0.0f;      // g = (0, 0, -q_g)
     const float ij = p.q_iinv[jj], tg = vc.tpos[jj];
+    const float* const trow = pp.ttab ? pp.ttab + (size_t)v * H * 12 + jj : nullptr;   // a tracking engine's rows
     float pj = vc.pos0f[jj], ej = vc.pos0f[3 + jj], vj = vc.vel0f[jj], wj = vc.vel0f[3 + jj];
     const float ox0 = vc.vel0f[3], oy0 = vc.vel0f[4], oz0 = vc.vel0f[5];
     const float a0 = (j == 0) ? 1.0f : 0.0f;
@@ -293,7 +304,7 @@ __global__ void __launch_bounds__(64) k_plan_quad(const float* __restrict__ u_pr
             planes[(size_t)(3 + j) * H + t] = ej;
         }
         // squared and L1 position error over the three axes (drone_mppi.py:87-107)
-        const float dd = pj - tg, d2 = dd * dd, d1 = fabsf(dd);
+        const float dd = pj - (trow ? trow[(size_t)t * 12] : tg), d2 = dd * dd, d1 = fabsf(dd);
         const float x = qbc<0>(d2) + qbc<1>(d2) + qbc<2>(d2);
         const float e1 = qbc<0>(d1) + qbc<1>(d1) + qbc<2>(d1);
         const float c = ((t == H - 1) ? p.w_tp : p.w_sp) * x;

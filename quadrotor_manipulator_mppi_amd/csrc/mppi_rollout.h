@@ -396,6 +396,36 @@ __device__ __forceinline__ float pose_cost(const Mat34& T, const VehicleConst& v
     return wp * cp + wo * co;
 }
 
+// The same cost against a target row (p*, R* row-major) the lane holds in registers: the tracking
+// kernels (rollout_body TRK, k_plan).  pose_cost restated, not lifted: the fixed-target kernels'
+// code stays as it is.
+__device__ __forceinline__ float pose_cost_row(const Mat34& T, const float (&g)[12], float wp, float wo) {
+    const float dx = T.m[3] - g[0], dy = T.m[7] - g[1], dz = T.m[11] - g[2];
+    const float cp = __builtin_amdgcn_sqrtf(dx * dx + dy * dy + dz * dz);
+    const float r00 = T.m[0] * g[3] + T.m[4] * g[6] + T.m[8] * g[9];
+    const float r10 = T.m[1] * g[3] + T.m[5] * g[6] + T.m[9] * g[9];
+    const float r20 = T.m[2] * g[3] + T.m[6] * g[6] + T.m[10] * g[9];
+    const float r21 = T.m[2] * g[4] + T.m[6] * g[7] + T.m[10] * g[10];
+    const float r22 = T.m[2] * g[5] + T.m[6] * g[8] + T.m[10] * g[11];
+    const float yaw = atan2_fast(r10, r00);
+    const float pitch = asinf(fminf(fmaxf(-r20, -1.0f), 1.0f));
+    const float roll = atan2_fast(r21, r22);
+    const float co = __builtin_amdgcn_sqrtf(yaw * yaw + pitch * pitch + roll * roll);
+    return wp * cp + wo * co;
+}
+// A row of the target table (V, H, 12: p*(3) then R*(9), 48 B) as three 16 B loads; DRONE reads p* only.
+template <bool POS_ONLY>
+__device__ __forceinline__ void load_target_row(const float* row, float (&g)[12]) {
+    const float4* r4 = reinterpret_cast<const float4*>(row);
+    const float4 a = r4[0];
+    g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w;
+    if constexpr (!POS_ONLY) {
+        const float4 b = r4[1], c = r4[2];
+        g[4] = b.x; g[5] = b.y; g[6] = b.z; g[7] = b.w;
+        g[8] = c.x; g[9] = c.y; g[10] = c.z; g[11] = c.w;
+    }
+}
+
 }  // namespace
 
 // =============================================================================
@@ -690,14 +720,22 @@ constexpr int roll_occ() {
 // records), so the instantiation has none of those stores, nor the plane descriptor, the S staging
 // in LDS or block 0's hand-off.  Everything the records are made of is the same code in the same
 // order: the records are bit-identical to the full kernel's.
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG, bool B512, bool QUIET = false>
+// TRK (k_rollout_tt; MPPI_COST_TARGET_TRACK): the pose target moves along the horizon.  The lane's
+// step(s) t are fixed for the block's lifetime, so it fetches its row(s) of the target table
+// (V, H, 12), one per 64-lane chunk, once, with the prologue's other global loads, and the pose cost
+// (the drone branch: the position cost) takes p*_t and R*_t from those registers instead of the
+// vehicle constants.  An extended (XC) body: extra terms, a full Sigma and generic chains go with it.
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG, bool B512, bool QUIET = false,
+          bool TRK = false>
 __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint32_t seed_hi,
                                              const uint32_t step_arg, const uint32_t k_off,
                                              const int32_t noise_arg, const int32_t H_arg,
                                              const int32_t geo_arg,
                                              const float* __restrict__ u_prev,
-                                             const JointDev* __restrict__ jtab, const DevParams& pk) {
+                                             const JointDev* __restrict__ jtab, const DevParams& pk,
+                                             const float* __restrict__ ttab = nullptr) {
     static_assert(!B512 || ONEG, "the fixed-block body is a single-group one");
+    static_assert(!TRK || (XC && !QUIET), "the tracking body is an extended one, and has no quiet form");
     static_assert(!QUIET || (!XC && NCH == 1), "the quiet body exists for the common one-chunk kernels");
     constexpr bool kTraj = !QUIET && !(MPPI_KO & 16);      // trajectory planes
     constexpr bool kCosts = !QUIET && !(MPPI_KO & 1024);   // the cost vector S
@@ -760,6 +798,15 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     // in SGPRs spills): V == 1 from the kernel arguments, else from vc[v]
     constexpr int kVCW = (int)(sizeof(VehicleConst) / 4);
     const int vcr = (tid < kVCW) ? (VONE ? ((const int*)&pk.vc0)[tid] : ((const int*)(pk.vc + v))[tid]) : 0;
+    // the lane's target rows (t clamped to H - 1: the pad lanes read the last row, their cost is masked)
+    float tgt[TRK ? NCH : 1][12];
+    if constexpr (TRK) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int t = t0 + 64 * c, tc = (t < H_arg) ? t : H_arg - 1;
+            load_target_row<MODEL == MPPI_MODEL_DRONE>(ttab + ((size_t)v * H_arg + tc) * 12, tgt[c]);
+        }
+    }
     // touch every kernel-argument line the hot phases read (one s_load per 64 B): they
     // land in the scalar cache while the first group's Philox draw runs below
     // (an integer fold: uniform, so SALU -- a float sum took one VALU op per line)
@@ -928,8 +975,9 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         float ecov = 0.0f, eact = 0.0f, gts[NCH];
 #pragma unroll
         for (int c = 0; c < NCH; ++c) gts[c] = 0.0f;
-        if (XC && p.cost_terms) {   // (the XC kernel also runs a full Sigma without extra terms:
-                                    //  gamma_t / sinv exist only with cost_terms)
+        // (the tracking bit alone reads neither gamma_t nor sinv)
+        if (XC && (TRK ? (p.cost_terms & ~MPPI_COST_TARGET_TRACK) : p.cost_terms)) {   // (the XC kernel also runs a full Sigma
+                                    //  without extra terms: gamma_t / sinv exist only with cost_terms)
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 const int t = t0 + 64 * c;
@@ -1053,8 +1101,8 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             const uint32_t toff = ((uint32_t)k * (uint32_t)hp + (uint32_t)t) * 4u;   // byte offset in a plane
             const bool stv = kTraj && p.store_traj && kval && t < hp;   // row incl. its pad (finite values)
             if (MODEL == MPPI_MODEL_DRONE) {
-                const float dx = posf[c][0] - vc.tpos[0], dy = posf[c][1] - vc.tpos[1],
-                            dz = posf[c][2] - vc.tpos[2];
+                const float dx = posf[c][0] - (TRK ? tgt[c][0] : vc.tpos[0]), dy = posf[c][1] - (TRK ? tgt[c][1] : vc.tpos[1]),
+                            dz = posf[c][2] - (TRK ? tgt[c][2] : vc.tpos[2]);
                 x = dx * dx + dy * dy + dz * dz;
                 if (stv) {
 #pragma unroll
@@ -1130,7 +1178,8 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 const float wsp = uniform_f32(p.w_sp), wso = uniform_f32(p.w_so), wtp = uniform_f32(p.w_tp),
                             wto = uniform_f32(p.w_to);
                 SECTION("pose_cost");
-                x = (MPPI_KO & 8) ? T.m[3] + T.m[7] + T.m[11] + T.m[0] : pose_cost(T, vc, term ? wtp : wsp, term ? wto : wso);
+                if constexpr (TRK) x = pose_cost_row(T, tgt[c], term ? wtp : wsp, term ? wto : wso);
+                else x = (MPPI_KO & 8) ? T.m[3] + T.m[7] + T.m[11] + T.m[0] : pose_cost(T, vc, term ? wtp : wsp, term ? wto : wso);
                 SECTION("traj_ee_stores");
                 if (stv) {
 #pragma unroll
@@ -1408,6 +1457,22 @@ __global__ void __launch_bounds__(512, (F64 ? 7 : roll_occ<NCH, F64, XC, true>()
                                                                         H_arg, geo_arg, u_prev, jtab, pk);
 }
 
+// The tracking rollout (rollout_body TRK): the extended kernel of every block size, one group or a
+// loop of them, under a symbol of its own.  The target table is an extra pointer argument before the
+// trailing DevParams (whose size and offsets, and every other kernel's arguments, stay as they are);
+// the step counter stays the third argument.
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE>
+__global__ void __launch_bounds__(512, (roll_occ<NCH, F64, true, false>())) k_rollout_tt(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                 const uint32_t step_arg, const uint32_t k_off,
+                                                 const int32_t noise_arg, const int32_t H_arg,
+                                                 const int32_t geo_arg,
+                                                 const float* __restrict__ u_prev,
+                                                 const JointDev* __restrict__ jtab,
+                                                 const float* __restrict__ ttab, const DevParams pk) {
+    rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, true, false, false, false, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg,
+                                                                                   H_arg, geo_arg, u_prev, jtab, pk, ttab);
+}
+
 // =============================================================================
 // launchers
 // =============================================================================
@@ -1505,3 +1570,28 @@ inline int dispatch_geom(const DevParams& p, int threads, hipStream_t s) {
     return -1;
 }
 
+// The tracking launch (DevParams::cost_terms & MPPI_COST_TARGET_TRACK): k_rollout_tt on every step
+// of a batch (no quiet form), LDS as the full extended kernel's.
+template <int MODEL, int NA, int NCH, int LSEG, bool F64>
+inline int launch_rollout_tt(const DevParams& p, const float* ttab, int threads, hipStream_t s) {
+    const int iters = p.iters;
+    const int s_run = iters * cost_run_stride((threads / 64) * (64 / LSEG));
+    if (threads <= 0 || threads > 512 || iters < 1 || s_run > kMaxCostRun) return -1;
+    const size_t lds = (size_t)(((p.H * NA + 3) & ~3) + 8 * wave_slot_floats<NA, NCH, LSEG>() + s_run) * sizeof(float);
+    const int32_t geo = threads | (iters << 16);
+    return pick<true, false>(p.V == 1, [&](auto vone) {
+        const auto k = k_rollout_tt<MODEL, NA, NCH, LSEG, F64, vone()>;
+        static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+        return go(k, dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
+                  p.noise_mode, p.H, geo, p.u_prev, p.joints, ttab, p);
+    });
+}
+
+template <int MODEL, int NA, bool F64>
+inline int dispatch_geom_tt(const DevParams& p, const float* ttab, int threads, hipStream_t s) {
+    if (p.nch == 1 && p.L == 32) return launch_rollout_tt<MODEL, NA, 1, 32, F64>(p, ttab, threads, s);
+    if (p.nch == 1 && p.L == 64) return launch_rollout_tt<MODEL, NA, 1, 64, F64>(p, ttab, threads, s);
+    if (p.nch == 2) return launch_rollout_tt<MODEL, NA, 2, 64, F64>(p, ttab, threads, s);
+    if (p.nch == 4) return launch_rollout_tt<MODEL, NA, 4, 64, F64>(p, ttab, threads, s);
+    return -1;
+}

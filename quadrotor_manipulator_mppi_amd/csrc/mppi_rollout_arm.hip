@@ -11,3 +11,12 @@ extern "C" int mppi_launch_rollout_arm64(const DevParams* p, int threads, void* 
     if (p->nch == 4) return launch_rollout_t<MPPI_MODEL_ARM, 7, 4, 64, true>(*p, threads, s);
     return -1;
 }
+// the tracking kernels (k_rollout_tt; MPPI_COST_TARGET_TRACK), the H <= 32 one from its own unit
+extern "C" int mppi_launch_rollout_arm64_tt(const DevParams* p, const float* ttab, int threads, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
+    if (p->nch == 1 && p->L == 32) return mppi_launch_rollout_arm64_h32_tt(p, ttab, threads, stream);
+    if (p->nch == 1 && p->L == 64) return launch_rollout_tt<MPPI_MODEL_ARM, 7, 1, 64, true>(*p, ttab, threads, s);
+    if (p->nch == 2) return launch_rollout_tt<MPPI_MODEL_ARM, 7, 2, 64, true>(*p, ttab, threads, s);
+    if (p->nch == 4) return launch_rollout_tt<MPPI_MODEL_ARM, 7, 4, 64, true>(*p, ttab, threads, s);
+    return -1;
+}

@@ -4,3 +4,7 @@
 extern "C" int mppi_launch_rollout_arm32(const DevParams* p, int threads, void* stream) {
     return dispatch_geom<MPPI_MODEL_ARM, 7, false>(*p, threads, (hipStream_t)stream);
 }
+// the tracking kernels (k_rollout_tt; MPPI_COST_TARGET_TRACK)
+extern "C" int mppi_launch_rollout_arm32_tt(const DevParams* p, const float* ttab, int threads, void* stream) {
+    return dispatch_geom_tt<MPPI_MODEL_ARM, 7, false>(*p, ttab, threads, (hipStream_t)stream);
+}

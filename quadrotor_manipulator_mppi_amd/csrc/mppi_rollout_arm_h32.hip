@@ -8,3 +8,7 @@
 extern "C" int mppi_launch_rollout_arm64_h32(const DevParams* p, int threads, void* stream) {
     return launch_rollout_t<MPPI_MODEL_ARM, 7, 1, 32, true>(*p, threads, (hipStream_t)stream);
 }
+// the tracking kernel of the same geometry (k_rollout_tt; MPPI_COST_TARGET_TRACK)
+extern "C" int mppi_launch_rollout_arm64_h32_tt(const DevParams* p, const float* ttab, int threads, void* stream) {
+    return launch_rollout_tt<MPPI_MODEL_ARM, 7, 1, 32, true>(*p, ttab, threads, (hipStream_t)stream);
+}

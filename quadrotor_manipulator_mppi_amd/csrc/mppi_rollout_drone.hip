@@ -51,6 +51,28 @@ extern "C" int mppi_launch_rollout(const DevParams* p, int threads, void* stream
     return -1;
 }
 
+// The tracking launch (cost_terms & MPPI_COST_TARGET_TRACK): the same dispatch over the tracking
+// kernels (k_rollout_tt, k_rollout_quad_tt), handed the engine's target table (V, H, 12).
+extern "C" int mppi_launch_rollout_track(const DevParams* p, const float* ttab, int threads, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    switch (p->model) {
+        case MPPI_MODEL_DRONE:
+            if (p->A == 3) return dispatch_geom_tt<MPPI_MODEL_DRONE, 3, false>(*p, ttab, threads, s);
+            break;
+        case MPPI_MODEL_ARM:
+            if (p->A == 7) return p->state_f64 ? mppi_launch_rollout_arm64_tt(p, ttab, threads, stream)
+                                               : mppi_launch_rollout_arm32_tt(p, ttab, threads, stream);
+            break;
+        case MPPI_MODEL_WHOLEBODY:
+            if (p->A == 10) return mppi_launch_rollout_wb_tt(p, ttab, threads, stream);
+            break;
+        case MPPI_MODEL_QUADROTOR:
+            if (p->A == 4) return mppi_launch_rollout_quad_tt(p, ttab, threads, stream);
+            break;
+    }
+    return -1;
+}
+
 extern "C" int mppi_launch_philox(uint64_t seed, uint32_t step, int vehicle, int64_t k0, int K, int H, int A,
                                   float* z, uint32_t* raw, void* stream) {
     const int n = K * H;

@@ -70,12 +70,18 @@ __device__ __forceinline__ float qsum(float x) {
 // QUIET (k_rollout_quad_q): the rollout of a batch's step before its last, as k_rollout's quiet form
 // (mppi_rollout.h rollout_body): no trajectory stores or plane descriptor, no cost staging or store
 // run, no stored noise, no hand-off of the vehicle constants; the record is bit-identical.
-template <bool VONE, bool LIT, int NWD, int NT, bool QUIET>
+// TRK (k_rollout_quad_tt; MPPI_COST_TARGET_TRACK): the position target moves along the horizon.  The
+// (H, 3) position rows of the vehicle's target table go into LDS with the noise tile in phase 1
+// ([H+1][4] floats after u_prev), and the dynamics wave reads its axis' target one step ahead, as it
+// reads u_t and the eps row, so the LDS latency stays off the serial chain.
+template <bool VONE, bool LIT, int NWD, int NT, bool QUIET, bool TRK = false>
 __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const uint32_t seed_hi,
                                                   const uint32_t step_arg, const uint32_t k_off,
                                                   const int32_t noise_arg, const int32_t H,
-                                                  const float* __restrict__ u_prev, const DevParams& pk) {
+                                                  const float* __restrict__ u_prev, const DevParams& pk,
+                                                  const float* __restrict__ ttab = nullptr) {
     static_assert(NWD == 1 || NWD == kQWaves, "dynamics waves per block");
+    static_assert(!TRK || !QUIET, "the tracking body has no quiet form");
     constexpr bool kTraj = !QUIET && !(MPPI_KO & 16), kCosts = !QUIET && !(MPPI_KO & 1024),
                    kHand = !QUIET && !(MPPI_KO & 2048);
     static_assert(NT == kQThreads || (NWD == 1 && NT == kQThreadsWide), "block size");
@@ -96,6 +102,7 @@ __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const 
     const int kb = b * QR;                       // the block's rollouts kb .. kb+QR-1
     float* const eps_t = qlds;
     float* const u_t = qlds + (H + 1) * kQPitch;
+    float* const tg_t = u_t + (H + 1) * kQA;   // TRK: the target positions [H+1][4] (row H spare, zero)
     const VehicleConst& vc = VONE ? pk.vc0 : pk.vc[v];
     if (kHand && VONE && b == 0) {   // hand vc0 to the finalize (it reads vc[v])
         constexpr int kVCW = (int)(sizeof(VehicleConst) / 4);
@@ -158,6 +165,12 @@ __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const 
         }
     }
     if (tid < H * kQA) u_t[tid] = u_r;
+    if constexpr (TRK) {
+        for (int i = tid; i < (H + 1) * 4; i += NT) {
+            const int t = i >> 2, a = i & 3;
+            tg_t[i] = (t < H && a < 3) ? ttab[((size_t)v * H + t) * 12 + a] : 0.0f;
+        }
+    }
     __syncthreads();
     if (wid >= NWD) { drain_stores(); return; }
 
@@ -195,12 +208,16 @@ __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const 
     const float* rowp = eps_t + r * kQA;
     const float* urp = u_t;
     float pu0 = urp[0], pe0 = rowp[0], pu1 = urp[1 + jj], pe1 = rowp[1 + jj];
+    const float* tgp = tg_t + jj;
+    float ptg = TRK ? tgp[0] : tg;
     auto step = [&](const int t, auto first_c, auto last_c) {
         constexpr bool FIRST = decltype(first_c)::value, LAST = decltype(last_c)::value;
         const float thr = pu0 + pe0, tau = pu1 + pe1;
+        const float tgc = ptg;   // this step's target (TRK: row t, loaded a step ahead)
         rowp += kQPitch;
         urp += kQA;
         pu0 = urp[0]; pe0 = rowp[0]; pu1 = urp[1 + jj]; pe1 = rowp[1 + jj];
+        if constexpr (TRK) { tgp += 4; ptg = tgp[0]; }
         quad_axis_step<LIT, FIRST>(pj, ej, vj, wj, thr, tau, dt, im, kd, gj, ij, a0, ox0, oy0, oz0);
         if (store) {
             const uint32_t o = (uint32_t)t * tstep_b;
@@ -208,7 +225,7 @@ __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const 
             traj_store(trs, off_e, o, ej);
         }
         // squared position error of this axis (drone_mppi.py:87-107), summed over axes below
-        const float dd = pj - tg;
+        const float dd = pj - (TRK ? tgc : tg);
         if (LAST) term = dd * dd; else stage = fmaf(dd, dd, stage);
     };
     using T_ = std::true_type;
@@ -297,6 +314,16 @@ __global__ void __launch_bounds__(NT) k_rollout_quad_q(const uint32_t seed_lo, c
     rollout_quad_body<VONE, LIT, NWD, NT, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg, H, u_prev, pk);
 }
 
+// the tracking form (a new symbol): the target table as an extra pointer before the trailing DevParams
+template <bool VONE, bool LIT, int NWD, int NT>
+__global__ void __launch_bounds__(NT) k_rollout_quad_tt(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                               const uint32_t step_arg, const uint32_t k_off,
+                                                               const int32_t noise_arg, const int32_t H,
+                                                               const float* __restrict__ u_prev,
+                                                               const float* __restrict__ ttab, const DevParams pk) {
+    rollout_quad_body<VONE, LIT, NWD, NT, false, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg, H, u_prev, pk, ttab);
+}
+
 template <bool VONE, bool LIT, int NWD, int NT, bool QUIET>
 constexpr auto quad_kernel() {
     if constexpr (QUIET) return k_rollout_quad_q<VONE, LIT, NWD, NT>;
@@ -323,6 +350,28 @@ extern "C" int mppi_launch_rollout_quad(const DevParams* p, int threads, void* s
                     return go(k, dim3(p->nb, p->V), dim3(NT), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,
                               (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, *p);
                 });
+            });
+        });
+    });
+}
+
+// The tracking launch: the same block shapes, the full kernel on every step, LDS + the target rows.
+extern "C" int mppi_launch_rollout_quad_tt(const DevParams* p, const float* ttab, int threads, void* stream) {
+    (void)threads;
+    const int nwd = p->iters;
+    if (p->H > 64 || p->A != kQA || (nwd != 1 && nwd != kQWaves) || p->nb * kQR * nwd < p->K) return -1;
+    const size_t lds = (size_t)((p->H + 1) * (kQR * nwd * kQA + 1) + (p->H + 1) * kQA + (p->H + 1) * 4) * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+    const bool wide = nwd == 1 && (size_t)p->nb * p->V <= 512;
+    const int shape = wide ? 0 : nwd == 1 ? 1 : 2;
+    return pick<true, false>(p->V == 1, [&](auto vone) {
+        return pick<true, false>(p->q_literal_jinv != 0, [&](auto lit) {
+            return pick<0, 1, 2>(shape, [&](auto sh) {
+                constexpr int NW = sh() == 2 ? kQWaves : 1, NT = sh() == 0 ? kQThreadsWide : kQThreads;
+                const auto k = k_rollout_quad_tt<vone(), lit(), NW, NT>;
+                static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+                return go(k, dim3(p->nb, p->V), dim3(NT), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,
+                          (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, ttab, *p);
             });
         });
     });

@@ -69,7 +69,7 @@ static mppi_status rollout_impl(mppi_engine* e, const float* d_noise, bool quiet
     p.step_ctr = e->step_ctr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (e->timing) { e0 = pool_event(e); e1 = pool_event(e); HIP_TRY(hipEventRecord(e0, e->stream)); }
-    int rc = mppi_launch_rollout(&p, e->threads, e->stream);
+    int rc = launch_rollout(p, e->d_ttab, e->threads, e->stream);
     if (rc != 0) return fail(MPPI_ERR_HIP, "rollout launch failed (%d: %s)", rc,
                              rc > 0 ? hipGetErrorString((hipError_t)rc) : "no kernel for this model/A/H");
     if (e->timing) {
@@ -270,8 +270,9 @@ mppi_status mppi_read_outputs(mppi_engine* e, double* out, float* u0, mppi_stats
             float T16[16];
             host_fk_c(e->cfg.joints, e->cfg.n_joints, e->fk_O.data(), e->fk_ax.data(), qdes, s, e->cfg.state_f64 != 0,
                       T16);
-            const float err = std::fabs(T16[3] - e->tpos[3 * v]) + std::fabs(T16[7] - e->tpos[3 * v + 1]) +
-                              std::fabs(T16[11] - e->tpos[3 * v + 2]);
+            // (a tracking engine: row 0 of the vehicle's table, the pose wanted one step ahead, where qdes is)
+            const float* tp = e->d_ttab ? &e->h_ttab[(size_t)v * e->H * 12] : &e->tpos[3 * v];
+            const float err = std::fabs(T16[3] - tp[0]) + std::fabs(T16[7] - tp[1]) + std::fabs(T16[11] - tp[2]);
             reach = err < e->cfg.reach_tol;
         }
         // 2: a peer-exchange step given up (a rank's timeout: u_prev kept) -- this step's flag or
@@ -332,7 +333,7 @@ mppi_status mppi_step(mppi_engine* e, const double* state, const float* h_noise,
     if (e->comm && (st = mppi_exchange(e)) != MPPI_OK) return st;
     if ((st = mppi_finalize(e)) != MPPI_OK) return st;
     if (!e->kern_call_hip || e->kern_call_peer != e->peer) {   // (mppi_kernel_info; described once)
-        e->kern_call = kernels_text(roll_symbol(rollout_params(e, StepPath::Hip, dn, false), e->threads),
+        e->kern_call = kernels_text(roll_symbol(rollout_params(e, StepPath::Hip, dn, false), e->threads, nullptr, e->d_ttab),
                                     fin_symbol(finalize_params(e, FinKind::Final)), nullptr);
         e->kern_call_hip = true;
         e->kern_call_peer = e->peer;
@@ -497,7 +498,7 @@ mppi_status mppi_run_steps(mppi_engine* e, int32_t n) {
         if ((st = finalize_impl(e, i == n - 1, true)) != MPPI_OK) return st;
     }
     {   // (mppi_kernel_info) the launches above, described
-        const auto roll = [&](bool quiet) { return roll_symbol(rollout_params(e, StepPath::Hip, nullptr, quiet), e->threads); };
+        const auto roll = [&](bool quiet) { return roll_symbol(rollout_params(e, StepPath::Hip, nullptr, quiet), e->threads, nullptr, e->d_ttab); };
         const auto fin = [&](bool quiet) { return fin_symbol(finalize_params(e, FinKind::Final, StepPath::Hip, quiet)); };
         const std::string q = fin(n > 1), rq = roll(n > 1);
         e->kern_batch = kernels_text(roll(false), fin(false), &q, &rq);

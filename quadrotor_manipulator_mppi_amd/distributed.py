@@ -405,6 +405,11 @@ class ShardedEngine:
         eng.set_u_prev(u.cpu().numpy())
         self.resyncs += 1
 
+    def set_target_trajectory(self, pos, quat=None, vehicle: int = 0):
+        """This rank's engine's target table (Engine.set_target_trajectory).  Every rank is given the
+        same table, like the state."""
+        self.engine.set_target_trajectory(pos, quat, vehicle)
+
     def get_plan(self):
         """The nominal plan (``Engine.get_plan``): the warm start is the same on every rank, so each
         rank's engine returns the same plan; no collective."""

@@ -97,7 +97,8 @@ def make_config(model: str = "arm", n_samples: Optional[int] = None, n_horizon: 
                 quad: Optional[Dict] = None, vehicle_offset: int = 0) -> capi.Config:
     """``cost_terms``: bitmask of ``capi.COST_*`` or an iterable of names among
     ``covar, center, joint_track, action, joint_limit`` -- the CostManager terms the
-    reference ships disabled (cost_manager.py:83-87).  ``cost_weights`` overrides
+    reference ships disabled (cost_manager.py:83-87; ARM and WHOLEBODY) -- and ``target_track`` (every
+    model): one pose target per horizon step, ``Engine.set_target_trajectory``.  ``cost_weights`` overrides
     ``w_covar, cost_alpha, cost_gamma, w_center, w_joint_track, w_action,
     joint_limit_penalty``.  ``quad`` overrides the QUADROTOR rigid body: ``quad_mass``,
     ``quad_inertia`` (3,), ``quad_kd``, ``quad_gravity``, ``quad_literal_jinv``.  ``vehicle_offset``:
@@ -162,7 +163,8 @@ def make_config(model: str = "arm", n_samples: Optional[int] = None, n_horizon: 
 
 
 COST_TERMS = {"covar": capi.COST_COVAR, "center": capi.COST_CENTER, "joint_track": capi.COST_JOINT_TRACK,
-              "action": capi.COST_ACTION, "joint_limit": capi.COST_JOINT_LIMIT}
+              "action": capi.COST_ACTION, "joint_limit": capi.COST_JOINT_LIMIT,
+              "target_track": capi.COST_TARGET_TRACK}
 COST_WEIGHT_FIELDS = ("w_covar", "cost_alpha", "cost_gamma", "w_center", "w_joint_track", "w_action",
                       "joint_limit_penalty")
 
@@ -318,6 +320,15 @@ class Engine:
             self._tgt_quat[:] = np.reshape(quat, 4)
         capi.check(self._L.mppi_set_target(self._h, vehicle, self._p_tpos,
                                            None if quat is None else self._p_tquat), "set_target")
+
+    def set_target_trajectory(self, pos, quat=None, vehicle: int = 0):
+        """Target trajectory of a ``target_track`` engine: ``pos`` (H, 3), row t the position wanted
+        at horizon index t, (t + 1) dt from now; ``quat`` (H, 4) xyzw rows (None: the fixed target's
+        orientation on every row).  ``pos=None`` clears the table: the fixed target again."""
+        p = None if pos is None else np.ascontiguousarray(pos, np.float32).reshape(self.H, 3)
+        q = None if quat is None or pos is None else np.ascontiguousarray(quat, np.float32).reshape(self.H, 4)
+        capi.check(self._L.mppi_set_target_trajectory(self._h, vehicle, capi.fptr(p), capi.fptr(q)),
+                   "set_target_trajectory")
 
     def set_joint_trajectory(self, traj=None, vehicle: int = 0):
         """Joint tracking target (H, nq) of the joint_track cost term (None = zeros)."""

@@ -20,7 +20,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ..engine import Engine, make_config
+from .. import _capi as capi
+from ..engine import Engine, cost_term_bits, make_config
 
 
 class OutputRing:
@@ -147,6 +148,51 @@ class SolverBase:
             eng.set_target(pos, quat)
             self._last_target = (eng, key)
 
+    # ------------------------------------------------- target trajectory
+    # ``track_target=True`` (a constructor switch of the three classes) makes the engine a
+    # ``target_track`` one: the pose target may move along the horizon.  While no table is set the
+    # control call keeps pushing the class's fixed target, which a clear table follows.
+    _track_target = False
+    _target_rows = None    # (pos (H,3), quat (H,4) or None) of set_target_trajectory; None: clear
+    _rows_sent = None      # (engine, rows) last written (_sync_target_rows)
+
+    def _track_bits(self, cost_terms=0) -> int:
+        return cost_term_bits(cost_terms) | (capi.COST_TARGET_TRACK if self._track_target else 0)
+
+    def set_target_trajectory(self, poses) -> None:
+        """One pose per horizon step: (H, 7) rows xyz + quaternion xyzw, or (H, 3) positions (the
+        drone classes; the arm then keeps ``target_pose``'s orientation on every row).  Row t is the
+        pose wanted at horizon index t, (t + 1) dt from now.  Used from the next control call on."""
+        if not self._track_target:
+            raise RuntimeError("set_target_trajectory needs track_target=True at construction")
+        a = np.ascontiguousarray(poses, np.float32)
+        H = getattr(self, self._horizon_attr)
+        if a.shape == (H, 7):
+            self._target_rows = (a[:, :3].copy(), a[:, 3:].copy())
+        elif a.shape == (H, 3):
+            self._target_rows = (a.copy(), None)
+        else:
+            raise ValueError(f"target trajectory of shape {a.shape}: ({H}, 7) or ({H}, 3)")
+
+    def clear_target_trajectory(self) -> None:
+        """Back to the fixed target (``target_pose`` / ``target``) on every horizon step."""
+        if not self._track_target:
+            raise RuntimeError("clear_target_trajectory needs track_target=True at construction")
+        self._target_rows = None
+
+    def _sync_target_rows(self, eng: Engine) -> None:
+        """The table into the engine when it changed since the last call (after _sync_target: a
+        clear table follows the fixed target)."""
+        if not self._track_target:
+            return
+        rows, sent = self._target_rows, self._rows_sent
+        if sent is None or sent[0] is not eng or sent[1] is not rows:
+            if rows is None:
+                eng.set_target_trajectory(None)
+            else:
+                eng.set_target_trajectory(rows[0], rows[1])
+            self._rows_sent = (eng, rows)
+
     def compute_weights(self, S: torch.Tensor, _lambda) -> torch.Tensor:
         """mppi.py:173-193 / drone_mppi.py:111-130 (host helper; the engine computes the same
         weights on device)."""
@@ -180,8 +226,10 @@ class VehicleSolver(SolverBase):
 
     _horizon_attr = "n_timestep"
 
-    def __init__(self, width: int, sigma: torch.Tensor, n_samples: int, n_timestep: int, *base_args):
+    def __init__(self, width: int, sigma: torch.Tensor, n_samples: int, n_timestep: int, *base_args,
+                 track_target: bool = False):
         super().__init__(sigma.shape[0], n_timestep, *base_args)
+        self._track_target = bool(track_target)
         self.n_samples = n_samples
         self.n_timestep = n_timestep
         self.x_prev = torch.zeros(width)
@@ -197,7 +245,7 @@ class VehicleSolver(SolverBase):
         return make_config(model, n_samples=self.n_samples, n_horizon=self.n_timestep, dt=self.dt,
                            lam=self.param_lambda, sigma=self.sigma.numpy(), seed=self._seed,
                            noise="injected" if key[0] else self._noise, device=self._dev_index,
-                           **extra)
+                           cost_terms=self._track_bits(), **extra)
 
     def set_state(self, x, v):
         """drone_mppi.py:179-183 (stored as float32 like the reference)."""
@@ -214,6 +262,7 @@ class VehicleSolver(SolverBase):
         # after construction rebuilds the engine at the next call
         eng = self._ensure_engine((noise is not None or self._noise == "injected", self.n_samples, self.n_timestep))
         self._sync_target(eng, np.asarray(self.target, np.float32))
+        self._sync_target_rows(eng)
         out, u0, stats = eng.step(row, noise)
         st = self._after_step(u0, stats)   # (u: the tensor is made on first read)
         if self.verbose:

@@ -55,14 +55,17 @@ class MPPI(SolverBase):
     def __init__(self, n_samples: int = 100, n_horizon: int = 32, device: Optional[int] = None,
                  noise: str = "philox", seed: int = 0x5EED, urdf_path: Optional[str] = None,
                  root_link: str = "base", end_link: str = "j2s7s300_link_7", verbose: bool = True,
-                 cost_terms=(), cost_weights=None, prewarm_us: int = 0):
-        """``cost_terms``: CostManager terms to switch on beyond the pose cost the
+                 cost_terms=(), cost_weights=None, prewarm_us: int = 0, track_target: bool = False):
+        """``track_target``: a pose target that may move along the horizon
+        (``set_target_trajectory`` with (H, 7) rows xyz + xyzw, ``clear_target_trajectory``); while
+        no table is set, ``target_pose`` is the target of every step as before.  ``cost_terms``: CostManager terms to switch on beyond the pose cost the
         reference runs (cost_manager.py:83-87): any of ``covar, center, joint_track,
         action, joint_limit`` (engine.COST_TERMS); ``cost_weights`` overrides their
         weights (defaults: cost_manager.py:21-43).  ``prewarm_us`` > 0: the engine's queue
         prewarm with that window (mppi_set_prewarm), for a node ticking with idle gaps such as
         kinova.py:101's rospy.Rate(100); results are unchanged."""
         super().__init__(7, n_horizon, device, noise, seed, verbose, prewarm_us)
+        self._track_target = bool(track_target)
         # mppi.py:37-42
         self.n_manipulator_dof = 7
         self.n_mobile_dof = 0
@@ -92,7 +95,8 @@ class MPPI(SolverBase):
         return make_config("arm", n_samples=self.n_samples, n_horizon=self.n_horizon, dt=self.dt,
                            lam=self._lambda, chain=self.chain, noise="injected" if key[1] else self._noise,
                            seed=self._seed, device=self._dev_index, state_f64=key[0], check_reach=True,
-                           cost_terms=self._cost_terms, cost_weights=self._cost_weights)
+                           cost_terms=self._track_bits(self._cost_terms) if self._track_target else self._cost_terms,
+                           cost_weights=self._cost_weights)
 
     # ------------------------------------------------------------ reference API
     def update_joint(self, q_full, v_full):
@@ -132,6 +136,7 @@ class MPPI(SolverBase):
         if views is None or views[0] is not pt or views[1] is not qt:
             views = self._target_views = (pt, qt, pt.numpy(), qt.numpy())
         self._sync_target(eng, views[2], views[3])
+        self._sync_target_rows(eng)
         out, u0, stats = eng.step(self._state_row(q, qd, base), noise)
         dt = np.float64 if f64 else np.float32
         self.qdes = out[0, :7].astype(dt)
@@ -148,5 +153,8 @@ class MPPI(SolverBase):
         if self.qdes is None:
             return False
         T = host_fk(self.chain, self.qdes, base, f64)
-        err = float(np.abs(T[:3, 3] - self.target_pose.pose.numpy()).sum())
+        # (a table set: row 0, the pose wanted one step ahead, where qdes is)
+        rows = self._target_rows
+        tgt = self.target_pose.pose.numpy() if rows is None else rows[0][0]
+        err = float(np.abs(T[:3, 3] - tgt).sum())
         return err < 0.005

@@ -25,9 +25,10 @@ from ._base import VehicleSolver
 class MPPI(VehicleSolver):
     def __init__(self, n_samples: int = 1000, n_timestep: int = 32, device: Optional[int] = None,
                  noise: str = "philox", seed: int = 0x5EED, mass: float = 14.7,
-                 inertia=(1.57, 3.93, 2.59), kd: float = 0.0, gravity: float = 9.81, verbose: bool = False, prewarm_us: int = 0):
+                 inertia=(1.57, 3.93, 2.59), kd: float = 0.0, gravity: float = 9.81, verbose: bool = False, prewarm_us: int = 0,
+                 track_target: bool = False):
         super().__init__(6, torch.diag(torch.tensor([30.0, 1.0, 1.0, 1.0])), n_samples, n_timestep,
-                         device, noise, seed, verbose, prewarm_us)
+                         device, noise, seed, verbose, prewarm_us, track_target=track_target)
         self.params = dict(quad_mass=mass, quad_inertia=tuple(inertia), quad_kd=kd, quad_gravity=gravity)
         self._u_prev_host[:, 0] = np.float32(mass * gravity)   # hover thrust
 
