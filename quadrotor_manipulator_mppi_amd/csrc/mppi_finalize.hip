@@ -41,6 +41,12 @@ constexpr int kMaxRec = 4096;
 #ifndef MPPI_FIN_XCDS
 #define MPPI_FIN_XCDS 8
 #endif
+// the quiet role folds no eta^2 (kRoleQuiet): it reaches only the effective sample size of the outputs
+// section, which the quiet role does not have -- u_prev = u_old + SavGol(N / eta), eta = NaN under the
+// records' nan flag, so rho, eta, the nan flag and the bodies stay.  0 = folded as in the other roles
+#ifndef MPPI_FIN_QUIET_LEAN
+#define MPPI_FIN_QUIET_LEAN 1
+#endif
 
 #if defined(MPPI_STAMPS) && !defined(MPPI_TIMELINE)
 #define FSTAMP(i)                                                                    \
@@ -128,6 +134,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
     constexpr bool kOut = kAny || ROLE == kRoleFinal || ROLE == kRolePeer;   // the outputs section
     constexpr bool kUpd = kOut || kQuiet;                                     // SavGol and the u_prev update
     constexpr bool kPeer = kAny || ROLE == kRolePeer;                         // the peer exchange
+    constexpr bool kEta2 = !(kQuiet && MPPI_FIN_QUIET_LEAN);                  // eta^2 (the outputs' ess)
     constexpr int NWV = NT / 64;
     constexpr int ROWS = 64 / CW;          // rows per wave
     constexpr int TR = NWV * ROWS;         // rows per block
@@ -346,6 +353,13 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
         float m = INFINITY;
 #pragma unroll
         for (int i = 0; i < kNPT; ++i) { m = fminf(m, hd[i].x); nanflag = fmaxf(nanflag, hd[i].w); }
+        if constexpr (!kEta2) {
+            // the headers' third words stay allocated until every header is in: dead from the start, the
+            // allocator gave their registers to the later loads' offsets, and each such offset waited
+            // (vmcnt) for the header load it shared a register with before the last loads were issued
+#pragma unroll
+            for (int i = 0; i < kNPT; ++i) asm volatile("" :: "v"(hd[i].z));
+        }
         // the body terms are accumulated outside the branch: used only inside it, the
         // compiler sank the body loads into it, behind a wait for every header load (two
         // memory round trips instead of one).  f = 0 adds exactly nothing (bodies are finite:
@@ -360,7 +374,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) acc[j] *= sc;
                 eta *= sc;
-                eta2 *= sc * sc;
+                if constexpr (kEta2) eta2 *= sc * sc;
             }
             rho_t = rn;
 #pragma unroll
@@ -368,7 +382,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
                 const float f = (hd[i].x < INFINITY) ? __expf(coef * (hd[i].x - rn)) : 0.0f;
                 fr[i] = f;
                 eta = fmaf(f, hd[i].y, eta);
-                eta2 = fmaf(f * f, hd[i].z, eta2);
+                if constexpr (kEta2) eta2 = fmaf(f * f, hd[i].z, eta2);
             }
         }
 #pragma unroll
@@ -400,7 +414,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
         const float sc = (rho_t < INFINITY) ? __expf(coef * (rho_t - rw)) : 0.0f;
 #pragma unroll
         for (int j = 0; j < CPL; ++j) acc[j] = fold_g(acc[j] * sc, OpAdd());
-        const float e1 = fold_g(eta * sc, OpAdd()), e2 = fold_g(eta2 * (sc * sc), OpAdd());
+        const float e1 = fold_g(eta * sc, OpAdd()), e2 = kEta2 ? fold_g(eta2 * (sc * sc), OpAdd()) : 0.0f;
         const float nf = fold_g(nanflag, OpMax());
         if (g == 0) {
 #pragma unroll
@@ -408,7 +422,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
                 const int wq = q * CPL + j - doff;   // window column (the tail's lane)
                 if (wq >= 0 && wq < W) wcol[wo][wq] = acc[j];
             }
-            if (q == 0) { wrho[wo] = rw; wnan[wo] = nf; weta[wo] = e1; weta2[wo] = e2; }
+            if (q == 0) { wrho[wo] = rw; wnan[wo] = nf; weta[wo] = e1; if constexpr (kEta2) weta2[wo] = e2; }
         }
     }
     FSTAMP(1);
@@ -428,7 +442,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
         const float f = (wrho[w] < INFINITY) ? __expf(coef * (wrho[w] - rho)) : 0.0f;
         N = fmaf(f, (lane < CW) ? wcol[w][lane] : 0.0f, N);
         eta = fmaf(f, weta[w], eta);
-        eta2 = fmaf(f * f, weta2[w], eta2);
+        if constexpr (kEta2) eta2 = fmaf(f * f, weta2[w], eta2);
     }
     FSTAMP(3);
     bool xlate = false;   // the peer exchange gave the step up: this step keeps the warm start (w_eps = 0)

@@ -70,6 +70,20 @@
 #ifndef MPPI_COMB_EXIT
 #define MPPI_COMB_EXIT 0
 #endif
+// the quiet bodies form no eta^2 (rollout_body QUIET, rollout_quad_body QUIET): the quiet FINAL, the only
+// reader of a quiet step's records, turns eta^2 into nothing (mppi_finalize.hip: the effective sample
+// size of the outputs section alone), so the header's third word is written as 0.  0 = formed as in
+// the full body (same-process A/B, tools/ab_native.py)
+#ifndef MPPI_QUIET_LEAN
+#define MPPI_QUIET_LEAN 1
+#endif
+// the Kinova chain of the C3 kernels (arm, fp64 state, one 32-lane segment; the max-ilp unit): the seven
+// joints' sin / cos (each needs only the integrator's q_j) formed ahead of the chain, seven independent
+// reductions and transcendental pairs, instead of each inside its joint's step, where its result is
+// consumed at once; 0 = inside the steps
+#ifndef MPPI_FK_PRETRIG
+#define MPPI_FK_PRETRIG 1
+#endif
 
 namespace {
 
@@ -325,8 +339,9 @@ __device__ __forceinline__ void sincos_joint(float q, float& s, float& c) {
 // One Kinova joint: T <- T * [P | o] * Rz(q), P a signed permutation fixed at
 // compile time (kKinova, mppi_dev.h): the rotation part is register renaming and
 // negation (source modifiers), the translation only its nonzero components.
-template <int J, typename QT>
-__device__ __forceinline__ void kin_joint(Mat34& T, const float* O, QT q) {
+// (PRE: the angle's sin and cos are given, else formed here, between the origin and the rotation)
+template <int J, bool PRE, typename QT>
+__device__ __forceinline__ void kin_joint_x(Mat34& T, const float* O, QT q, float s, float c) {
     constexpr KinOrigin k = kKinova[J];
     Mat34 r;
 #pragma unroll
@@ -339,8 +354,7 @@ __device__ __forceinline__ void kin_joint(Mat34& T, const float* O, QT q) {
         for (int j = 0; j < 3; ++j) r.m[4 * i + j] = (k.s[j] > 0) ? T.m[4 * i + k.p[j]] : -T.m[4 * i + k.p[j]];
         r.m[4 * i + 3] = tr;
     }
-    float s, c;
-    sincos_joint(q, s, c);
+    if constexpr (!PRE) sincos_joint(q, s, c);
     // Rodrigues about z (transformation_matrix.py:68-93).  Its R22 = fl(c + fl(1 - c)) is
     // 1 or 1 - 2^-24 (a rounding tie of 1 - c for some c < -1/2); the fast path takes 1,
     // as it takes the origins' pi/2 rotations exactly (<= 6e-8 relative).
@@ -352,6 +366,14 @@ __device__ __forceinline__ void kin_joint(Mat34& T, const float* O, QT q) {
         T.m[4 * i + 2] = r.m[4 * i + 2];   // R22 = fl(c + fl(1 - c)) taken as 1
         T.m[4 * i + 3] = r.m[4 * i + 3];
     }
+}
+template <int J, typename QT>
+__device__ __forceinline__ void kin_joint(Mat34& T, const float* O, QT q) {
+    kin_joint_x<J, false>(T, O, q, 0.0f, 0.0f);
+}
+template <int J>
+__device__ __forceinline__ void kin_joint_sc(Mat34& T, const float* O, const float s, const float c) {
+    kin_joint_x<J, true>(T, O, 0.0f, s, c);
 }
 
 // atan2 with octant reduction and a degree-8 odd minimax polynomial on [0,1]
@@ -740,6 +762,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     constexpr bool kTraj = !QUIET && !(MPPI_KO & 16);      // trajectory planes
     constexpr bool kCosts = !QUIET && !(MPPI_KO & 1024);   // the cost vector S
     constexpr bool kHand = !QUIET && !(MPPI_KO & 2048);    // block 0's vehicle-constant hand-off
+    constexpr bool kEta2 = !(QUIET && MPPI_QUIET_LEAN);    // eta^2 (the outputs' effective sample size)
     constexpr int R = 64 / LSEG;
     constexpr int QOFF = (MODEL == MPPI_MODEL_WHOLEBODY) ? 3 : 0;
     constexpr int NQ = (MODEL == MPPI_MODEL_DRONE) ? 0 : NA - QOFF;
@@ -1127,13 +1150,27 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                     T.m[3] += posf[c][QOFF]; T.m[7] += posf[c][QOFF + 1];
                 } else if (NQ == 7 && (!XC || p.chain_fast == 2)) {   // Kinova: origin rotations are signed
                     // permutations (the common kernel runs only this chain; any other goes to XC)
-                    kin_joint<0>(T, jnt[p.j0 + 0].O, qang(c, 0));
-                    kin_joint<1>(T, jnt[p.j0 + 1].O, qang(c, 1));
-                    kin_joint<2>(T, jnt[p.j0 + 2].O, qang(c, 2));
-                    kin_joint<3>(T, jnt[p.j0 + 3].O, qang(c, 3));
-                    kin_joint<4>(T, jnt[p.j0 + 4].O, qang(c, 4));
-                    kin_joint<5>(T, jnt[p.j0 + 5].O, qang(c, 5));
-                    kin_joint<6>(T, jnt[p.j0 + 6].O, qang(c, 6));
+                    if constexpr (MPPI_FK_PRETRIG && !XC && NCH == 1 && F64 && LSEG == 32 && MODEL == MPPI_MODEL_ARM) {
+                        float sj[7], cj[7];
+#pragma unroll
+                        for (int j = 0; j < 7; ++j) sincos_joint(qang(c, j), sj[j], cj[j]);
+                        __builtin_amdgcn_sched_barrier(0);   // (the scheduler would sink each pair to its use)
+                        kin_joint_sc<0>(T, jnt[p.j0 + 0].O, sj[0], cj[0]);
+                        kin_joint_sc<1>(T, jnt[p.j0 + 1].O, sj[1], cj[1]);
+                        kin_joint_sc<2>(T, jnt[p.j0 + 2].O, sj[2], cj[2]);
+                        kin_joint_sc<3>(T, jnt[p.j0 + 3].O, sj[3], cj[3]);
+                        kin_joint_sc<4>(T, jnt[p.j0 + 4].O, sj[4], cj[4]);
+                        kin_joint_sc<5>(T, jnt[p.j0 + 5].O, sj[5], cj[5]);
+                        kin_joint_sc<6>(T, jnt[p.j0 + 6].O, sj[6], cj[6]);
+                    } else {
+                        kin_joint<0>(T, jnt[p.j0 + 0].O, qang(c, 0));
+                        kin_joint<1>(T, jnt[p.j0 + 1].O, qang(c, 1));
+                        kin_joint<2>(T, jnt[p.j0 + 2].O, qang(c, 2));
+                        kin_joint<3>(T, jnt[p.j0 + 3].O, qang(c, 3));
+                        kin_joint<4>(T, jnt[p.j0 + 4].O, qang(c, 4));
+                        kin_joint<5>(T, jnt[p.j0 + 5].O, qang(c, 5));
+                        kin_joint<6>(T, jnt[p.j0 + 6].O, qang(c, 6));
+                    }
                 } else if (!XC) {   // (unreachable: the common kernel is dispatched for Kinova chains only)
                 } else if (p.chain_fast) {   // nq revolute-z joints, q_index = 0..nq-1 in order
 #pragma unroll
@@ -1271,10 +1308,10 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             for (int s = 0; s < R; ++s) {
                 const float e = (S_seg[s] < INFINITY) ? __expf(p.coef * (S_seg[s] - rn)) : 0.0f;
                 es += e;
-                e2 += e * e;
+                if constexpr (kEta2) e2 += e * e;
             }
             eta_w = eta_w * f + es;
-            eta2_w = eta2_w * f * f + e2;
+            if constexpr (kEta2) eta2_w = eta2_w * f * f + e2;
             const float e_mine = (kval && !(S_mine != S_mine)) ? __expf(p.coef * (S_mine - rn)) : 0.0f;
             if constexpr (kStash) {
                 asm volatile("" ::: "memory");
@@ -1376,7 +1413,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
 #pragma unroll
         for (int w = 0; w < 8; ++w) {
             eta += fw[w] * wsh[w * wstride + 1];
-            eta2 += fw[w] * fw[w] * wsh[w * wstride + 2];
+            if constexpr (kEta2) eta2 += fw[w] * fw[w] * wsh[w * wstride + 2];
             nanf = fmaxf(nanf, wsh[w * wstride + 3]);
         }
         wt_store4(uniform_ptr(p.hdr), ((uint32_t)v * (uint32_t)p.nb + blockIdx.x) * 16u, make_float4(rho_b, eta, eta2, nanf));

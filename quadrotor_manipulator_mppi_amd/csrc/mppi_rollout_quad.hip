@@ -253,7 +253,9 @@ __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const 
         for (int w = 0; w < NWD; ++w) { rho = fminf(rho, wred[w][0]); nanf = fmaxf(nanf, wred[w][3]); }
     }
     const float e = (mine && !bad && rho < INFINITY) ? __expf(scoef * (S - rho)) : 0.0f;
-    float eta = wave_fold_all(e, OpAdd()), eta2 = wave_fold_all(e * e, OpAdd());
+    // (no eta^2 in the quiet body, MPPI_QUIET_LEAN: the quiet FINAL turns it into nothing)
+    constexpr bool kEta2 = !(QUIET && MPPI_QUIET_LEAN);
+    float eta = wave_fold_all(e, OpAdd()), eta2 = kEta2 ? wave_fold_all(e * e, OpAdd()) : 0.0f;
     if (j == 0) e_lds[r] = e;
     wave_lds_handoff();
     if constexpr (kCosts) {   // this wave's 16 costs as one write-through 64 B run (mppi_device.h st_dev_run)
@@ -272,13 +274,13 @@ __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const 
         }
     }
     if constexpr (NWD > 1) {
-        if (lane == 0) { wred[wid][1] = eta; wred[wid][2] = eta2; }
+        if (lane == 0) { wred[wid][1] = eta; if constexpr (kEta2) wred[wid][2] = eta2; }
         if (wid > 0 && lane < H) part[wid][lane] = make_float4(n[0], n[1], n[2], n[3]);
         __syncthreads();
         if (wid != 0) { drain_stores(); return; }
         eta = 0.0f; eta2 = 0.0f;
 #pragma unroll
-        for (int w = 0; w < NWD; ++w) { eta += wred[w][1]; eta2 += wred[w][2]; }
+        for (int w = 0; w < NWD; ++w) { eta += wred[w][1]; if constexpr (kEta2) eta2 += wred[w][2]; }
         if (lane < H) {
 #pragma unroll
             for (int w = 1; w < NWD; ++w) {
