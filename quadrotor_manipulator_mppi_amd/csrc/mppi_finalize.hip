@@ -47,6 +47,19 @@ constexpr int kMaxRec = 4096;
 #ifndef MPPI_FIN_QUIET_LEAN
 #define MPPI_FIN_QUIET_LEAN 1
 #endif
+// a chunk whose rows are all below n (a block-uniform scalar test; the one chunk of the default shapes:
+// n = 128 or 256 records = TR * kNPT) builds no row-valid mask and masks no header; a ragged chunk takes
+// the masked path.  In the roles without the peer exchange only (FINAL, quiet, PACK): with it in the
+// kernels that carry the exchange, eight ranks as eight engines in one process gave a step up
+// (tests/test_gpu_peer.py), so those keep every chunk masked.  0 = every chunk masked
+#ifndef MPPI_FIN_FULL_CHUNK
+#define MPPI_FIN_FULL_CHUNK 1
+#endif
+// the 16 row factors exp(coef * (rho_row - rn)) without their rho_row < inf selects (the argument is at
+// the site in fin_body); 0 = with the selects
+#ifndef MPPI_FIN_EXP_BARE
+#define MPPI_FIN_EXP_BARE 1
+#endif
 
 #if defined(MPPI_STAMPS) && !defined(MPPI_TIMELINE)
 #define FSTAMP(i)                                                                    \
@@ -135,6 +148,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
     constexpr bool kUpd = kOut || kQuiet;                                     // SavGol and the u_prev update
     constexpr bool kPeer = kAny || ROLE == kRolePeer;                         // the peer exchange
     constexpr bool kEta2 = !(kQuiet && MPPI_FIN_QUIET_LEAN);                  // eta^2 (the outputs' ess)
+    constexpr bool kFull = MPPI_FIN_FULL_CHUNK && !kPeer;                     // full chunks skip the row masks
     constexpr int NWV = NT / 64;
     constexpr int ROWS = 64 / CW;          // rows per wave
     constexpr int TR = NWV * ROWS;         // rows per block
@@ -323,11 +337,13 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
         float xv[kNPT][CPL];
         uint32_t okm = 0;   // rows past n are masked at use: a select on the loaded value
                             // here made the compiler wait for each load in turn
+        // (block-uniform: n and base are scalars.  A full chunk has no row to mask)
+        const bool ragged = !kFull || base + TR * kNPT > n;
         const uint32_t r0 = (uint32_t)(base + gr);
         const uint32_t hoff = r0 * hrs_b, coff = r0 * drs_b + (uint32_t)(qv ? q : 0) * (uint32_t)(4 * CPL);
 #pragma unroll
         for (int i = 0; i < kNPT; ++i) {
-            okm |= (uint32_t)(r0 + (uint32_t)(i * TR) < (uint32_t)n) << i;
+            if constexpr (!kFull) okm |= (uint32_t)(r0 + (uint32_t)(i * TR) < (uint32_t)n) << i;
             const u32x4 h = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, (int)(hoff + (uint32_t)(i * TR) * hrs_b), 0, kAuxDev);
             hd[i] = make_float4(__uint_as_float(h.x), __uint_as_float(h.y), __uint_as_float(h.z), __uint_as_float(h.w));
             const int bo = (int)(coff + (uint32_t)(i * TR) * drs_b);
@@ -346,9 +362,15 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
             __builtin_amdgcn_sched_barrier(0);   // the first chunk's record loads issue first
             pin_tail();
         }
+        if (ragged) {
+            if constexpr (kFull) {   // (the mask is built here, on the ragged path alone)
 #pragma unroll
-        for (int i = 0; i < kNPT; ++i)
-            if (!((okm >> i) & 1u)) hd[i].x = INFINITY;   // f = 0: y, z and xv drop out
+                for (int i = 0; i < kNPT; ++i) okm |= (uint32_t)(r0 + (uint32_t)(i * TR) < (uint32_t)n) << i;
+            }
+#pragma unroll
+            for (int i = 0; i < kNPT; ++i)
+                if (!((okm >> i) & 1u)) hd[i].x = INFINITY;   // f = 0: y, z and xv drop out
+        }
         FSTAMP(7);
         float m = INFINITY;
 #pragma unroll
@@ -379,7 +401,16 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
             rho_t = rn;
 #pragma unroll
             for (int i = 0; i < kNPT; ++i) {
-                const float f = (hd[i].x < INFINITY) ? __expf(coef * (hd[i].x - rn)) : 0.0f;
+                // MPPI_FIN_EXP_BARE: no select.  It only ever caught hd[i].x = +inf (a masked row, a block
+                // without a finite cost): a record's rho is a min that skips NaN costs (they travel in the
+                // nan flag), so it is never NaN.  rn < +inf inside this branch and coef < 0 (mppi_create
+                // refuses a lambda whose fp32(-1 / lambda) is not negative), so for +inf the argument is
+                // coef * (+inf) = -inf and v_exp_f32(-inf) = +0: the select's own value.  (rn = -inf gives
+                // -inf again, or NaN for a row at -inf with and without the select.)  The wave and block
+                // factors below keep theirs: their reference is a min over lanes or waves that is +inf when
+                // none of them saw a finite cost, and inf - inf is NaN.
+                const float f = MPPI_FIN_EXP_BARE ? __expf(coef * (hd[i].x - rn))
+                                                  : (hd[i].x < INFINITY) ? __expf(coef * (hd[i].x - rn)) : 0.0f;
                 fr[i] = f;
                 eta = fmaf(f, hd[i].y, eta);
                 if constexpr (kEta2) eta2 = fmaf(f * f, hd[i].z, eta2);

@@ -283,6 +283,10 @@ mppi_status validate(const mppi_config& c) {
     if (c.n_horizon <= half)
         return fail(MPPI_ERR_INVALID_ARG, "Padding (%d) is too large for data length (%d).", half, c.n_horizon);
     if (!(c.lambda_ > 0.0) || !(c.dt > 0.0)) return fail(MPPI_ERR_INVALID_ARG, "lambda and dt must be > 0");
+    // the kernels' exponent scale is fp32(-1 / lambda), and they rely on its sign (a factor exp(coef * (+inf -
+    // finite)) is +0 without a select: mppi_finalize.hip): an infinite or > 1e45 lambda would make it -0
+    if (!((float)(-1.0 / c.lambda_) < 0.0f))
+        return fail(MPPI_ERR_INVALID_ARG, "lambda %g: -1/lambda underflows single precision", c.lambda_);
     if (c.shard_count < 1 || c.shard_rank < 0 || c.shard_rank >= c.shard_count)
         return fail(MPPI_ERR_INVALID_ARG, "shard %d/%d", c.shard_rank, c.shard_count);
     // the Philox counter word of a sample is its global index as 32 bits (k_rollout's kg): past

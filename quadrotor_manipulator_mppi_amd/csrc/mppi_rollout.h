@@ -84,7 +84,19 @@
 #ifndef MPPI_FK_PRETRIG
 #define MPPI_FK_PRETRIG 1
 #endif
-
+// the single-group common kernels (k_rollout_q, k_rollout_s, the single-group k_rollout / k_rollout_ql) load
+// every DevParams scalar the body reads after the staging barrier ahead of the Philox draw and hold it in
+// SGPRs from there (rollout_body kPin): left to the compiler each was an s_load at its use, waited for on
+// the spot -- 10 round trips on the wave's chain at C3, five of them in the block combine.  0 = the
+// prologue's one-dword touches and the loads at their uses
+#ifndef MPPI_ROLL_PIN
+#define MPPI_ROLL_PIN 1
+#endif
+// the block combine's record store bases (header, body) formed ahead of its barrier, and without the
+// vehicle's offset in the one-vehicle kernels (v = 0); 0 = formed between the barrier and the stores
+#ifndef MPPI_COMB_PRE
+#define MPPI_COMB_PRE 1
+#endif
 namespace {
 
 // ------------------------------------------------------------------- Philox
@@ -833,11 +845,37 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     // touch every kernel-argument line the hot phases read (one s_load per 64 B): they
     // land in the scalar cache while the first group's Philox draw runs below
     // (an integer fold: uniform, so SALU -- a float sum took one VALU op per line)
+    // kPin (MPPI_ROLL_PIN; the kernels with the SGPRs for it, kRoom: the single-group common ones -- the
+    // looping and the extended ones stand at 98..106 already, and the fp32 single-group kernels of every
+    // block size, budgeted for 8 waves per SIMD, spilled 4..21 SGPRs with it): instead of the touches, the values
+    // themselves -- every DevParams scalar the body reads after the staging barrier, as wide s_loads here,
+    // made opaque by the empty asms after the draw, so none is re-loaded or sunk to its use.  These
+    // kernels then read nothing of the argument segment after the barrier.
+    constexpr bool kRoom = ONEG && !XC && (B512 || F64);
+    constexpr bool kPin = MPPI_ROLL_PIN && kRoom;
     uint32_t kwarm = 0u;
-    {
+    if constexpr (!kPin) {
         const uint32_t* kp = (const uint32_t*)&pk;
 #pragma unroll
         for (int o = 0; o < (int)(offsetof(DevParams, sigma) / 4); o += 16) kwarm ^= kp[o];
+    }
+    // (HOT(m): member m of the arguments -- the pinned copy, or in a kernel without them the plain read)
+#define HOT(m) (kPin ? s_##m : pk.m)
+    int32_t s_K = 0, s_nb = 0, s_j0 = 0, s_hp = 0, s_C = 0, s_store_traj = 0, s_store_noise = 0;
+    float s_dt = 0.0f, s_dt2 = 0.0f, s_coef = 0.0f, s_w_sp = 0.0f, s_w_so = 0.0f, s_w_tp = 0.0f, s_w_to = 0.0f, s_sdiag[NA];
+    float *s_hdr = nullptr, *s_rdata = nullptr, *s_traj = nullptr, *s_S = nullptr, *s_noise_out = nullptr;
+    const float* s_noise_in = nullptr;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) s_sdiag[a] = kPin ? pk.sdiag[a] : 0.0f;
+    if constexpr (kPin) {
+        s_K = pk.K; s_nb = pk.nb; s_j0 = pk.j0;
+        s_dt = pk.dt; s_dt2 = pk.dt2; s_coef = pk.coef;
+        s_w_sp = pk.w_sp; s_w_so = pk.w_so; s_w_tp = pk.w_tp; s_w_to = pk.w_to;
+        s_hdr = pk.hdr; s_rdata = pk.rdata; s_noise_in = pk.noise_in;
+        if constexpr (!QUIET) {   // the full kernels' own: trajectory planes, costs, stored noise
+            s_hp = pk.hp; s_C = pk.C; s_store_traj = pk.store_traj; s_store_noise = pk.store_noise;
+            s_traj = pk.traj; s_S = pk.S; s_noise_out = pk.noise_out;
+        }
     }
     STAMPW(9);
     // the first group's standard normals overlap the loads above
@@ -866,7 +904,24 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     }
     SECTION("prologue_staging");
     STAMP(10);
-    asm volatile("" :: "s"(kwarm));
+    if constexpr (kPin) {   // one wait for all of them, behind the draw
+        asm volatile("" : "+s"(s_K), "+s"(s_nb), "+s"(s_j0), "+s"(s_dt), "+s"(s_dt2), "+s"(s_coef), "+s"(s_w_sp), "+s"(s_w_so),
+                          "+s"(s_w_tp), "+s"(s_w_to), "+s"(s_hdr), "+s"(s_rdata), "+s"(s_noise_in));
+        if constexpr (!QUIET)
+            asm volatile("" : "+s"(s_hp), "+s"(s_C), "+s"(s_store_traj), "+s"(s_store_noise), "+s"(s_traj), "+s"(s_S),
+                              "+s"(s_noise_out));
+        if constexpr (NA == 3) asm volatile("" : "+s"(s_sdiag[0]), "+s"(s_sdiag[1]), "+s"(s_sdiag[2]));
+        else if constexpr (NA == 7)
+            asm volatile("" : "+s"(s_sdiag[0]), "+s"(s_sdiag[1]), "+s"(s_sdiag[2]), "+s"(s_sdiag[3]), "+s"(s_sdiag[4]),
+                              "+s"(s_sdiag[5]), "+s"(s_sdiag[6]));
+        else {
+            static_assert(NA == 10, "pin the noise scales of a new action width here");
+            asm volatile("" : "+s"(s_sdiag[0]), "+s"(s_sdiag[1]), "+s"(s_sdiag[2]), "+s"(s_sdiag[3]), "+s"(s_sdiag[4]),
+                              "+s"(s_sdiag[5]), "+s"(s_sdiag[6]), "+s"(s_sdiag[7]), "+s"(s_sdiag[8]), "+s"(s_sdiag[9]));
+        }
+    } else {
+        asm volatile("" :: "s"(kwarm));
+    }
 #pragma unroll
     for (int j = 0; j < NU; ++j) {
         const int i = tid + j * nthr;
@@ -902,8 +957,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     STAMPW(8);
     if (!(MPPI_KO & 256)) lds_barrier();
     const VehicleConst& vc = vcv;
-    const float* sdiag = pk.sdiag;
-    const int H = H_arg, K = pk.K;
+    const int H = H_arg, K = HOT(K);
     constexpr int kWs = wave_slot_floats<NA, NCH, LSEG>();
     float* const xw = smem + ((HA + 3) & ~3) + wid * kWs;   // this wave's LDS slot
     // the block's costs, nw * R consecutive k per group, staged in LDS for write-through store runs
@@ -915,10 +969,10 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     // descriptor stays in SGPRs)
     // rows padded to 64 B (hp = H rounded up to 16) and written whole, pad lanes included: the
     // write-through stores then never leave a partial 64 B sector for HBM to merge
-    const int hp = kTraj ? pk.hp : 0;
+    const int hp = kTraj ? HOT(hp) : 0;
     const uint32_t plane_b = (uint32_t)K * (uint32_t)hp * 4u;
-    const __amdgpu_buffer_rsrc_t trs = traj_rsrc(kTraj ? pk.traj + (size_t)v * pk.C * K * hp : nullptr, plane_b,
-                                                 kTraj ? pk.C : 0);
+    const __amdgpu_buffer_rsrc_t trs = traj_rsrc(kTraj ? HOT(traj) + (size_t)v * HOT(C) * K * hp : nullptr, plane_b,
+                                                 kTraj ? HOT(C) : 0);
 
     float acc[NCH][NA];
 #pragma unroll
@@ -937,7 +991,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         // group it of block b: groups b, b + nb, ...  All blocks' groups of one iteration are
         // consecutive, so the grid's concurrent trajectory stores stay in one region of the planes
         // (consecutive groups per block scattered them: whole-body K=65536 85.5 -> 106-110 us)
-        const int g = blockIdx.x + it * p.nb;
+        const int g = blockIdx.x + it * HOT(nb);
         const int k = (g * nw + wid) * R + sub;
         const bool kval = k < K;
         const int kc = kval ? k : K - 1;   // clamped: every load stays in bounds
@@ -951,7 +1005,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             const bool val = kval && t < H;
             const int tc = (t < H) ? t : H - 1;
             if (noise_mode == MPPI_NOISE_INJECTED) {
-                const float* src = p.noise_in + (((size_t)v * K + kc) * H + tc) * NA;
+                const float* src = HOT(noise_in) + (((size_t)v * K + kc) * H + tc) * NA;
 #pragma unroll
                 for (int a = 0; a < NA; ++a) eps[c][a] = src[a];
             } else {
@@ -964,7 +1018,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 }
                 if (!XC || p.sigma_diag) {   // a full Sigma runs in the extended (XC) kernel
 #pragma unroll
-                    for (int a = 0; a < NA; ++a) eps[c][a] = z[a] * sdiag[a];
+                    for (int a = 0; a < NA; ++a) eps[c][a] = z[a] * (kPin ? s_sdiag[a] : pk.sdiag[a]);
                 } else {
 #pragma unroll
                     for (int b = 0; b < NA; ++b) {
@@ -986,8 +1040,8 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 eps[c][a] = val ? eps[c][a] : 0.0f;
                 act[c][a] = val ? ur[a] + eps[c][a] : 0.0f;
             }
-            if (!QUIET && p.store_noise && val) {   // (readback only: written through, st_dev)
-                float* dst = p.noise_out + (((size_t)v * K + k) * H + t) * NA;
+            if (!QUIET && HOT(store_noise) && val) {   // (readback only: written through, st_dev)
+                float* dst = HOT(noise_out) + (((size_t)v * K + k) * H + t) * NA;
 #pragma unroll
                 for (int a = 0; a < NA; ++a) st_dev(dst + a, eps[c][a]);
             }
@@ -1042,7 +1096,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         double posd[NCH][F64 ? NA : 1];
         if constexpr (NCH == 1 && !(MPPI_KO & 1)) {
             float inc[NA];
-            integrate_lds<LSEG, NA>(act[0], xw, lane, p.dt, 0.5f * p.dt2, vc.vel0f, inc);
+            integrate_lds<LSEG, NA>(act[0], xw, lane, HOT(dt), 0.5f * HOT(dt2), vc.vel0f, inc);
 #pragma unroll
             for (int a = 0; a < NA; ++a) {
                 if (!F64) {
@@ -1061,7 +1115,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             for (int c = 0; c < NCH; ++c) {
                 float c1[NA], c2[NA];
 #pragma unroll
-                for (int a = 0; a < NA; ++a) c1[a] = act[c][a] * p.dt;
+                for (int a = 0; a < NA; ++a) c1[a] = act[c][a] * HOT(dt);
                 seg_scan_f32_multi<LSEG, NA>(c1);
 #pragma unroll
                 for (int a = 0; a < NA; ++a) {
@@ -1071,12 +1125,12 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                     }
                     // (0.5 a) dt^2 == a (0.5 dt^2) bit for bit: both are one rounding of the
                     // same product, the halvings being exact
-                    const float h2 = act[c][a] * (0.5f * p.dt2);
+                    const float h2 = act[c][a] * (0.5f * HOT(dt2));
                     const float velf = c1[a] + vc.vel0f[a];
                     float prev = dpp_f32<0x138, 0xF>(velf);     // wave_shr:1
                     if (t0 == 0) prev = (c == 0) ? vc.vel0f[a] : lastv[a];
                     if (NCH > 1) lastv[a] = read_lane_f32(velf, 63);
-                    c2[a] = prev * p.dt + h2;
+                    c2[a] = prev * HOT(dt) + h2;
                 }
                 seg_scan_f32_multi<LSEG, NA>(c2);
 #pragma unroll
@@ -1122,7 +1176,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             const bool term = (t == H - 1);
             float x;
             const uint32_t toff = ((uint32_t)k * (uint32_t)hp + (uint32_t)t) * 4u;   // byte offset in a plane
-            const bool stv = kTraj && p.store_traj && kval && t < hp;   // row incl. its pad (finite values)
+            const bool stv = kTraj && HOT(store_traj) && kval && t < hp;   // row incl. its pad (finite values)
             if (MODEL == MPPI_MODEL_DRONE) {
                 const float dx = posf[c][0] - (TRK ? tgt[c][0] : vc.tpos[0]), dy = posf[c][1] - (TRK ? tgt[c][1] : vc.tpos[1]),
                             dz = posf[c][2] - (TRK ? tgt[c][2] : vc.tpos[2]);
@@ -1155,27 +1209,27 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
 #pragma unroll
                         for (int j = 0; j < 7; ++j) sincos_joint(qang(c, j), sj[j], cj[j]);
                         __builtin_amdgcn_sched_barrier(0);   // (the scheduler would sink each pair to its use)
-                        kin_joint_sc<0>(T, jnt[p.j0 + 0].O, sj[0], cj[0]);
-                        kin_joint_sc<1>(T, jnt[p.j0 + 1].O, sj[1], cj[1]);
-                        kin_joint_sc<2>(T, jnt[p.j0 + 2].O, sj[2], cj[2]);
-                        kin_joint_sc<3>(T, jnt[p.j0 + 3].O, sj[3], cj[3]);
-                        kin_joint_sc<4>(T, jnt[p.j0 + 4].O, sj[4], cj[4]);
-                        kin_joint_sc<5>(T, jnt[p.j0 + 5].O, sj[5], cj[5]);
-                        kin_joint_sc<6>(T, jnt[p.j0 + 6].O, sj[6], cj[6]);
+                        kin_joint_sc<0>(T, jnt[HOT(j0) + 0].O, sj[0], cj[0]);
+                        kin_joint_sc<1>(T, jnt[HOT(j0) + 1].O, sj[1], cj[1]);
+                        kin_joint_sc<2>(T, jnt[HOT(j0) + 2].O, sj[2], cj[2]);
+                        kin_joint_sc<3>(T, jnt[HOT(j0) + 3].O, sj[3], cj[3]);
+                        kin_joint_sc<4>(T, jnt[HOT(j0) + 4].O, sj[4], cj[4]);
+                        kin_joint_sc<5>(T, jnt[HOT(j0) + 5].O, sj[5], cj[5]);
+                        kin_joint_sc<6>(T, jnt[HOT(j0) + 6].O, sj[6], cj[6]);
                     } else {
-                        kin_joint<0>(T, jnt[p.j0 + 0].O, qang(c, 0));
-                        kin_joint<1>(T, jnt[p.j0 + 1].O, qang(c, 1));
-                        kin_joint<2>(T, jnt[p.j0 + 2].O, qang(c, 2));
-                        kin_joint<3>(T, jnt[p.j0 + 3].O, qang(c, 3));
-                        kin_joint<4>(T, jnt[p.j0 + 4].O, qang(c, 4));
-                        kin_joint<5>(T, jnt[p.j0 + 5].O, qang(c, 5));
-                        kin_joint<6>(T, jnt[p.j0 + 6].O, qang(c, 6));
+                        kin_joint<0>(T, jnt[HOT(j0) + 0].O, qang(c, 0));
+                        kin_joint<1>(T, jnt[HOT(j0) + 1].O, qang(c, 1));
+                        kin_joint<2>(T, jnt[HOT(j0) + 2].O, qang(c, 2));
+                        kin_joint<3>(T, jnt[HOT(j0) + 3].O, qang(c, 3));
+                        kin_joint<4>(T, jnt[HOT(j0) + 4].O, qang(c, 4));
+                        kin_joint<5>(T, jnt[HOT(j0) + 5].O, qang(c, 5));
+                        kin_joint<6>(T, jnt[HOT(j0) + 6].O, qang(c, 6));
                     }
                 } else if (!XC) {   // (unreachable: the common kernel is dispatched for Kinova chains only)
                 } else if (p.chain_fast) {   // nq revolute-z joints, q_index = 0..nq-1 in order
 #pragma unroll
                     for (int j = 0; j < NQ; ++j) {
-                        const JointDev& J = jnt[p.j0 + j];
+                        const JointDev& J = jnt[HOT(j0) + j];
                         mul_affine(T, J.O);
                         float s, cc;
                         sincos_joint(qang(c, j), s, cc);
@@ -1189,7 +1243,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                         }
                     }
                 } else {
-                    for (int jn = p.j0; jn < p.nj; ++jn) {
+                    for (int jn = HOT(j0); jn < p.nj; ++jn) {
                         const JointDev& J = jnt[jn];
                         mul_affine(T, J.O);
                         if (J.type == MPPI_JOINT_FIXED) continue;
@@ -1212,8 +1266,8 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 }
                 // the four weights as SGPR values: selecting between two kernel-argument
                 // addresses per lane would otherwise become two vector loads in the FK
-                const float wsp = uniform_f32(p.w_sp), wso = uniform_f32(p.w_so), wtp = uniform_f32(p.w_tp),
-                            wto = uniform_f32(p.w_to);
+                const float wsp = uniform_f32(HOT(w_sp)), wso = uniform_f32(HOT(w_so)), wtp = uniform_f32(HOT(w_tp)),
+                            wto = uniform_f32(HOT(w_to));
                 SECTION("pose_cost");
                 if constexpr (TRK) x = pose_cost_row(T, tgt[c], term ? wtp : wsp, term ? wto : wso);
                 else x = (MPPI_KO & 8) ? T.m[3] + T.m[7] + T.m[11] + T.m[0] : pose_cost(T, vc, term ? wtp : wsp, term ? wto : wso);
@@ -1266,7 +1320,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             const int ks = (g * nw + wid) * R + s;
             const float stage = read_lane_f32(st, s * LSEG + LSEG - 1);
             const float term = read_lane_f32(xt, s * LSEG + ((H - 1) & 63));
-            float S = (MODEL == MPPI_MODEL_DRONE) ? (p.w_sp * stage) + (p.w_tp * term) : stage + term;
+            float S = (MODEL == MPPI_MODEL_DRONE) ? (HOT(w_sp) * stage) + (HOT(w_tp) * term) : stage + term;
             S_seg[s] = (ks < K) ? S : INFINITY;
         }
         if (XC) {   // S += covar, center, jtraj, action, limit
@@ -1289,7 +1343,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
 #pragma unroll
         for (int s = 1; s < R; ++s) S_mine = (sub == s) ? S_seg[s] : S_mine;
         if (!kCosts) { }
-        else if (MPPI_S_PLAIN) { if (kval && t0 == 0) p.S[(size_t)v * K + k] = S_mine; }   // (experiment: round 3's plain store)
+        else if (MPPI_S_PLAIN) { if (kval && t0 == 0) HOT(S)[(size_t)v * K + k] = S_mine; }   // (experiment: round 3's plain store)
         else if (kval && t0 == 0) s_stage[it * cost_run_stride(nw * R) + wid * R + sub] = S_mine;
 
         // ---- online softmin (mppi.py:184-188) over this wave's rollouts (scalar bookkeeping)
@@ -1302,17 +1356,22 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         }
         if (m < INFINITY) {
             const float rn = fminf(rho_w, m);
-            const float f = (rho_w == INFINITY) ? 0.0f : __expf(p.coef * (rho_w - rn));
+            // The selects around this section's exps stay.  This one is free where it counts: in a
+            // single-group kernel rho_w is the constant +inf here and f folds to 0, while a bare
+            // exp(coef * (inf - rn)) would not fold (coef's sign is a run-time fact).  The next guards
+            // S_seg = NaN (a NaN cost is kept out of the min but is still an S_seg: exp(NaN) != 0) along
+            // with k >= K's +inf, and e_mine's guard is the same NaN test.
+            const float f = (rho_w == INFINITY) ? 0.0f : __expf(HOT(coef) * (rho_w - rn));
             float es = 0.0f, e2 = 0.0f;
 #pragma unroll
             for (int s = 0; s < R; ++s) {
-                const float e = (S_seg[s] < INFINITY) ? __expf(p.coef * (S_seg[s] - rn)) : 0.0f;
+                const float e = (S_seg[s] < INFINITY) ? __expf(HOT(coef) * (S_seg[s] - rn)) : 0.0f;
                 es += e;
                 if constexpr (kEta2) e2 += e * e;
             }
             eta_w = eta_w * f + es;
             if constexpr (kEta2) eta2_w = eta2_w * f * f + e2;
-            const float e_mine = (kval && !(S_mine != S_mine)) ? __expf(p.coef * (S_mine - rn)) : 0.0f;
+            const float e_mine = (kval && !(S_mine != S_mine)) ? __expf(HOT(coef) * (S_mine - rn)) : 0.0f;
             if constexpr (kStash) {
                 asm volatile("" ::: "memory");
 #pragma unroll
@@ -1368,6 +1427,32 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     for (int c = 0; c < NCH; ++c)
 #pragma unroll
         for (int a = 0; a < NA; ++a) mine[4 + (c * 64 + lane) * NA + a] = acc[c][a];
+    // The record stores' bases and offsets (MPPI_COMB_PRE): they depend on the block's index, nb, H and NA
+    // alone, so they are formed here, ahead of the barrier, and made opaque -- between the barrier and
+    // the stores, where the block's other waves are already idle, only LDS reads and arithmetic remain.
+    // A one-vehicle kernel has v = 0: no vehicle offset (64-bit scalar multiplies) at all.
+    constexpr bool kPre = MPPI_COMB_PRE && kRoom;   // (the kernels with SGPRs to spare, as kPin)
+    const uint32_t vz = (kPre && VONE) ? 0u : (uint32_t)v;
+    uint32_t hoff, rbase, rstride;
+    float *hdr_u, *rdata_v;
+    auto header_base = [&]() __attribute__((always_inline)) {
+        hoff = (vz * (uint32_t)HOT(nb) + blockIdx.x) * 16u;
+        hdr_u = uniform_ptr(HOT(hdr));
+    };
+    auto body_base = [&]() __attribute__((always_inline)) {
+        rdata_v = uniform_ptr(HOT(rdata) + (size_t)vz * NA * HOT(nb) * H);   // this vehicle's bodies (< 1 GiB)
+        rbase = blockIdx.x * (uint32_t)H;
+        rstride = (uint32_t)HOT(nb) * (uint32_t)H;
+    };
+    if constexpr (kPre) {
+        header_base();
+        body_base();
+        // (uniform, but the compiler may have formed them on the VALU for a vector user: an asm operand must be an SGPR)
+        hoff = __builtin_amdgcn_readfirstlane(hoff);
+        rbase = __builtin_amdgcn_readfirstlane(rbase);
+        rstride = __builtin_amdgcn_readfirstlane(rstride);
+        asm volatile("" : "+s"(hoff), "+s"(hdr_u), "+s"(rdata_v), "+s"(rbase), "+s"(rstride));
+    }
     STAMPW(11);
     lds_barrier();
     STAMP(6);
@@ -1378,9 +1463,9 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         // write-through made the drone C2 step 0.2-0.3 us slower, from the last wave it is
         // within the A/B noise of round 3's plain stores (profiles/r04/ab_cost_store_variants.txt)
         const int nS = nw * R, q = (nS + 3) >> 2;
-        float* const Sv = uniform_ptr(p.S + (size_t)v * K);
+        float* const Sv = uniform_ptr(HOT(S) + (size_t)v * K);
         for (int i = lane; i < iters * q; i += 64) {
-            const int it = i / q, k0 = (blockIdx.x + it * p.nb) * nS;
+            const int it = i / q, k0 = (blockIdx.x + it * HOT(nb)) * nS;
             st_dev_run(Sv, (uint32_t)k0, s_stage + it * cost_run_stride(nS), min(nS, K - k0), i - it * q);
         }
     }
@@ -1403,7 +1488,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         float mine = INFINITY;
 #pragma unroll
         for (int w = 0; w < 8; ++w) mine = ((lane & 7) == w) ? rws[w] : mine;
-        const float f = (mine < INFINITY) ? __expf(p.coef * (mine - rho_b)) : 0.0f;
+        const float f = (mine < INFINITY) ? __expf(HOT(coef) * (mine - rho_b)) : 0.0f;
 #pragma unroll
         for (int w = 0; w < 8; ++w) fw[w] = read_lane_f32(f, w);
     }
@@ -1416,16 +1501,15 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             if constexpr (kEta2) eta2 += fw[w] * fw[w] * wsh[w * wstride + 2];
             nanf = fmaxf(nanf, wsh[w * wstride + 3]);
         }
-        wt_store4(uniform_ptr(p.hdr), ((uint32_t)v * (uint32_t)p.nb + blockIdx.x) * 16u, make_float4(rho_b, eta, eta2, nanf));
+        if constexpr (!kPre) header_base();
+        wt_store4(hdr_u, hoff, make_float4(rho_b, eta, eta2, nanf));
     }
     // record body, dim-major: rdata[v][a][block][t] = sum_w f_w sum_segments acc_w[seg*L + t].
     // (a, t) of element i without an integer division (~25 VALU): a = trunc((i + 1/2) / H)
     // in fp32 is exact, the quotient's error (< 1e-5 for i < A*H <= 2560) being far below
     // the 1/(2H) margin; 32-bit record indices (V*A*nb*H < 2^31, checked at create).
     const float rH = __builtin_amdgcn_rcpf((float)H);   // (1 ulp: far inside the 1/(2H) margin)
-    float* const rdata_v = uniform_ptr(p.rdata + (size_t)v * NA * p.nb * H);   // this vehicle's bodies (< 1 GiB)
-    const uint32_t rbase = blockIdx.x * (uint32_t)H;
-    const uint32_t rstride = (uint32_t)p.nb * (uint32_t)H;
+    if constexpr (!kPre) body_base();
     for (int i = tid; i < ((MPPI_KO & 64) ? 0 : HA); i += nthr) {
         const int a = (int)(((float)i + 0.5f) * rH), t = i - a * H;
         const int c = t >> 6, tl = t & 63;
@@ -1442,6 +1526,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     STAMP(7);
     STAMPRT(14);
     drain_stores();
+#undef HOT
 }
 
 template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG>
