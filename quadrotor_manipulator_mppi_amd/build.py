@@ -46,8 +46,7 @@ SOURCES = [(u, f + (_MAXILP if u in _XI else [])) for u, f in
            ("mppi_host_math.cpp", []), ("mppi_layout.cpp", []), ("mppi_engine.cpp", []), ("mppi_launches.cpp", []), ("mppi_step.cpp", []), ("mppi_debug.cpp", []),
            ("mppi_exchange.cpp", []),
            ("mppi_prewarm.cpp", []), ("mppi_dynamics.cpp", []), ("mppi_aql.cpp", [])]
-HEADERS = ["mppi_dev.h", "mppi_device.h", "mppi_rollout.h", "mppi_quad_step.h", "mppi_elites.h", "mppi_aql.h", "mppi_layout.h", "mppi_engine.h",
-           os.path.join("..", "..", "include", "mppi_hip.h")]
+HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join("..", "..", "include", "mppi_hip.h")]
 # Native dispatch (mppi_aql.cpp) loads each kernel unit's gfx950 code object from next to the
 # library: <library stem>.<unit>.co, built from the same source with the same flags.
 KERNEL_UNITS = [s for s, _ in SOURCES if s.endswith(".hip")]

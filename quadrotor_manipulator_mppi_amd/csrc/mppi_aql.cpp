@@ -472,7 +472,7 @@ int step_prepare(Step* s, const mppi::LaunchDesc& roll, const mppi::LaunchDesc& 
 // Packet fence scopes (0 none, 1 agent, 2 system): rollout acquire, rollout release, finalize
 // acquire, finalize release.  What one kernel of the step reads from the other is written
 // through at device scope and drained before the writing waves end (the rollouts' record
-// bodies, headers and handed-over vehicle constants, mppi_rollout.h drain_stores; the
+// bodies, headers and handed-over vehicle constants, mppi_stores.h drain_stores; the
 // finalize's u_prev), and read with device-scope loads that bypass the L1 (mppi_device.h
 // ld_dev / kAuxDev).  So no packet of a batch needs a release, whose end-of-kernel L2
 // writeback cost up to ~0.8 us per C3 step, and only a submission's FIRST packet acquires

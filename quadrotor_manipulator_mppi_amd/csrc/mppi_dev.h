@@ -129,7 +129,7 @@ struct DevParams {
     // (V, A, ts) words each incremented once per FINAL (FinTail::xovl), and their count per vehicle
     const uint32_t* ovl;
     int32_t ovl_n;
-    int32_t kern;                 // kRollKern* bits (mppi_rollout.h launch_rollout_x)
+    int32_t kern;                 // kRollKern* bits (mppi_rollout_launch.h launch_rollout_x)
 };
 // DevParams::kern bits.  Generic: the kernels as before the fixed-block single-group one
 // (MPPI_GENERIC_KERNELS).  Quiet: this rollout's trajectory planes, costs, stored noise and

@@ -1,5 +1,5 @@
-// mppi_device.h -- device helpers shared by the gfx950 kernels (rollout, finalize).
-// Internal: included only by mppi_rollout.hip / mppi_finalize.hip.
+// mppi_device.h -- device helpers and the launch plumbing (go, pick) shared by the gfx950 kernel units.
+// Internal: included by every .hip unit, directly or through the rollout's headers.
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -30,7 +30,7 @@ __device__ __forceinline__ uint32_t step_of(uint32_t step_arg, int32_t noise_arg
 
 // Loads of what one kernel of a step hands the next (record bodies and headers, u_prev, the
 // handed-over vehicle constants): device scope (sc1), past this CU's L1.  The producers write
-// these through at device scope and drain their stores (mppi_rollout.h drain_stores), so a
+// these through at device scope and drain their stores (mppi_stores.h drain_stores), so a
 // native batch's packets after its first need no acquire fence (mppi_aql.cpp): nothing a
 // kernel reads from its predecessor can come from a stale L1 line.
 template <typename T>
@@ -56,6 +56,9 @@ __device__ __forceinline__ T* uniform_ptr(T* p) {
     const uint64_t a = (uint64_t)p;
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
     return (T*)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ float uniform_f32(float x) {   // wave-uniform value kept in an SGPR
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
 }
 
 // A run of n consecutive floats from LDS (src) to base[off .. off + n), base wave-uniform (off may
@@ -235,6 +238,13 @@ inline int pick(T v, F&& f) {
     // (a left fold: the compiler expands a right fold from its last element, and with it the kernels)
     (void)(... || (v == Alt && ((rc = f(std::integral_constant<decltype(Alt), Alt>{})), true)));
     return rc;
+}
+
+// a rollout launch the caller marked quiet (DevParams::kern) and a quiet kernel can run: device noise,
+// not stored, no overlap wait
+inline bool quiet_launch(const DevParams& p) {
+    return (p.kern & kRollKernQuiet) && (p.noise_mode & 0xFF) != MPPI_NOISE_INJECTED && !p.store_noise &&
+           !(p.noise_mode & kNoiseOverlap);
 }
 
 }  // namespace

@@ -186,7 +186,7 @@ mppi_status mppi_exchange(mppi_engine* e) {
 
 // ---------------------------------------------------------------- peer exchange
 // An upper bound of the finalize's blocks: its grid.x is 8 XCD lanes x dim groups x t-slices
-// (mppi_launch_finalize), and the dim groups are A / MPPI_FIN_XCDS rounded up, at most A (the
+// (mppi_launch_finalize), and the dim groups are A / kFinXcds (mppi_finalize.hip) rounded up, at most A (the
 // kernel indexes the region with its own grid, so any build's fits)
 static size_t fin_blocks(const mppi_engine* e) { return (size_t)8 * e->A * e->fin_ts * e->V; }
 

@@ -33,33 +33,8 @@ constexpr int kMaxRec = 4096;
 #ifndef MPPI_FIN_KO
 #define MPPI_FIN_KO 0
 #endif
-// timing knockout for tools/ A/B experiments (results unsafe): 1 = no commit marks (peer exchange)
-#ifndef MPPI_FIN_NOMARK
-#define MPPI_FIN_NOMARK 0
-#endif
 // XCDs the finalize's blocks run on (8; 4 = the first four, see the block map in k_finalize)
-#ifndef MPPI_FIN_XCDS
-#define MPPI_FIN_XCDS 8
-#endif
-// the quiet role folds no eta^2 (kRoleQuiet): it reaches only the effective sample size of the outputs
-// section, which the quiet role does not have -- u_prev = u_old + SavGol(N / eta), eta = NaN under the
-// records' nan flag, so rho, eta, the nan flag and the bodies stay.  0 = folded as in the other roles
-#ifndef MPPI_FIN_QUIET_LEAN
-#define MPPI_FIN_QUIET_LEAN 1
-#endif
-// a chunk whose rows are all below n (a block-uniform scalar test; the one chunk of the default shapes:
-// n = 128 or 256 records = TR * kNPT) builds no row-valid mask and masks no header; a ragged chunk takes
-// the masked path.  In the roles without the peer exchange only (FINAL, quiet, PACK): with it in the
-// kernels that carry the exchange, eight ranks as eight engines in one process gave a step up
-// (tests/test_gpu_peer.py), so those keep every chunk masked.  0 = every chunk masked
-#ifndef MPPI_FIN_FULL_CHUNK
-#define MPPI_FIN_FULL_CHUNK 1
-#endif
-// the 16 row factors exp(coef * (rho_row - rn)) without their rho_row < inf selects (the argument is at
-// the site in fin_body); 0 = with the selects
-#ifndef MPPI_FIN_EXP_BARE
-#define MPPI_FIN_EXP_BARE 1
-#endif
+constexpr int kFinXcds = 8;
 
 #if defined(MPPI_STAMPS) && !defined(MPPI_TIMELINE)
 #define FSTAMP(i)                                                                    \
@@ -147,8 +122,16 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
     constexpr bool kOut = kAny || ROLE == kRoleFinal || ROLE == kRolePeer;   // the outputs section
     constexpr bool kUpd = kOut || kQuiet;                                     // SavGol and the u_prev update
     constexpr bool kPeer = kAny || ROLE == kRolePeer;                         // the peer exchange
-    constexpr bool kEta2 = !(kQuiet && MPPI_FIN_QUIET_LEAN);                  // eta^2 (the outputs' ess)
-    constexpr bool kFull = MPPI_FIN_FULL_CHUNK && !kPeer;                     // full chunks skip the row masks
+    // The quiet role folds no eta^2: it reaches only the effective sample size of the outputs section,
+    // which the quiet role does not have -- u_prev = u_old + SavGol(N / eta), eta = NaN under the records'
+    // nan flag, so rho, eta, the nan flag and the bodies stay.
+    constexpr bool kEta2 = !kQuiet;
+    // A chunk whose rows are all below n (a block-uniform scalar test; the one chunk of the default shapes:
+    // n = 128 or 256 records = TR * kNPT) builds no row-valid mask and masks no header; a ragged chunk takes
+    // the masked path.  In the roles without the peer exchange only (FINAL, quiet, PACK): with it in the
+    // kernels that carry the exchange, eight ranks as eight engines in one process gave a step up
+    // (tests/test_gpu_peer.py), so those keep every chunk masked.
+    constexpr bool kFull = !kPeer;
     constexpr int NWV = NT / 64;
     constexpr int ROWS = 64 / CW;          // rows per wave
     constexpr int TR = NWV * ROWS;         // rows per block
@@ -166,16 +149,16 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
     const int tsz = GEO::kStatic ? GEO::tsz : (int)(geo & 0xFFu), hf = GEO::kStatic ? GEO::hf : (int)((geo >> 8) & 0xFFu);
     const int ts = GEO::kStatic ? GEO::ts : (int)((geo >> 16) & 0xFFu), A = GEO::kStatic ? GEO::A : (int)(geo >> 24);
     // XCD-aware block map: the dispatcher deals blocks round robin over the 8 XCDs (block b
-    // on XCD b mod 8).  Dim a lives on XCD a mod X (X = MPPI_FIN_XCDS of them), every slice of
+    // on XCD b mod 8).  Dim a lives on XCD a mod X (X = kFinXcds of them), every slice of
     // it too: the slices read the same record lines (one 128 B line holds 32 t of a row),
     // which one L2 then fetches once instead of once per slice.  Blocks b mod 8 >= X and
     // dims >= A exit at once.
-    const int x8 = blockIdx.x & 7, j8 = blockIdx.x >> 3, na = (A + MPPI_FIN_XCDS - 1) / MPPI_FIN_XCDS;
+    const int x8 = blockIdx.x & 7, j8 = blockIdx.x >> 3, na = (A + kFinXcds - 1) / kFinXcds;
     // (na is 1 for A <= 8 and 2 for the whole-body's 10 dims: the general scalar division is
     // ~30 dependent SALU ops at the head of every block)
     const int sl = (na == 1) ? j8 : (na == 2) ? (j8 >> 1) : j8 / na;
-    const int a = x8 + MPPI_FIN_XCDS * (j8 - sl * na), v = blockIdx.y;
-    if (x8 >= MPPI_FIN_XCDS || a >= A) return;
+    const int a = x8 + kFinXcds * (j8 - sl * na), v = blockIdx.y;
+    if (x8 >= kFinXcds || a >= A) return;
     if (MPPI_FIN_KO & 16) { if (tid == 0) p.u_prev[blockIdx.x] = 0.0f; return; }   // timing knockout: launch floor
     FSTAMPRT(13);
     FSTAMP(0);
@@ -401,7 +384,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
             rho_t = rn;
 #pragma unroll
             for (int i = 0; i < kNPT; ++i) {
-                // MPPI_FIN_EXP_BARE: no select.  It only ever caught hd[i].x = +inf (a masked row, a block
+                // The bare exp, no rho_row < inf select.  It only ever caught hd[i].x = +inf (a masked row, a block
                 // without a finite cost): a record's rho is a min that skips NaN costs (they travel in the
                 // nan flag), so it is never NaN.  rn < +inf inside this branch and coef < 0 (mppi_create
                 // refuses a lambda whose fp32(-1 / lambda) is not negative), so for +inf the argument is
@@ -409,8 +392,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
                 // -inf again, or NaN for a row at -inf with and without the select.)  The wave and block
                 // factors below keep theirs: their reference is a min over lanes or waves that is +inf when
                 // none of them saw a finite cost, and inf - inf is NaN.
-                const float f = MPPI_FIN_EXP_BARE ? __expf(coef * (hd[i].x - rn))
-                                                  : (hd[i].x < INFINITY) ? __expf(coef * (hd[i].x - rn)) : 0.0f;
+                const float f = __expf(coef * (hd[i].x - rn));
                 fr[i] = f;
                 eta = fmaf(f, hd[i].y, eta);
                 if constexpr (kEta2) eta2 = fmaf(f * f, hd[i].z, eta2);
@@ -585,7 +567,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
             gu64* dw = (gu64*)xdec + par * nbk;   // this parity's marks, one word per block (no two blocks
                                                   // store to one word: 80 stores into one would serialise)
             if (!late) {
-                if (lane == 0 && !MPPI_FIN_NOMARK)
+                if (lane == 0)
                     __hip_atomic_store(dw + blk, ((unsigned long long)tag << 32) | kDecCommit, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
             } else {
@@ -891,7 +873,7 @@ extern "C" int mppi_launch_finalize(const FinParams* p, void* stream) {
     int nt = 512;
     for (int c : {128, 256})
         if (c * 16 / cw >= p->nrec) { nt = c; break; }
-    const dim3 grid(8 * ((p->A + MPPI_FIN_XCDS - 1) / MPPI_FIN_XCDS) * p->ts, p->V), block(nt);   // XCD-aware map (k_finalize)
+    const dim3 grid(8 * ((p->A + kFinXcds - 1) / kFinXcds) * p->ts, p->V), block(nt);   // XCD-aware map (k_finalize)
     hipStream_t s = (hipStream_t)stream;
     // A role kernel at a table geometry where one applies; else (other geometries, READBACK, the
     // overlap experiment's counters, MPPI_GENERIC_KERNELS) the kernel of every role below.  The quiet

@@ -6,7 +6,7 @@
 // scans over t (seg_scan_f32_multi), wave w standing for chunk w, the carries between the 64-lane
 // chunks handed on through LDS and added in the same order; the measured position is added in the
 // state dtype (fp64 state -> fp64 positions and sin/cos reduction).  Each lane then runs the FK
-// chain and the cost terms of its own step with the rollout's device functions (mppi_rollout.h
+// chain and the cost terms of its own step with the rollout's device functions (mppi_fk.h
 // kin_joint, mul_affine, mul_revolute, mul_prismatic, sincos_joint, pose_cost), and the block sums
 // the steps' costs.
 // The quadrotor's dynamics are sequential in t: one wave per vehicle, its first four lanes stepping
@@ -14,11 +14,13 @@
 //
 // Outputs (engine-owned, plain stores by the lanes): the state channels and EE rows as planes
 // (V, C, H), cost_t (V, H), pos_err (V, H), S (V).
+#include "mppi_fk.h"
+#include "mppi_integrator.h"   // seg_scan_f32_multi
 #include "mppi_quad_step.h"
 
 namespace {
 
-// The chain of one step over the rollout's joint functions (mppi_rollout.h kin_joint, mul_affine,
+// The chain of one step over the rollout's joint functions (mppi_fk.h kin_joint, mul_affine,
 // sincos_joint, mul_revolute, mul_prismatic), chosen at run time as the rollout's extended kernel
 // chooses it (DevParams::chain_fast).  Only this dispatch and the three loops below are the plan's
 // own: lifted out of rollout_body into functions both kernels call, they changed the rollout's

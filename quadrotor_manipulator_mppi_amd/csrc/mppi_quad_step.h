@@ -3,7 +3,7 @@
 // rollout: lane j < 3 owns axis j (position, velocity, Euler angle j, body rate j), lane 3 follows
 // axis 2; quad_perm DPP broadcasts hand each lane the other axes' values.
 #pragma once
-#include "mppi_rollout.h"
+#include "mppi_fk.h"   // sincos_joint
 
 namespace {
 

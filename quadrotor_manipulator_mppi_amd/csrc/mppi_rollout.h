@@ -1,6 +1,8 @@
 // mppi_rollout.h -- gfx950 (CDNA4) rollout kernel of the MPPI control step (the
-// template; instantiated per model in mppi_rollout_{drone,arm,arm32,wb}.hip so the
-// translation units compile in parallel).
+// template; instantiated per model in mppi_rollout_{drone,arm,arm_h32,arm32,wb}.hip so the
+// translation units compile in parallel, through the launchers of mppi_rollout_launch.h).
+// The pieces the body is made of: mppi_noise.h (Philox, Box-Muller), mppi_integrator.h,
+// mppi_fk.h (FK chain, pose cost), mppi_stores.h, mppi_diag.h (knockouts, stamps, sections).
 //
 //   k_rollout   one launch per step: noise draw -> double-integrator rollout ->
 //               FK chain -> per-rollout cost -> online-softmin partials.
@@ -19,715 +21,11 @@
 // wave writes 64 consecutive floats (256 B).
 #pragma once
 #include "mppi_device.h"
-
-// Timing knockouts for tools/ experiments only (MPPI_HIPCC_EXTRA=-DMPPI_KO=n; results are
-// wrong in such a build): 1 drops the integrator scans, 2 the Philox draw, 4 the FK chain,
-// 8 the pose cost, 16 the trajectory stores, 32 Box-Muller, 64 the block record body,
-// 128 the u_prev loads (H*A <= 4 * block threads), 256 the prologue's block barrier (LDS
-// staging read unsynchronised), 512 the end-of-wave store drain (the hand-off unordered),
-// 1024 the cost vector S (its LDS staging and store runs), 2048 block 0's vehicle-constant
-// hand-off (16 + 1024 + 2048 on every launch: the upper bound of the quiet rollout, below).
-#ifndef MPPI_KO
-#define MPPI_KO 0
-#endif
-// waves per SIMD the rollout kernel is register-budgeted for (4: <= 128 VGPRs)
-// NCH == 4 (H in 193..256) is budgeted for 2 waves (<= 256 VGPRs): at 4 it spilled
-// 0.3-2 KB per lane and ran 2.3x slower (arm K=4096 H=256 40.7 -> 28.1 us, whole-body
-// 81.8 -> 35.3 us); NCH == 2 keeps 4 (its 8-96 B spill is cheaper than 3 or 2 waves:
-// arm H=128 13.6 us at 4, 16.7 at 3 and 2; profiles/r02/ab_rollout_occupancy_long_h.txt)
-#ifndef MPPI_ROLL_OCC_NCH2
-#define MPPI_ROLL_OCC_NCH2 4
-#endif
-// the extended (XC) NCH == 2 kernels likewise run best at 2 (whole-body K=8192 H=128 full
-// Sigma 72.1 -> 43.6 us, arm 21.8 -> 19.3); XC NCH == 1 keeps 4 (2 and 3 measured slower;
-// profiles/r02/ab_rollout_occupancy_xc.txt)
-#ifndef MPPI_ROLL_OCC_NCH2_XC
-#define MPPI_ROLL_OCC_NCH2_XC 2
-#endif
-#ifndef MPPI_ROLL_OCC_XC
-#define MPPI_ROLL_OCC_XC 4
-#endif
-#ifndef MPPI_ROLL_OCC
-#define MPPI_ROLL_OCC 4
-#endif
-// wave priority by remaining rollout groups (k_rollout, iters > 1)
-#ifndef MPPI_PRIO
-#define MPPI_PRIO 1
-#endif
-// experiment knob: the costs S as plain per-lane stores (round 3), not staged write-through runs
-#ifndef MPPI_S_PLAIN
-#define MPPI_S_PLAIN 0
-#endif
-// park eps in LDS across the FK and cost (k_rollout, NA >= 7) -- in the extended and the
-// multi-chunk kernels only: the common one-chunk kernels keep it in registers (whole-body 89 -> 96
-// VGPRs, still 5 waves per SIMD, no scratch; same-process A/B, mean of both orders,
-// profiles/r05/eps_stash: C3 -0.10 us per step, whole-body K=8192 -0.22, K=65536 -1.7, V=8 fleet -1.7)
-#ifndef MPPI_EPS_STASH
-#define MPPI_EPS_STASH 1
-#endif
-// experiment knob: after the block-combine barrier the waves with no record element (and
-// not wave 0, the header's) leave at once instead of computing the rescale factors too
-#ifndef MPPI_COMB_EXIT
-#define MPPI_COMB_EXIT 0
-#endif
-// the quiet bodies form no eta^2 (rollout_body QUIET, rollout_quad_body QUIET): the quiet FINAL, the only
-// reader of a quiet step's records, turns eta^2 into nothing (mppi_finalize.hip: the effective sample
-// size of the outputs section alone), so the header's third word is written as 0.  0 = formed as in
-// the full body (same-process A/B, tools/ab_native.py)
-#ifndef MPPI_QUIET_LEAN
-#define MPPI_QUIET_LEAN 1
-#endif
-// the Kinova chain of the C3 kernels (arm, fp64 state, one 32-lane segment; the max-ilp unit): the seven
-// joints' sin / cos (each needs only the integrator's q_j) formed ahead of the chain, seven independent
-// reductions and transcendental pairs, instead of each inside its joint's step, where its result is
-// consumed at once; 0 = inside the steps
-#ifndef MPPI_FK_PRETRIG
-#define MPPI_FK_PRETRIG 1
-#endif
-// the single-group common kernels (k_rollout_q, k_rollout_s, the single-group k_rollout / k_rollout_ql) load
-// every DevParams scalar the body reads after the staging barrier ahead of the Philox draw and hold it in
-// SGPRs from there (rollout_body kPin): left to the compiler each was an s_load at its use, waited for on
-// the spot -- 10 round trips on the wave's chain at C3, five of them in the block combine.  0 = the
-// prologue's one-dword touches and the loads at their uses
-#ifndef MPPI_ROLL_PIN
-#define MPPI_ROLL_PIN 1
-#endif
-// the block combine's record store bases (header, body) formed ahead of its barrier, and without the
-// vehicle's offset in the one-vehicle kernels (v = 0); 0 = formed between the barrier and the stores
-#ifndef MPPI_COMB_PRE
-#define MPPI_COMB_PRE 1
-#endif
-namespace {
-
-// ------------------------------------------------------------------- Philox
-// a ^ b ^ k in one VALU op: gfx950's v_bitop3_b32 with truth table 0x96 (three-input
-// XOR).  The compiler emits two v_xor_b32 for it (there is no v_xor3 on gfx950).
-__device__ __forceinline__ uint32_t xor3_sk(uint32_t a, uint32_t b, uint32_t k) {
-    uint32_t r;
-    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(r) : "v"(a), "v"(b), "s"(k));
-    return r;
-}
-
-__device__ __forceinline__ void philox10(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3,
-                                         uint32_t k0, uint32_t k1) {
-    k0 = __builtin_amdgcn_readfirstlane(k0);   // the key is wave-uniform: keep it scalar
-    k1 = __builtin_amdgcn_readfirstlane(k1);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r) {   // key schedule in place (opaque scalar adds): hoisting 18 round keys
-                   // would spill SGPRs in the rollout kernel
-            asm volatile("s_add_u32 %0, %0, 0x9e3779b9" : "+s"(k0) :: "scc");
-            asm volatile("s_add_u32 %0, %0, 0xbb67ae85" : "+s"(k1) :: "scc");
-        }
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;   // one v_mad_u64_u32 each
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = xor3_sk((uint32_t)(p1 >> 32), c1, k0), n2 = xor3_sk((uint32_t)(p0 >> 32), c3, k1);
-        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
-    }
-}
-
-// s_setprio takes an immediate: min(r, 3) for a wave-uniform r
-__device__ __forceinline__ void set_wave_prio(int r) {
-    if (r >= 3) __builtin_amdgcn_s_setprio(3);
-    else if (r == 2) __builtin_amdgcn_s_setprio(2);
-    else if (r == 1) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-}
-
-__device__ __forceinline__ float uniform_f32(float x) {   // wave-uniform value kept in an SGPR
-    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
-}
-
-// One standard-normal pair per 32-bit Philox word (Box-Muller on the hardware
-// transcendental units: v_log_f32 (log2), v_sqrt_f32, v_sin_f32 / v_cos_f32 with the
-// argument in revolutions).  The radius takes the top 18 bits, u1 = (w>>14 + 1/2) 2^-18,
-// the angle the low 14, u2 = ((w & 0x3fff) + 1/2) 2^-14 (midpoint grids: the radial CDF
-// is off by <= 2^-19, the angle's midpoint rule by O(2^-28); the tail is cut at 5.1
-// sigma, mass 3e-7).  One Philox4x32-10 call thus yields 8 normals: the 7 arm dims take
-// one call and the 10 whole-body dims two (two words per pair took 2 and 3).
-__device__ __forceinline__ void box_muller32(uint32_t w, float& z0, float& z1) {
-    if (MPPI_KO & 32) { z0 = __uint_as_float((w & 0x3FFFFFu) | 0x3F800000u); z1 = z0 - 1.5f; return; }
-    const float u1 = ((float)(w >> 14) + 0.5f) * 3.814697265625e-6f;      // 2^-18
-    const float u2 = ((float)(w & 0x3FFFu) + 0.5f) * 6.103515625e-5f;     // 2^-14
-    // -2 ln u1 lies in [1.3e-6, 26.3] (u1 >= 2^-19): the bare v_sqrt_f32 (1 ulp) needs none
-    // of the denormal scaling and correction steps __builtin_sqrtf adds (~12 VALU)
-    const float r = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));
-    z0 = r * __builtin_amdgcn_cosf(u2);
-    z1 = r * __builtin_amdgcn_sinf(u2);
-}
-
-// Philox2x32-10 (Salmon et al., SC'11; Random123's philox2x32): one 32x32 -> 64 multiply
-// per round instead of two, for the draws that need at most 2 words.
-__device__ __forceinline__ void philox2x10(uint32_t& c0, uint32_t& c1, uint32_t k) {
-    k = __builtin_amdgcn_readfirstlane(k);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r) asm volatile("s_add_u32 %0, %0, 0x9e3779b9" : "+s"(k) :: "scc");
-        const uint64_t p = (uint64_t)0xD256D193u * c0;   // one v_mad_u64_u32
-        const uint32_t n0 = xor3_sk((uint32_t)(p >> 32), c1, k);
-        c1 = (uint32_t)p;
-        c0 = n0;
-    }
-}
-
-// The key of the Philox2x32 draws: the 64-bit seed folded to 32 bits, plus the control
-// step times the golden ratio (a bijection of the step for a fixed seed).
-__host__ __device__ __forceinline__ uint32_t philox2_key(uint32_t seed_lo, uint32_t seed_hi, uint32_t step) {
-    return (seed_lo ^ (seed_hi * 0x85EBCA6Bu)) + step * 0x9E3779B9u;
-}
-// Its second counter word: (veh<<8 | t) ^ (step<<16) (t < 256 = MPPI_MAX_HORIZON).  The step
-// in the counter as well as in the key: two seeds whose folded 32-bit keys meet at some pair
-// of steps still draw different words unless the steps are equal too.  The uniform part
-// (veh<<8 ^ step<<16) is one scalar value, so the lane pays one OR, as before.
-__host__ __device__ __forceinline__ uint32_t philox2_ctr1(uint32_t veh, uint32_t t, uint32_t step) {
-    return t | ((veh << 8) ^ (step << 16));
-}
-
-// Standard normals z[a], a < NA, of sample kg at step t (noise):
-//   * normals 8j .. 8j+7 (j < NA/8): Philox4x32-10 call j, counter (kg, t, veh<<8 | j, step),
-//     key (seed lo, seed hi); word i gives the pair (8j+2i, 8j+2i+1);
-//   * the r = NA mod 8 left over: r <= 4 -> one Philox2x32-10 call, counter
-//     (kg, philox2_ctr1(veh, t, step)), key philox2_key(seed, step), its words giving pairs 8J.., 8J+2..
-//     (J = NA/8); r >= 5 -> Philox4x32-10 call J as above.
-// (the whole-body's 10 dims: one 4x32 call + one 2x32 call, 30 multiplies instead of 40)
-// The draw in two halves (the rollout overlaps them with LDS latency, k_rollout): the
-// Philox words of one (k, t) -- word 4j + i of call j, then the Philox2x32 words -- and the
-// normals Box-Muller makes of them.
-template <int NA>
-constexpr int draw_words() {
-    return 4 * (NA / 8 + ((NA % 8) >= 5 ? 1 : 0)) + (((NA % 8) >= 1 && (NA % 8) <= 4) ? 2 : 0);
-}
-template <int NA>
-__device__ __forceinline__ void draw_philox(uint32_t (&w)[draw_words<NA>()], uint32_t kg, uint32_t t, uint32_t veh,
-                                            uint32_t step, uint32_t s0, uint32_t s1) {
-    constexpr int J = NA / 8, REM = NA % 8;
-    constexpr int N4 = J + (REM >= 5 ? 1 : 0);   // Philox4x32 calls
-#pragma unroll
-    for (int j = 0; j < N4; ++j) {
-        w[4 * j] = kg; w[4 * j + 1] = t; w[4 * j + 2] = (veh << 8) | (uint32_t)j; w[4 * j + 3] = step;
-        if (!(MPPI_KO & 2)) philox10(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3], s0, s1);
-    }
-    if constexpr (REM >= 1 && REM <= 4) {
-        w[4 * N4] = kg; w[4 * N4 + 1] = philox2_ctr1(veh, t, step);
-        if (!(MPPI_KO & 2)) philox2x10(w[4 * N4], w[4 * N4 + 1], philox2_key(s0, s1, step));
-    }
-}
-template <int NA>
-__device__ __forceinline__ void draw_box_muller(const uint32_t (&w)[draw_words<NA>()], float (&z)[NA]) {
-#pragma unroll
-    for (int i = 0; 2 * i < NA; ++i) {   // word i gives normals 2i, 2i + 1 (both layouts above)
-        float a, b;
-        box_muller32(w[i], a, b);
-        z[2 * i] = a;
-        if (2 * i + 1 < NA) z[2 * i + 1] = b;
-    }
-}
-template <int NA>
-__device__ __forceinline__ void draw_normals(float (&z)[NA], uint32_t kg, uint32_t t, uint32_t veh,
-                                             uint32_t step, uint32_t s0, uint32_t s1) {
-    uint32_t w[draw_words<NA>()];
-    draw_philox<NA>(w, kg, t, veh, step, s0, s1);
-    draw_box_muller<NA>(w, z);
-}
-
-// Philox words one (k, t) draw consumes (the raw layout of k_philox / oracle.philox_normals)
-__host__ __device__ constexpr int philox_words(int NA) {
-    return 4 * (NA / 8) + ((NA % 8) == 0 ? 0 : (NA % 8) <= 4 ? 2 : 4);
-}
-
-// ---------------------------------------------------------------- FK helpers
-struct Mat34 { float m[12]; };   // rows 0..2 of a homogeneous transform
-
-// T <- T * [O3 | o]  (O a constant joint origin, uniform across the wave)
-__device__ __forceinline__ void mul_affine(Mat34& T, const float* O) {
-    Mat34 r;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float t0 = T.m[4 * i], t1 = T.m[4 * i + 1], t2 = T.m[4 * i + 2];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) r.m[4 * i + j] = t0 * O[j] + t1 * O[4 + j] + t2 * O[8 + j];
-        r.m[4 * i + 3] = t0 * O[3] + t1 * O[7] + t2 * O[11] + T.m[4 * i + 3];
-    }
-    T = r;
-}
-
-// T <- T * Rot(axis, q) for a revolute joint (Rodrigues, transformation_matrix.py:68-93)
-__device__ __forceinline__ void mul_revolute(Mat34& T, const JointDev& J, float c, float s) {
-    const float omc = 1.0f - c;
-    if (J.axis_z) {   // R = [[c,-s,0],[s,c,0],[0,0,c+(1-c)]]
-        const float r22 = c + omc;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float a0 = T.m[4 * i], a1 = T.m[4 * i + 1];
-            T.m[4 * i] = a0 * c + a1 * s;
-            T.m[4 * i + 1] = a1 * c - a0 * s;
-            T.m[4 * i + 2] = T.m[4 * i + 2] * r22;
-        }
-        return;
-    }
-    const float vx = J.ax[0], vy = J.ax[1], vz = J.ax[2];
-    float R[9];
-    R[0] = c + J.axx[0] * omc; R[1] = J.axx[1] * omc - vz * s; R[2] = J.axx[2] * omc + vy * s;
-    R[3] = J.axx[3] * omc + vz * s; R[4] = c + J.axx[4] * omc; R[5] = J.axx[5] * omc - vx * s;
-    R[6] = J.axx[6] * omc - vy * s; R[7] = J.axx[7] * omc + vx * s; R[8] = c + J.axx[8] * omc;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float a0 = T.m[4 * i], a1 = T.m[4 * i + 1], a2 = T.m[4 * i + 2];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) T.m[4 * i + j] = a0 * R[j] + a1 * R[3 + j] + a2 * R[6 + j];
-    }
-}
-
-// T <- T * Slide(axis * q) (transformation_matrix.py:38-55)
-__device__ __forceinline__ void mul_prismatic(Mat34& T, const JointDev& J, float q) {
-    const float d0 = J.ax[0] * q, d1 = J.ax[1] * q, d2 = J.ax[2] * q;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        T.m[4 * i + 3] += T.m[4 * i] * d0 + T.m[4 * i + 1] * d1 + T.m[4 * i + 2] * d2;
-}
-
-// sin/cos of a joint angle.  The reference evaluates them in the state dtype
-// (fp32, or fp64 when update_joint got float64 arrays, mppi.py:197) and rounds
-// into the fp32 transform (transformation_matrix.py:68-93).  Cody-Waite
-// reduction by pi/2 in fp64 (exact for |q| << 2^20), then minimax polynomials
-// in fp32 on [-pi/4, pi/4] (Cephes sinf/cosf): ~25 VALU ops, <= 2 ulp, no
-// large-argument path (ocml sincosf is ~130 ops with a Payne-Hanek branch).
-__device__ __forceinline__ void sincos_poly(float x, int qd, float& s, float& c) {
-    const float x2 = x * x;
-    float sp = fmaf(x2, -1.9515295891e-4f, 8.3321608736e-3f);
-    sp = fmaf(x2, sp, -1.6666654611e-1f);
-    const float sn = fmaf(x * x2, sp, x);
-    float cp = fmaf(x2, 2.443315711809948e-5f, -1.388731625493765e-3f);
-    cp = fmaf(x2, cp, 4.166664568298827e-2f);
-    const float cs = fmaf(x2 * x2, cp, fmaf(-0.5f, x2, 1.0f));
-    qd &= 3;
-    s = (qd & 1) ? cs : sn;
-    c = (qd & 1) ? sn : cs;
-    if (qd & 2) s = -s;
-    if ((qd + 1) & 2) c = -c;
-}
-
-// Default: reduce the angle to f in [-1/2, 1/2] revolutions in the angle's own precision,
-// then the hardware v_sin_f32 / v_cos_f32 of 2 pi f (2 transcendentals + 4 ops instead of
-// ~20).  Measured on MI355X over random angles in [-3 pi, 3 pi]
-// (tools/microbench7.hip, profiles/r01/sincos_accuracy.txt): max error 1.8e-7 (fp64
-// angle) and 2.6e-7 (fp32 angle) absolute, vs 9e-8 for the polynomials -- 1e2 below the
-// trajectory tolerances.  MPPI_SINCOS_POLY=1 selects the polynomials.
-#ifndef MPPI_SINCOS_POLY
-#define MPPI_SINCOS_POLY 0
-#endif
-__device__ __forceinline__ void sincos_joint(double q, float& s, float& c) {
-    if (MPPI_SINCOS_POLY) {
-        const double n = rint(q * 0.63661977236758134308);
-        double r = fma(-n, 1.5707963267948966192, q);
-        r = fma(-n, 6.123233995736766036e-17, r);
-        sincos_poly((float)r, (int)n, s, c);
-        return;
-    }
-    const double r = q * 0.15915494309189533577;
-    const float f = (float)(r - rint(r));
-    s = __builtin_amdgcn_sinf(f);
-    c = __builtin_amdgcn_cosf(f);
-}
-
-// fp32 state (torch.sin of a float32 tensor): 1/2pi = C_HI + C_LO, the fractional
-// revolution by two FMAs (the polynomial path: a two-constant Cody-Waite reduction by
-// pi/2, the dropped tail 1.8e-15 * n).
-__device__ __forceinline__ void sincos_joint(float q, float& s, float& c) {
-    if (MPPI_SINCOS_POLY) {
-        const float n = __builtin_rintf(q * 0.636619772367581343f);
-        float r = fmaf(-n, 1.5707963705062866f, q);
-        r = fmaf(-n, -4.371138828673793e-08f, r);
-        sincos_poly(r, (int)n, s, c);
-        return;
-    }
-    const float n = __builtin_rintf(q * 0.15915494309189535f);
-    float f = fmaf(q, 0.15915494309189535f, -n);
-    f = fmaf(q, 6.4206382e-09f, f);
-    s = __builtin_amdgcn_sinf(f);
-    c = __builtin_amdgcn_cosf(f);
-}
-
-// One Kinova joint: T <- T * [P | o] * Rz(q), P a signed permutation fixed at
-// compile time (kKinova, mppi_dev.h): the rotation part is register renaming and
-// negation (source modifiers), the translation only its nonzero components.
-// (PRE: the angle's sin and cos are given, else formed here, between the origin and the rotation)
-template <int J, bool PRE, typename QT>
-__device__ __forceinline__ void kin_joint_x(Mat34& T, const float* O, QT q, float s, float c) {
-    constexpr KinOrigin k = kKinova[J];
-    Mat34 r;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float tr = T.m[4 * i + 3];
-        if (k.tmask & 1) tr = fmaf(T.m[4 * i + 0], O[3], tr);
-        if (k.tmask & 2) tr = fmaf(T.m[4 * i + 1], O[7], tr);
-        if (k.tmask & 4) tr = fmaf(T.m[4 * i + 2], O[11], tr);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) r.m[4 * i + j] = (k.s[j] > 0) ? T.m[4 * i + k.p[j]] : -T.m[4 * i + k.p[j]];
-        r.m[4 * i + 3] = tr;
-    }
-    if constexpr (!PRE) sincos_joint(q, s, c);
-    // Rodrigues about z (transformation_matrix.py:68-93).  Its R22 = fl(c + fl(1 - c)) is
-    // 1 or 1 - 2^-24 (a rounding tie of 1 - c for some c < -1/2); the fast path takes 1,
-    // as it takes the origins' pi/2 rotations exactly (<= 6e-8 relative).
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float a0 = r.m[4 * i], a1 = r.m[4 * i + 1];
-        T.m[4 * i] = a0 * c + a1 * s;
-        T.m[4 * i + 1] = a1 * c - a0 * s;
-        T.m[4 * i + 2] = r.m[4 * i + 2];   // R22 = fl(c + fl(1 - c)) taken as 1
-        T.m[4 * i + 3] = r.m[4 * i + 3];
-    }
-}
-template <int J, typename QT>
-__device__ __forceinline__ void kin_joint(Mat34& T, const float* O, QT q) {
-    kin_joint_x<J, false>(T, O, q, 0.0f, 0.0f);
-}
-template <int J>
-__device__ __forceinline__ void kin_joint_sc(Mat34& T, const float* O, const float s, const float c) {
-    kin_joint_x<J, true>(T, O, 0.0f, s, c);
-}
-
-// atan2 with octant reduction and a degree-8 odd minimax polynomial on [0,1]
-// (SLEEF atanf coefficients): ~25 ops, <= 3.5 ulp (ocml atan2f: 45 ops).
-__device__ __forceinline__ float atan2_fast(float y, float x) {
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    float rc = __builtin_amdgcn_rcpf(mx);
-    rc = rc * fmaf(-mx, rc, 2.0f);
-    const float a = (mx > 0.0f) ? mn * rc : 0.0f;
-    const float t = a * a;
-    float u = 0.00282363896258175373077393f;
-    u = fmaf(u, t, -0.0159569028764963150024414f);
-    u = fmaf(u, t, 0.0425049886107444763183594f);
-    u = fmaf(u, t, -0.0748900920152664184570312f);
-    u = fmaf(u, t, 0.106347933411598205566406f);
-    u = fmaf(u, t, -0.142027363181114196777344f);
-    u = fmaf(u, t, 0.199926957488059997558594f);
-    u = fmaf(u, t, -0.333331018686294555664062f);
-    float r = fmaf(a * t, u, a);
-    if (ay > ax) r = 1.57079632679489661923f - r;
-    if (__builtin_signbit(x)) r = 3.14159265358979323846f - r;
-    return __builtin_copysignf(r, y);
-}
-
-// Pose cost of one (k,t): w_pos*||p - p*|| + w_ori*||eulerZYX(R^T R*)||
-// (pose_cost.py:24-63; rotation_conversions.py:277-319; inv(R) of the
-// orthonormal FK rotation taken as R^T).
-__device__ __forceinline__ float pose_cost(const Mat34& T, const VehicleConst& vc, float wp, float wo) {
-    const float dx = T.m[3] - vc.tpos[0], dy = T.m[7] - vc.tpos[1], dz = T.m[11] - vc.tpos[2];
-    const float cp = __builtin_amdgcn_sqrtf(dx * dx + dy * dy + dz * dz);
-    const float* tR = vc.tR;
-    const float r00 = T.m[0] * tR[0] + T.m[4] * tR[3] + T.m[8] * tR[6];
-    const float r10 = T.m[1] * tR[0] + T.m[5] * tR[3] + T.m[9] * tR[6];
-    const float r20 = T.m[2] * tR[0] + T.m[6] * tR[3] + T.m[10] * tR[6];
-    const float r21 = T.m[2] * tR[1] + T.m[6] * tR[4] + T.m[10] * tR[7];
-    const float r22 = T.m[2] * tR[2] + T.m[6] * tR[5] + T.m[10] * tR[8];
-    const float yaw = atan2_fast(r10, r00);
-    const float pitch = asinf(fminf(fmaxf(-r20, -1.0f), 1.0f));
-    const float roll = atan2_fast(r21, r22);
-    const float co = __builtin_amdgcn_sqrtf(yaw * yaw + pitch * pitch + roll * roll);
-    return wp * cp + wo * co;
-}
-
-// The same cost against a target row (p*, R* row-major) the lane holds in registers: the tracking
-// kernels (rollout_body TRK, k_plan).  pose_cost restated, not lifted: the fixed-target kernels'
-// code stays as it is.
-__device__ __forceinline__ float pose_cost_row(const Mat34& T, const float (&g)[12], float wp, float wo) {
-    const float dx = T.m[3] - g[0], dy = T.m[7] - g[1], dz = T.m[11] - g[2];
-    const float cp = __builtin_amdgcn_sqrtf(dx * dx + dy * dy + dz * dz);
-    const float r00 = T.m[0] * g[3] + T.m[4] * g[6] + T.m[8] * g[9];
-    const float r10 = T.m[1] * g[3] + T.m[5] * g[6] + T.m[9] * g[9];
-    const float r20 = T.m[2] * g[3] + T.m[6] * g[6] + T.m[10] * g[9];
-    const float r21 = T.m[2] * g[4] + T.m[6] * g[7] + T.m[10] * g[10];
-    const float r22 = T.m[2] * g[5] + T.m[6] * g[8] + T.m[10] * g[11];
-    const float yaw = atan2_fast(r10, r00);
-    const float pitch = asinf(fminf(fmaxf(-r20, -1.0f), 1.0f));
-    const float roll = atan2_fast(r21, r22);
-    const float co = __builtin_amdgcn_sqrtf(yaw * yaw + pitch * pitch + roll * roll);
-    return wp * cp + wo * co;
-}
-// A row of the target table (V, H, 12: p*(3) then R*(9), 48 B) as three 16 B loads; DRONE reads p* only.
-template <bool POS_ONLY>
-__device__ __forceinline__ void load_target_row(const float* row, float (&g)[12]) {
-    const float4* r4 = reinterpret_cast<const float4*>(row);
-    const float4 a = r4[0];
-    g[0] = a.x; g[1] = a.y; g[2] = a.z; g[3] = a.w;
-    if constexpr (!POS_ONLY) {
-        const float4 b = r4[1], c = r4[2];
-        g[4] = b.x; g[5] = b.y; g[6] = b.z; g[7] = b.w;
-        g[8] = c.x; g[9] = c.y; g[10] = c.z; g[11] = c.w;
-    }
-}
-
-}  // namespace
-
-// =============================================================================
-// k_rollout
-// =============================================================================
-// Diagnostic phase stamps (build with -DMPPI_STAMPS; see tools/stamps.md):
-// s_memtime per wave between scheduling barriers.  Compiled out otherwise.
-#if defined(MPPI_STAMPS) && !defined(MPPI_TIMELINE)
-#define STAMP(i)                                                                                      \
-    do {                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                            \
-        if (pk.stamps && lane == 0) {                                                                 \
-            const size_t w_ = ((size_t)blockIdx.y * p.nb + blockIdx.x) * nw + wid;        \
-            pk.stamps[w_ * kStamps + (i)] = __builtin_amdgcn_s_memtime();                             \
-        }                                                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                            \
-    } while (0)
-// STAMPW first drains this wave's outstanding memory operations, so the stamp
-// after a load phase measures its latency (diagnostic builds perturb overlap).
-#define STAMPW(i)                                                                  \
-    do {                                                                           \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                \
-        STAMP(i);                                                                  \
-    } while (0)
-// STAMPRT: the 100 MHz real-time counter (s_memrealtime), slots 13/14 = wave start/end:
-// wall-clock wave lifetimes, the shader clock (memtime / realtime) and the grid's timeline
-#define STAMPRT(i)                                                                                    \
-    do {                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                            \
-        if (pk.stamps && lane == 0) {                                                                 \
-            const size_t w_ = ((size_t)blockIdx.y * p.nb + blockIdx.x) * nw + wid;        \
-            pk.stamps[w_ * kStamps + (i)] = __builtin_amdgcn_s_memrealtime();                         \
-            if ((i) == 13) /* where the wave ran: XCC_ID (hwreg 20) << 32 | HW_ID (hwreg 4) */        \
-                pk.stamps[w_ * kStamps + 15] = ((unsigned long long)__builtin_amdgcn_s_getreg(0xF814) << 32) | \
-                                               (unsigned)__builtin_amdgcn_s_getreg(0xF804);           \
-        }                                                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                            \
-    } while (0)
-#elif defined(MPPI_STAMPS)   // MPPI_TIMELINE: wall-clock time at wave start / end and at three phase
-                             // boundaries (after the first group's Philox: slot 10, after the
-                             // prologue's barrier: slot 1, after the rollout groups: slot 5), no
-                             // waits: the kernel's own schedule; -DMPPI_TIMELINE_FINE=1 stamps every
-                             // phase boundary (tools/probes.py timeline prints the per-phase medians)
-#ifndef MPPI_TIMELINE_FINE
-#define MPPI_TIMELINE_FINE 0
-#endif
-#define STAMP(i)                                                                                      \
-    do {                                                                                              \
-        if (((i) == 1 || (i) == 5 || (i) == 10 || MPPI_TIMELINE_FINE) && pk.stamps && lane == 0) {    \
-            const size_t w_ = ((size_t)blockIdx.y * p.nb + blockIdx.x) * nw + wid;        \
-            pk.stamps[w_ * kStamps + (i)] = __builtin_amdgcn_s_memrealtime();                         \
-        }                                                                                             \
-    } while (0)
-#define STAMPW(i) STAMP(i)
-#define STAMPRT(i)                                                                                    \
-    do {                                                                                              \
-        if (pk.stamps && lane == 0) {                                                                 \
-            const size_t w_ = ((size_t)blockIdx.y * p.nb + blockIdx.x) * nw + wid;        \
-            pk.stamps[w_ * kStamps + (i)] = __builtin_amdgcn_s_memrealtime();                         \
-            if ((i) == 13)                                                                            \
-                pk.stamps[w_ * kStamps + 15] = ((unsigned long long)__builtin_amdgcn_s_getreg(0xF814) << 32) | \
-                                               (unsigned)__builtin_amdgcn_s_getreg(0xF804);           \
-        }                                                                                             \
-    } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#define STAMPW(i) do { } while (0)
-#define STAMPRT(i) do { } while (0)
-#endif
-
-// Static instruction-mix sections (diagnostic builds, -DMPPI_SECTIONS; tools/isa_sections.py):
-// a named comment in the listing with scheduling barriers on both sides, so no instruction moves
-// across it.  Compiled out otherwise.
-#ifdef MPPI_SECTIONS
-#define SECTION(name)                                        \
-    do {                                                     \
-        __builtin_amdgcn_sched_barrier(0);                   \
-        asm volatile("; MPPI_SECTION " name ::: "memory");   \
-        __builtin_amdgcn_sched_barrier(0);                   \
-    } while (0)
-#else
-#define SECTION(name) do { } while (0)
-#endif
-
-// Inclusive fp32 segment sum (cost reduction; order-insensitive at tolerance).
-template <int L>
-__device__ __forceinline__ float seg_scan_f32(float x) {
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x111, 0xF, 0xF, true));
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x112, 0xF, 0xF, true));
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x114, 0xF, 0xF, true));
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x118, 0xF, 0xF, true));
-    if (L >= 32) x += dpp_f32<0x142, 0xA>(x);
-    if (L >= 64) x += dpp_f32<0x143, 0xC>(x);
-    return x;
-}
-
-
-// Trajectory stores (every wave store instruction writes 256 contiguous bytes).  The
-// planes of one vehicle are one buffer resource (C*K*H*4 < 4 GiB, checked at create):
-// the lane's byte offset sits in one VGPR and the plane offset in an SGPR, so a store
-// costs no 64-bit address arithmetic (a v_lshl_add_u64 per store with flat addresses).
-// MPPI_TRAJ_AUX is the stores' cache-policy field: sc1 (device scope: written through
-// the XCD's L2) | nt (streaming).  With plain stores (0) the L2s hold up to 8 x 4 MB of
-// dirty trajectory lines when the waves finish, and the kernel-end release writes them
-// back serially: same-box A/B (profiles/r02/ab_store_policy.txt) whole-body K=8192 H=64
-// rollout 16.4 -> 12.8 us, arm C3 7.1 -> 6.0 us, V=8 fleet 93.7 -> 81.2 us.
-#ifndef MPPI_TRAJ_AUX
-#define MPPI_TRAJ_AUX 18
-#endif
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t traj_rsrc(float* planes_v, uint32_t plane_b, int C) {
-    return __builtin_amdgcn_make_buffer_rsrc(planes_v, 0, (int)(plane_b * (uint32_t)C), 0x00020000);
-}
-__device__ __forceinline__ void traj_store(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff, float x) {
-    if (MPPI_KO & 16) return;
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x), rs, (int)voff, (int)soff, MPPI_TRAJ_AUX);
-}
-// Write-through stores for the record bodies the finalize reads (full 256 B t-runs): a raw
-// buffer over a wave-uniform base, byte offsets < 4 GiB.  NOT for S: its one-lane 4 B
-// stores become partial-line writes through to memory (whole-body K=8192 rollout
-// 13.7 -> 19.0 us, profiles/r02/ab_store_policy.txt); in L2 they merge into full lines.
-// Record bodies: sc1 (written through) without nt, so the lines stay allocated on their way
-// to memory and the finalize's loads (other XCDs) come back sooner.  Order-balanced A/B vs
-// sc1|nt (profiles/r02/ab_record_store_policy.txt): step pair arm C3 10.40 -> 10.08 us,
-// whole-body K=8192 19.66 -> 18.96 us, quadrotor 12.25 -> 11.99 us.
-#ifndef MPPI_REC_AUX
-#define MPPI_REC_AUX 16
-#endif
-__device__ __forceinline__ void wt_store(float* base_uniform, uint32_t byte_off, float x) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base_uniform, 0, (int)0xFFFFFFFFu, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(x), rs, (int)byte_off, 0, MPPI_REC_AUX);
-}
-// the record header (rho, eta, eta2, nan) of one block, written through like the bodies
-__device__ __forceinline__ void wt_store4(float* base_uniform, uint32_t byte_off, float4 x) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base_uniform, 0, (int)0xFFFFFFFFu, 0x00020000);
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = {__float_as_uint(x.x), __float_as_uint(x.y), __float_as_uint(x.z), __float_as_uint(x.w)};
-    __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)byte_off, 0, MPPI_REC_AUX);
-}
-// The rollout's outputs the finalize reads (record bodies and headers, and the vehicle
-// constants block 0 hands over) are written through at device scope; every wave waits for its
-// stores before it ends.  So they are visible device-wide when the kernel completes, and the
-// native dispatch's rollout packet needs no release fence (the end-of-kernel L2 writeback,
-// ~0.8 us per step at C3; mppi_aql.cpp).
-__device__ __forceinline__ void drain_stores() {
-    if (!(MPPI_KO & 512)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// fp32 inclusive scans of NA independent dims inside L-lane segments, step-major
-// (the DPP wait states of one dim are filled by the others).  Each step is one
-// v_add_f32_dpp: x + dpp(x), where out-of-row sources read 0 (row_shr with
-// bound_ctrl) or rows outside row_mask add 0 (row_bcast), so no zeroing moves.
-template <int L, int NA>
-__device__ __forceinline__ void seg_scan_f32_multi(float (&x)[NA]) {
-    if (MPPI_KO & 1) return;
-#define MPPI_SCAN_STEP(CTRL, RM, BC)                                                    \
-    _Pragma("unroll") for (int a = 0; a < NA; ++a) x[a] += __int_as_float(             \
-        __builtin_amdgcn_update_dpp(0, __float_as_int(x[a]), CTRL, RM, 0xF, BC));
-    MPPI_SCAN_STEP(0x111, 0xF, true)
-    MPPI_SCAN_STEP(0x112, 0xF, true)
-    MPPI_SCAN_STEP(0x114, 0xF, true)
-    MPPI_SCAN_STEP(0x118, 0xF, true)
-#undef MPPI_SCAN_STEP
-    // row_bcast steps as in-place v_add_f32_dpp: rows outside row_mask keep x (the
-    // compiler's DPP combiner would zero a temporary and add instead).  s_nop 1 covers
-    // the VALU-write -> DPP-read hazard the asm hides from the hazard recognizer.
-    if (L >= 32) {
-#pragma unroll
-        for (int a = 0; a < NA; ++a)
-            asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf" : "+v"(x[a]));
-    }
-    if (L >= 64) {
-#pragma unroll
-        for (int a = 0; a < NA; ++a)
-            asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(x[a]));
-    }
-}
-
-// Value of segment s's lane l, as a wave-uniform (scalar) quantity.
-template <int R>
-__device__ __forceinline__ float seg_pick(float x, int sub, int l_in_seg, int L) {
-    float r = read_lane_f32(x, l_in_seg);
-#pragma unroll
-    for (int s = 1; s < R; ++s) r = (sub == s) ? read_lane_f32(x, s * L + l_in_seg) : r;
-    return r;
-}
-
-// ---------------------------------------------------------------------------
-// Integrator in the transposed domain (NCH == 1).  The two cumsums of
-// standard_normal_noise.py:41-48 as DPP scans cost 13 DPP ops per dim and lane
-// (row_shr 1/2/4/8, row_bcast 15/31, wave_shr 1).  Instead the wave writes its
-// controls to its LDS slot (row = lane = (segment, t), pitch P = NA rounded up to odd,
-// so the transposed reads are bank-conflict free) and re-reads them with lane =
-// (series = (segment, dim), chunk of CL consecutive t).  Each lane integrates its chunk
-// sequentially (4 full-rate ops per element), the chunks of a series combine by an
-// affine exclusive scan over CPS consecutive lanes (2 log2 CPS + 2 DPP moves), and the
-// position increments go back through LDS to lane = t.  For a chunk starting at
-// velocity V and position P (relative to q0, q0dot), element i:
-//   dq(i) = P + lp(i) + (i + 1) dt V,   lp(i) = sum_{j <= i} (lv(j) dt + a_j dt^2 / 2),
-//   lv(j) = sum_{m < j} a_m dt;   combine(L then R) : V = V_L + V_R,
-//   P = P_L + P_R + n_R dt V_L  (n_R elements in R).
-// q0dot enters as (t + 1) dt q0dot.  fp32 throughout (the old scans were fp32 too); the
-// increments stay ~1e-10 from the reference's double-accumulated cumsums.
-template <int L, int NA>
-struct IntegGeom {
-    static constexpr int R = 64 / L;
-    static constexpr int S = R * NA;   // series per wave
-    static constexpr int CPS = (S <= 4) ? 16 : (S <= 8) ? 8 : (S <= 16) ? 4 : (S <= 32) ? 2 : 1;
-    static constexpr int CL = L / CPS;   // elements per chunk
-    static constexpr int P = NA | 1;     // LDS row pitch (odd)
-    static_assert(S * CPS <= 64 && CPS <= L, "integrator lane map");
-};
-
-// floats per wave slot in LDS: the block-combine deposit (4 + NCH*64*NA) and, for
-// NCH == 1, the integrator's 64 x P transposition buffer
-template <int NA, int NCH, int L>
-constexpr int wave_slot_floats() {
-    return (NCH == 1 && 64 * IntegGeom<L, NA>::P > 4 + NCH * 64 * NA) ? 64 * IntegGeom<L, NA>::P
-                                                                     : 4 + NCH * 64 * NA;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float row_shr_f32(float x) {   // out-of-row sources read 0
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
-}
-
-// inc[a] (lane = segment*L + t) = q(t) - q0 for the controls act[a] of this lane
-template <int L, int NA>
-__device__ __forceinline__ void integrate_lds(const float (&act)[NA], float* xw, const int lane, const float dt,
-                                              const float dt2h, const float* vel0f, float (&inc)[NA]) {
-    using G = IntegGeom<L, NA>;
-    constexpr int P = G::P, CPS = G::CPS, CL = G::CL, S = G::S;
-#pragma unroll
-    for (int a = 0; a < NA; ++a) xw[lane * P + a] = act[a];
-    wave_lds_handoff();
-    const int sr = lane / CPS, ch = lane & (CPS - 1);
-    const bool on = sr < S;
-    const int seg = sr / NA, a = sr - seg * NA;
-    const int rb = on ? (seg * L + ch * CL) * P + a : 0;
-    float lv = 0.0f, lp = 0.0f, loc[CL];
-#pragma unroll
-    for (int i = 0; i < CL; ++i) {
-        const float x = xw[rb + i * P];
-        lp += fmaf(lv, dt, x * dt2h);
-        lv = fmaf(x, dt, lv);
-        loc[i] = lp;
-    }
-    // inclusive affine scan over the series' chunks (consecutive lanes of one DPP row)
-    float V = lv, Q = lp;
-#define MPPI_ISCAN(D, CTRL)                                                                if (CPS > D) {                                                                             const float vs = row_shr_f32<CTRL>(V), qs = row_shr_f32<CTRL>(Q);                       if (ch >= D) { Q = Q + fmaf((float)(D * CL) * dt, vs, qs); V = V + vs; }            }
-    MPPI_ISCAN(1, 0x111)
-    MPPI_ISCAN(2, 0x112)
-    MPPI_ISCAN(4, 0x114)
-    MPPI_ISCAN(8, 0x118)
-#undef MPPI_ISCAN
-    float Vx = row_shr_f32<0x111>(V), Qx = row_shr_f32<0x111>(Q);   // exclusive: previous chunk's
-    if (ch == 0) { Vx = 0.0f; Qx = 0.0f; }
-    const float v0 = on ? vel0f[a] : 0.0f;
-    const float q0 = fmaf((float)(ch * CL) * dt, v0, Qx);   // chunk start incl. the q0dot drift
-    const float vb = dt * (Vx + v0);
-    wave_lds_handoff();
-    if (on) {
-#pragma unroll
-        for (int i = 0; i < CL; ++i) xw[rb + i * P] = fmaf((float)(i + 1), vb, q0 + loc[i]);
-    }
-    wave_lds_handoff();
-#pragma unroll
-    for (int a2 = 0; a2 < NA; ++a2) inc[a2] = xw[lane * P + a2];
-}
+#include "mppi_diag.h"
+#include "mppi_noise.h"
+#include "mppi_fk.h"
+#include "mppi_stores.h"
+#include "mppi_integrator.h"
 
 // The leading scalar arguments are preloaded into SGPRs at wave launch on gfx950
 // (-mllvm -amdgpu-kernarg-preload-count, build.py): the first group's Philox
@@ -744,9 +42,18 @@ __device__ __forceinline__ void integrate_lds(const float (&act)[NA], float* xw,
 // instead of four, one joint-table load instead of two, and the loops that only a smaller block or
 // a longer warm start needs (the staging tails, the absent waves' fill) and the overlap poll are
 // not in the instantiation.  The launcher picks it when all of that holds (launch_rollout_x).
+//
+// roll_occ: waves per SIMD the rollout kernel is register-budgeted for (4: <= 128 VGPRs).
+// NCH == 4 (H in 193..256) is budgeted for 2 waves (<= 256 VGPRs): at 4 it spilled
+// 0.3-2 KB per lane and ran 2.3x slower (arm K=4096 H=256 40.7 -> 28.1 us, whole-body
+// 81.8 -> 35.3 us); NCH == 2 keeps 4 (its 8-96 B spill is cheaper than 3 or 2 waves:
+// arm H=128 13.6 us at 4, 16.7 at 3 and 2; profiles/r02/ab_rollout_occupancy_long_h.txt).
+// The extended (XC) NCH == 2 kernels likewise run best at 2 (whole-body K=8192 H=128 full
+// Sigma 72.1 -> 43.6 us, arm 21.8 -> 19.3); XC NCH == 1 keeps 4 (2 and 3 measured slower;
+// profiles/r02/ab_rollout_occupancy_xc.txt)
 template <int NCH, bool F64, bool XC, bool ONEG>
 constexpr int roll_occ() {
-    return (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH == 2 ? (XC ? MPPI_ROLL_OCC_NCH2_XC : MPPI_ROLL_OCC_NCH2) : (XC ? MPPI_ROLL_OCC_XC : MPPI_ROLL_OCC));
+    return (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH == 2 ? (XC ? 2 : 4) : 4);
 }
 // QUIET (k_rollout_q, k_rollout_ql): the rollout of a batch's step before its last (mppi_step.cpp
 // quiet_rollout): nothing reads that step's trajectory planes, costs S, stored noise or handed-over
@@ -774,7 +81,10 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     constexpr bool kTraj = !QUIET && !(MPPI_KO & 16);      // trajectory planes
     constexpr bool kCosts = !QUIET && !(MPPI_KO & 1024);   // the cost vector S
     constexpr bool kHand = !QUIET && !(MPPI_KO & 2048);    // block 0's vehicle-constant hand-off
-    constexpr bool kEta2 = !(QUIET && MPPI_QUIET_LEAN);    // eta^2 (the outputs' effective sample size)
+    // eta^2 (the outputs' effective sample size).  The quiet body forms none: the quiet FINAL, the only
+    // reader of a quiet step's records, turns eta^2 into nothing (mppi_finalize.hip: the effective sample
+    // size of the outputs section alone), so the header's third word is written as 0.
+    constexpr bool kEta2 = !QUIET;
     constexpr int R = 64 / LSEG;
     constexpr int QOFF = (MODEL == MPPI_MODEL_WHOLEBODY) ? 3 : 0;
     constexpr int NQ = (MODEL == MPPI_MODEL_DRONE) ? 0 : NA - QOFF;
@@ -845,29 +155,30 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     // touch every kernel-argument line the hot phases read (one s_load per 64 B): they
     // land in the scalar cache while the first group's Philox draw runs below
     // (an integer fold: uniform, so SALU -- a float sum took one VALU op per line)
-    // kPin (MPPI_ROLL_PIN; the kernels with the SGPRs for it, kRoom: the single-group common ones -- the
-    // looping and the extended ones stand at 98..106 already, and the fp32 single-group kernels of every
-    // block size, budgeted for 8 waves per SIMD, spilled 4..21 SGPRs with it): instead of the touches, the values
-    // themselves -- every DevParams scalar the body reads after the staging barrier, as wide s_loads here,
-    // made opaque by the empty asms after the draw, so none is re-loaded or sunk to its use.  These
-    // kernels then read nothing of the argument segment after the barrier.
+    // kRoom (the kernels with the SGPRs for it: the single-group common ones k_rollout_q, k_rollout_s and
+    // the fp64 single-group k_rollout / k_rollout_ql -- the looping and the extended ones stand at 98..106
+    // already, and the fp32 single-group kernels of every block size, budgeted for 8 waves per SIMD,
+    // spilled 4..21 SGPRs with it): instead of the touches, the values themselves -- every DevParams
+    // scalar the body reads after the staging barrier, as wide s_loads here, made opaque by the empty
+    // asms after the draw, so none is re-loaded or sunk to its use.  Left to the compiler each was an
+    // s_load at its use, waited for on the spot: 10 round trips on the wave's chain at C3, five of them
+    // in the block combine.  These kernels then read nothing of the argument segment after the barrier.
     constexpr bool kRoom = ONEG && !XC && (B512 || F64);
-    constexpr bool kPin = MPPI_ROLL_PIN && kRoom;
     uint32_t kwarm = 0u;
-    if constexpr (!kPin) {
+    if constexpr (!kRoom) {
         const uint32_t* kp = (const uint32_t*)&pk;
 #pragma unroll
         for (int o = 0; o < (int)(offsetof(DevParams, sigma) / 4); o += 16) kwarm ^= kp[o];
     }
     // (HOT(m): member m of the arguments -- the pinned copy, or in a kernel without them the plain read)
-#define HOT(m) (kPin ? s_##m : pk.m)
+#define HOT(m) (kRoom ? s_##m : pk.m)
     int32_t s_K = 0, s_nb = 0, s_j0 = 0, s_hp = 0, s_C = 0, s_store_traj = 0, s_store_noise = 0;
     float s_dt = 0.0f, s_dt2 = 0.0f, s_coef = 0.0f, s_w_sp = 0.0f, s_w_so = 0.0f, s_w_tp = 0.0f, s_w_to = 0.0f, s_sdiag[NA];
     float *s_hdr = nullptr, *s_rdata = nullptr, *s_traj = nullptr, *s_S = nullptr, *s_noise_out = nullptr;
     const float* s_noise_in = nullptr;
 #pragma unroll
-    for (int a = 0; a < NA; ++a) s_sdiag[a] = kPin ? pk.sdiag[a] : 0.0f;
-    if constexpr (kPin) {
+    for (int a = 0; a < NA; ++a) s_sdiag[a] = kRoom ? pk.sdiag[a] : 0.0f;
+    if constexpr (kRoom) {
         s_K = pk.K; s_nb = pk.nb; s_j0 = pk.j0;
         s_dt = pk.dt; s_dt2 = pk.dt2; s_coef = pk.coef;
         s_w_sp = pk.w_sp; s_w_so = pk.w_so; s_w_tp = pk.w_tp; s_w_to = pk.w_to;
@@ -904,7 +215,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     }
     SECTION("prologue_staging");
     STAMP(10);
-    if constexpr (kPin) {   // one wait for all of them, behind the draw
+    if constexpr (kRoom) {   // one wait for all of them, behind the draw
         asm volatile("" : "+s"(s_K), "+s"(s_nb), "+s"(s_j0), "+s"(s_dt), "+s"(s_dt2), "+s"(s_coef), "+s"(s_w_sp), "+s"(s_w_so),
                           "+s"(s_w_tp), "+s"(s_w_to), "+s"(s_hdr), "+s"(s_rdata), "+s"(s_noise_in));
         if constexpr (!QUIET)
@@ -1018,7 +329,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 }
                 if (!XC || p.sigma_diag) {   // a full Sigma runs in the extended (XC) kernel
 #pragma unroll
-                    for (int a = 0; a < NA; ++a) eps[c][a] = z[a] * (kPin ? s_sdiag[a] : pk.sdiag[a]);
+                    for (int a = 0; a < NA; ++a) eps[c][a] = z[a] * (kRoom ? s_sdiag[a] : pk.sdiag[a]);
                 } else {
 #pragma unroll
                     for (int b = 0; b < NA; ++b) {
@@ -1150,13 +461,17 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         }
         if (it == 0) STAMP(3);
         SECTION("fk_chain");
-        if (ONEG && MPPI_PRIO) set_wave_prio(2);   // progress priority (single group): see below
+        if (ONEG) set_wave_prio(2);   // progress priority (single group): see below
 
         // eps is read again only by the softmin accumulate at the end of the group: park
         // it in this wave's LDS slot (the integrator is done with it; each lane its own
         // row, so no hand-off) across the FK and cost, the kernel's register peak.  The
         // compiler barriers stop it from forwarding the stored values in registers.
-        constexpr bool kStash = MPPI_EPS_STASH && NA >= 7 && (XC || NCH > 1);
+        // In the extended and the multi-chunk kernels only: the common one-chunk kernels keep it in
+        // registers (whole-body 89 -> 96 VGPRs, still 5 waves per SIMD, no scratch; same-process A/B, mean of
+        // both orders, profiles/r05/eps_stash: C3 -0.10 us per step, whole-body K=8192 -0.22, K=65536 -1.7,
+        // V=8 fleet -1.7)
+        constexpr bool kStash = NA >= 7 && (XC || NCH > 1);
         constexpr int kESP = (NCH == 1) ? IntegGeom<LSEG, NA>::P : NA;   // row pitch (odd for NCH == 1)
         if constexpr (kStash) {
 #pragma unroll
@@ -1204,7 +519,11 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                     T.m[3] += posf[c][QOFF]; T.m[7] += posf[c][QOFF + 1];
                 } else if (NQ == 7 && (!XC || p.chain_fast == 2)) {   // Kinova: origin rotations are signed
                     // permutations (the common kernel runs only this chain; any other goes to XC)
-                    if constexpr (MPPI_FK_PRETRIG && !XC && NCH == 1 && F64 && LSEG == 32 && MODEL == MPPI_MODEL_ARM) {
+                    // the C3 kernels (arm, fp64 state, one 32-lane segment; the max-ilp unit): the seven joints'
+                    // sin / cos (each needs only the integrator's q_j) formed ahead of the chain, seven independent
+                    // reductions and transcendental pairs, instead of each inside its joint's step, where its
+                    // result is consumed at once
+                    if constexpr (!XC && NCH == 1 && F64 && LSEG == 32 && MODEL == MPPI_MODEL_ARM) {
                         float sj[7], cj[7];
 #pragma unroll
                         for (int j = 0; j < 7; ++j) sincos_joint(qang(c, j), sj[j], cj[j]);
@@ -1303,7 +622,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         }
         if (it == 0) STAMP(4);
         SECTION("cost_sum_softmin");
-        if (ONEG && MPPI_PRIO) set_wave_prio(1);
+        if (ONEG) set_wave_prio(1);
 
         // ---- S_k = fl(ws * sum_{t<H-1} x_t) + fl(wt * x_{H-1}) per segment (wave-uniform picks)
         float st = 0.0f;
@@ -1342,9 +661,11 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         float S_mine = S_seg[0];
 #pragma unroll
         for (int s = 1; s < R; ++s) S_mine = (sub == s) ? S_seg[s] : S_mine;
-        if (!kCosts) { }
-        else if (MPPI_S_PLAIN) { if (kval && t0 == 0) HOT(S)[(size_t)v * K + k] = S_mine; }   // (experiment: round 3's plain store)
-        else if (kval && t0 == 0) s_stage[it * cost_run_stride(nw * R) + wid * R + sub] = S_mine;
+        // (s_S named: the group's closure keeps the reference round 3's plain S store gave it.  Without it
+        // the every-knockout build of the whole-body k_rollout_q allocates two VGPRs the other way round;
+        // drop it with the next change to these kernels' instruction streams.)
+        (void)s_S;
+        if (kCosts && kval && t0 == 0) s_stage[it * cost_run_stride(nw * R) + wid * R + sub] = S_mine;
 
         // ---- online softmin (mppi.py:184-188) over this wave's rollouts (scalar bookkeeping)
         float m = INFINITY;
@@ -1390,10 +711,11 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         // Progress priority: 3 until the integrator is done, 2 through FK and cost, 1 for the
         // softmin, 0 in the block combine.  The waves of a SIMD start over ~2 us of launch
         // ramp; under the arbiter's oldest-first order the early ones would finish early and
-        // leave the late ones to run alone -- here a wave that is ahead yields.
-        if (MPPI_PRIO) set_wave_prio(3);
+        // leave the late ones to run alone -- here a wave that is ahead yields.  (Priorities off
+        // measured slower: DESIGN.md §11, profiles/r05/prio/.)
+        set_wave_prio(3);
         group(0);
-        if (MPPI_PRIO) set_wave_prio(0);
+        set_wave_prio(0);
     } else if (iters == 1) {
         group(0);
     } else {
@@ -1402,10 +724,10 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         // last ones run alone, without latency hiding (the grid's tail).  A
         // wave that is ahead drops its priority, the laggards catch up.
         for (int it = 0; it < iters; ++it) {
-            if (MPPI_PRIO) set_wave_prio(iters - 1 - it);
+            set_wave_prio(iters - 1 - it);
             group(it);
         }
-        if (MPPI_PRIO) set_wave_prio(0);
+        set_wave_prio(0);
     }
     STAMP(5);
     SECTION("block_combine_record");
@@ -1427,12 +749,12 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     for (int c = 0; c < NCH; ++c)
 #pragma unroll
         for (int a = 0; a < NA; ++a) mine[4 + (c * 64 + lane) * NA + a] = acc[c][a];
-    // The record stores' bases and offsets (MPPI_COMB_PRE): they depend on the block's index, nb, H and NA
+    // The record stores' bases and offsets: they depend on the block's index, nb, H and NA
     // alone, so they are formed here, ahead of the barrier, and made opaque -- between the barrier and
     // the stores, where the block's other waves are already idle, only LDS reads and arithmetic remain.
     // A one-vehicle kernel has v = 0: no vehicle offset (64-bit scalar multiplies) at all.
-    constexpr bool kPre = MPPI_COMB_PRE && kRoom;   // (the kernels with SGPRs to spare, as kPin)
-    const uint32_t vz = (kPre && VONE) ? 0u : (uint32_t)v;
+    // (In the kernels with SGPRs to spare, kRoom; the others form them between the barrier and the stores.)
+    const uint32_t vz = (kRoom && VONE) ? 0u : (uint32_t)v;
     uint32_t hoff, rbase, rstride;
     float *hdr_u, *rdata_v;
     auto header_base = [&]() __attribute__((always_inline)) {
@@ -1444,7 +766,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         rbase = blockIdx.x * (uint32_t)H;
         rstride = (uint32_t)HOT(nb) * (uint32_t)H;
     };
-    if constexpr (kPre) {
+    if constexpr (kRoom) {
         header_base();
         body_base();
         // (uniform, but the compiler may have formed them on the VALU for a vector user: an asm operand must be an SGPR)
@@ -1456,7 +778,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     STAMPW(11);
     lds_barrier();
     STAMP(6);
-    if (kCosts && !MPPI_S_PLAIN && wid == nw - 1) {
+    if (kCosts && wid == nw - 1) {
         // The block's costs: one write-through run per group (st_dev_run), nw * R consecutive
         // samples each -- one whole 64 B line per group at R = 2 (H <= 32: C2, C3).  Issued by
         // the block's last wave, which has the fewest record stores behind it: from wave 0 the
@@ -1468,10 +790,6 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             const int it = i / q, k0 = (blockIdx.x + it * HOT(nb)) * nS;
             st_dev_run(Sv, (uint32_t)k0, s_stage + it * cost_run_stride(nS), min(nS, K - k0), i - it * q);
         }
-    }
-    if (MPPI_COMB_EXIT && wid != 0 && wid * 64 >= HA) {
-        drain_stores();
-        return;
     }
     // rho_b = the min of the 8 wave slots, which every thread reads for f_w anyway (an LDS
     // atomicMin before the barrier cost a waterfall loop and a ds_min per wave)
@@ -1501,7 +819,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             if constexpr (kEta2) eta2 += fw[w] * fw[w] * wsh[w * wstride + 2];
             nanf = fmaxf(nanf, wsh[w * wstride + 3]);
         }
-        if constexpr (!kPre) header_base();
+        if constexpr (!kRoom) header_base();
         wt_store4(hdr_u, hoff, make_float4(rho_b, eta, eta2, nanf));
     }
     // record body, dim-major: rdata[v][a][block][t] = sum_w f_w sum_segments acc_w[seg*L + t].
@@ -1509,7 +827,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     // in fp32 is exact, the quotient's error (< 1e-5 for i < A*H <= 2560) being far below
     // the 1/(2H) margin; 32-bit record indices (V*A*nb*H < 2^31, checked at create).
     const float rH = __builtin_amdgcn_rcpf((float)H);   // (1 ulp: far inside the 1/(2H) margin)
-    if constexpr (!kPre) body_base();
+    if constexpr (!kRoom) body_base();
     for (int i = tid; i < ((MPPI_KO & 64) ? 0 : HA); i += nthr) {
         const int a = (int)(((float)i + 0.5f) * rH), t = i - a * H;
         const int c = t >> 6, tl = t & 63;
@@ -1593,127 +911,4 @@ __global__ void __launch_bounds__(512, (roll_occ<NCH, F64, true, false>())) k_ro
                                                  const float* __restrict__ ttab, const DevParams pk) {
     rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, true, false, false, false, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg,
                                                                                    H_arg, geo_arg, u_prev, jtab, pk, ttab);
-}
-
-// =============================================================================
-// launchers
-// =============================================================================
-// The geometries the quiet rollout is instantiated for: the kernels the default shapes run (arm and
-// drone at H <= 32, whole-body at H in 33..64; common kernel, one chunk).  Every other launch
-// keeps the full kernel on every step.
-template <int MODEL, int NCH, int LSEG, bool XC>
-constexpr bool quiet_geom() {
-    return !XC && NCH == 1 && LSEG == (MODEL == MPPI_MODEL_WHOLEBODY ? 64 : 32);
-}
-// a launch the caller marked quiet (DevParams::kern) and a quiet kernel can run: device noise, not
-// stored, no overlap wait
-inline bool quiet_launch(const DevParams& p) {
-    return (p.kern & kRollKernQuiet) && (p.noise_mode & 0xFF) != MPPI_NOISE_INJECTED && !p.store_noise &&
-           !(p.noise_mode & kNoiseOverlap);
-}
-
-// The kernel of a launch form: FIXED = the single-group kernel at 512 threads (k_rollout_s, quiet
-// k_rollout_q), else the kernel of every block size (k_rollout, quiet k_rollout_ql).
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG, bool FIXED, bool QUIET>
-constexpr auto rollout_kernel() {
-    if constexpr (FIXED && QUIET) return k_rollout_q<MODEL, NA, NCH, LSEG, F64, VONE, XC>;
-    else if constexpr (FIXED) return k_rollout_s<MODEL, NA, NCH, LSEG, F64, VONE, XC>;
-    else if constexpr (QUIET) return k_rollout_ql<MODEL, NA, NCH, LSEG, F64, VONE, XC, ONEG>;
-    else return k_rollout<MODEL, NA, NCH, LSEG, F64, VONE, XC, ONEG>;
-}
-
-// The launch of all four (FIXED implies ONEG and ignores `threads`).
-// (LDS: warm start, 8 wave slots, and -- not in the quiet forms -- the block's cost runs: iters of
-// them, one per group, each (threads / 64) * R floats padded to 16 B -- sized by the block's own
-// waves, not by 8)
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC, bool ONEG, bool FIXED, bool QUIET>
-inline int launch_rollout_k(const DevParams& p, int threads, hipStream_t s) {
-    static_assert(ONEG || !FIXED, "the fixed-block kernel runs one group");
-    if (FIXED) threads = 512;
-    const int iters = ONEG ? 1 : p.iters;
-    const int s_run = QUIET ? 0 : iters * cost_run_stride((threads / 64) * (64 / LSEG));
-    if (threads <= 0 || threads > 512 || iters < 1 || s_run > kMaxCostRun) return -1;
-    const size_t lds = (size_t)(((p.H * NA + 3) & ~3) + 8 * wave_slot_floats<NA, NCH, LSEG>() + s_run) * sizeof(float);
-    const int32_t geo = threads | (iters << 16);
-    return pick<true, false>(p.V == 1, [&](auto vone) {
-        const auto k = rollout_kernel<MODEL, NA, NCH, LSEG, F64, vone(), XC, ONEG, FIXED, QUIET>();
-        static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
-        return go(k, dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
-                  p.noise_mode, p.H, geo, p.u_prev, p.joints, p);
-    });
-}
-
-// the single-group (ONEG) variant exists for the common kernel at NCH == 1; at 512 threads, without
-// the overlap experiment's wait and unless the engine asks for the kernels as they were
-// (DevParams::kern, MPPI_GENERIC_KERNELS), its fixed-block form
-// A launch marked quiet (quiet_launch) runs the quiet form of whichever of the three it would run,
-// where that form is instantiated (quiet_geom); the full kernel otherwise.
-template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool XC>
-inline int launch_rollout_x(const DevParams& p, int threads, hipStream_t s) {
-    bool quiet = false;
-    if constexpr (quiet_geom<MODEL, NCH, LSEG, XC>()) quiet = quiet_launch(p);
-    if constexpr (!XC && NCH == 1)
-        if (p.iters == 1) {
-            if (threads == 512 && !(p.kern & kRollKernGeneric) && !(p.noise_mode & kNoiseOverlap) && p.H <= LSEG * NCH) {
-                if constexpr (quiet_geom<MODEL, NCH, LSEG, XC>())
-                    if (quiet) return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, true, true, true>(p, threads, s);
-                return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, true, true, false>(p, threads, s);
-            }
-            if constexpr (quiet_geom<MODEL, NCH, LSEG, XC>())
-                if (quiet) return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, true, false, true>(p, threads, s);
-            return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, true, false, false>(p, threads, s);
-        }
-    if constexpr (quiet_geom<MODEL, NCH, LSEG, XC>())
-        if (quiet) return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, false, false, true>(p, threads, s);
-    return launch_rollout_k<MODEL, NA, NCH, LSEG, F64, XC, false, false, false>(p, threads, s);
-}
-
-// The extended (XC) instantiation carries the extra CostManager terms, a full
-// (non-diagonal) Sigma and the generic FK chains: their registers would otherwise be
-// reserved in the common kernel (the full zSigma product alone held the A*A Sigma in
-// VGPRs; with the generic chain loops the whole-body kernel needed 98 VGPRs, without
-// them 87).  The common kernel assumes a diagonal Sigma, no extra terms and the Kinova
-// chain (or no chain: the drone).
-template <int MODEL, int NA, int NCH, int LSEG, bool F64>
-inline int launch_rollout_t(const DevParams& p, int threads, hipStream_t s) {
-    const bool generic_chain = MODEL != MPPI_MODEL_DRONE && !(NA - (MODEL == MPPI_MODEL_WHOLEBODY ? 3 : 0) == 7 &&
-                                                              p.chain_fast == 2);
-    if (p.cost_terms || !p.sigma_diag || generic_chain)
-        return launch_rollout_x<MODEL, NA, NCH, LSEG, F64, true>(p, threads, s);
-    return launch_rollout_x<MODEL, NA, NCH, LSEG, F64, false>(p, threads, s);
-}
-
-template <int MODEL, int NA, bool F64>
-inline int dispatch_geom(const DevParams& p, int threads, hipStream_t s) {
-    if (p.nch == 1 && p.L == 32) return launch_rollout_t<MODEL, NA, 1, 32, F64>(p, threads, s);
-    if (p.nch == 1 && p.L == 64) return launch_rollout_t<MODEL, NA, 1, 64, F64>(p, threads, s);
-    if (p.nch == 2) return launch_rollout_t<MODEL, NA, 2, 64, F64>(p, threads, s);
-    if (p.nch == 4) return launch_rollout_t<MODEL, NA, 4, 64, F64>(p, threads, s);
-    return -1;
-}
-
-// The tracking launch (DevParams::cost_terms & MPPI_COST_TARGET_TRACK): k_rollout_tt on every step
-// of a batch (no quiet form), LDS as the full extended kernel's.
-template <int MODEL, int NA, int NCH, int LSEG, bool F64>
-inline int launch_rollout_tt(const DevParams& p, const float* ttab, int threads, hipStream_t s) {
-    const int iters = p.iters;
-    const int s_run = iters * cost_run_stride((threads / 64) * (64 / LSEG));
-    if (threads <= 0 || threads > 512 || iters < 1 || s_run > kMaxCostRun) return -1;
-    const size_t lds = (size_t)(((p.H * NA + 3) & ~3) + 8 * wave_slot_floats<NA, NCH, LSEG>() + s_run) * sizeof(float);
-    const int32_t geo = threads | (iters << 16);
-    return pick<true, false>(p.V == 1, [&](auto vone) {
-        const auto k = k_rollout_tt<MODEL, NA, NCH, LSEG, F64, vone()>;
-        static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
-        return go(k, dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
-                  p.noise_mode, p.H, geo, p.u_prev, p.joints, ttab, p);
-    });
-}
-
-template <int MODEL, int NA, bool F64>
-inline int dispatch_geom_tt(const DevParams& p, const float* ttab, int threads, hipStream_t s) {
-    if (p.nch == 1 && p.L == 32) return launch_rollout_tt<MODEL, NA, 1, 32, F64>(p, ttab, threads, s);
-    if (p.nch == 1 && p.L == 64) return launch_rollout_tt<MODEL, NA, 1, 64, F64>(p, ttab, threads, s);
-    if (p.nch == 2) return launch_rollout_tt<MODEL, NA, 2, 64, F64>(p, ttab, threads, s);
-    if (p.nch == 4) return launch_rollout_tt<MODEL, NA, 4, 64, F64>(p, ttab, threads, s);
-    return -1;
 }

@@ -1,5 +1,5 @@
 // mppi_rollout_drone.hip -- drone rollout kernels, the rollout dispatcher, and the Philox readback kernel.
-#include "mppi_rollout.h"
+#include "mppi_rollout_launch.h"
 
 // readback of the device noise: draw_normals for every (k, t) of one vehicle, with the
 // raw Philox words in consumption order (philox_words(A) per (k, t))

@@ -40,7 +40,10 @@
 //      block.
 #include <type_traits>
 
+#include "mppi_diag.h"
+#include "mppi_noise.h"
 #include "mppi_quad_step.h"
+#include "mppi_stores.h"
 
 namespace {
 
@@ -253,8 +256,8 @@ __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const 
         for (int w = 0; w < NWD; ++w) { rho = fminf(rho, wred[w][0]); nanf = fmaxf(nanf, wred[w][3]); }
     }
     const float e = (mine && !bad && rho < INFINITY) ? __expf(scoef * (S - rho)) : 0.0f;
-    // (no eta^2 in the quiet body, MPPI_QUIET_LEAN: the quiet FINAL turns it into nothing)
-    constexpr bool kEta2 = !(QUIET && MPPI_QUIET_LEAN);
+    // (no eta^2 in the quiet body: the quiet FINAL turns it into nothing, mppi_rollout.h kEta2)
+    constexpr bool kEta2 = !QUIET;
     float eta = wave_fold_all(e, OpAdd()), eta2 = kEta2 ? wave_fold_all(e * e, OpAdd()) : 0.0f;
     if (j == 0) e_lds[r] = e;
     wave_lds_handoff();
@@ -332,27 +335,36 @@ constexpr auto quad_kernel() {
     else return k_rollout_quad<VONE, LIT, NWD, NT>;
 }
 
-extern "C" int mppi_launch_rollout_quad(const DevParams* p, int threads, void* stream) {
-    (void)threads;   // block size chosen below; p->iters = dynamics waves per block (1 or 4)
+// What the two launches share: the argument check, the LDS size (eps tile and u_prev, plus `extra` floats)
+// and the block -- 512 threads of one dynamics wave (few blocks), 256 of one, or 256 of four.
+// f(vone, lit, NW, NT, lds): the launch of that instantiation (p->iters = dynamics waves per block, 1 or 4).
+template <typename F>
+inline int launch_quad(const DevParams* p, int extra, F&& f) {
     const int nwd = p->iters;
     if (p->H > 64 || p->A != kQA || (nwd != 1 && nwd != kQWaves) || p->nb * kQR * nwd < p->K) return -1;
-    const size_t lds = (size_t)((p->H + 1) * (kQR * nwd * kQA + 1) + (p->H + 1) * kQA) * sizeof(float);
-    hipStream_t s = (hipStream_t)stream;
+    const size_t lds = (size_t)((p->H + 1) * (kQR * nwd * kQA + 1) + (p->H + 1) * kQA + extra) * sizeof(float);
     const bool wide = nwd == 1 && (size_t)p->nb * p->V <= 512;
-    const bool quiet = quiet_launch(*p);   // (a batch's step before its last: mppi_rollout.h)
-    // the block: 512 threads of one dynamics wave (few blocks), 256 of one, or 256 of four
     const int shape = wide ? 0 : nwd == 1 ? 1 : 2;
     return pick<true, false>(p->V == 1, [&](auto vone) {
         return pick<true, false>(p->q_literal_jinv != 0, [&](auto lit) {
             return pick<0, 1, 2>(shape, [&](auto sh) {
                 constexpr int NW = sh() == 2 ? kQWaves : 1, NT = sh() == 0 ? kQThreadsWide : kQThreads;
-                return pick<true, false>(quiet, [&](auto q) {
-                    const auto k = quad_kernel<vone(), lit(), NW, NT, q()>();
-                    static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
-                    return go(k, dim3(p->nb, p->V), dim3(NT), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,
-                              (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, *p);
-                });
+                return f(vone, lit, std::integral_constant<int, NW>{}, std::integral_constant<int, NT>{}, lds);
             });
+        });
+    });
+}
+
+extern "C" int mppi_launch_rollout_quad(const DevParams* p, int threads, void* stream) {
+    (void)threads;   // block size chosen in launch_quad
+    hipStream_t s = (hipStream_t)stream;
+    const bool quiet = quiet_launch(*p);   // (a batch's step before its last: mppi_device.h)
+    return launch_quad(p, 0, [&](auto vone, auto lit, auto nw, auto nt, size_t lds) {
+        return pick<true, false>(quiet, [&](auto q) {
+            const auto k = quad_kernel<vone(), lit(), nw(), nt(), q()>();
+            static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+            return go(k, dim3(p->nb, p->V), dim3(nt()), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,
+                      (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, *p);
         });
     });
 }
@@ -360,21 +372,11 @@ extern "C" int mppi_launch_rollout_quad(const DevParams* p, int threads, void* s
 // The tracking launch: the same block shapes, the full kernel on every step, LDS + the target rows.
 extern "C" int mppi_launch_rollout_quad_tt(const DevParams* p, const float* ttab, int threads, void* stream) {
     (void)threads;
-    const int nwd = p->iters;
-    if (p->H > 64 || p->A != kQA || (nwd != 1 && nwd != kQWaves) || p->nb * kQR * nwd < p->K) return -1;
-    const size_t lds = (size_t)((p->H + 1) * (kQR * nwd * kQA + 1) + (p->H + 1) * kQA + (p->H + 1) * 4) * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    const bool wide = nwd == 1 && (size_t)p->nb * p->V <= 512;
-    const int shape = wide ? 0 : nwd == 1 ? 1 : 2;
-    return pick<true, false>(p->V == 1, [&](auto vone) {
-        return pick<true, false>(p->q_literal_jinv != 0, [&](auto lit) {
-            return pick<0, 1, 2>(shape, [&](auto sh) {
-                constexpr int NW = sh() == 2 ? kQWaves : 1, NT = sh() == 0 ? kQThreadsWide : kQThreads;
-                const auto k = k_rollout_quad_tt<vone(), lit(), NW, NT>;
-                static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
-                return go(k, dim3(p->nb, p->V), dim3(NT), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,
-                          (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, ttab, *p);
-            });
-        });
+    return launch_quad(p, (p->H + 1) * 4, [&](auto vone, auto lit, auto nw, auto nt, size_t lds) {
+        const auto k = k_rollout_quad_tt<vone(), lit(), nw(), nt()>;
+        static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+        return go(k, dim3(p->nb, p->V), dim3(nt()), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,
+                  (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, ttab, *p);
     });
 }

@@ -1,5 +1,5 @@
 """The kernels' exponent scale is fp32(-1 / lambda) and the finalize's row factors rely on its sign
-(csrc/mppi_finalize.hip, MPPI_FIN_EXP_BARE: exp(coef * (+inf - finite)) must be +0 without a select), so
+(csrc/mppi_finalize.hip fin_body, the bare row factors: exp(coef * (+inf - finite)) must be +0 without a select), so
 configuration validation refuses a lambda whose scale is not negative in single precision: infinite,
 or so large that -1 / lambda underflows to -0.  Checked through the pure layout stage, without a GPU."""
 import os

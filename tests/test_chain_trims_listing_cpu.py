@@ -1,6 +1,6 @@
 """The C3 rollout kernels (arm, fp64 state, L = 32: k_rollout_q and k_rollout_s) hold every
 kernel-argument scalar they read after the staging barrier in SGPRs from the prologue
-(csrc/mppi_rollout.h rollout_body, kPin).  Compiled here with build.py's flags for the unit to a
+(csrc/mppi_rollout.h rollout_body, kRoom).  Compiled here with build.py's flags for the unit to a
 listing: after the first s_barrier neither kernel has a scalar load (everything else they read there is
 LDS or vector memory, so any s_load would be one from the argument segment), neither uses scratch or
 spills an SGPR, and both stay inside their register budgets: 102 SGPRs; 72 VGPRs for the quiet kernel

@@ -5,7 +5,7 @@ of ``k_rollout`` / ``k_rollout_quad`` (``store_noise``) is held, element by elem
 ``eps = draw_normals(k_global, t, fleet-wide vehicle, step, seed) Sigma`` as ``O.philox_normals``
 restates it in float64 (tests/noise_stream.py: ``expected_eps`` / ``assert_stream``, the tolerance
 of ``test_device_philox_matches_restatement`` carried through Sigma).  The five counter arguments
-are computed by the kernels themselves (csrc/mppi_rollout.h, mppi_rollout_quad.hip, mppi_device.h):
+are computed by the kernels themselves (csrc/mppi_noise.h, mppi_rollout.h, mppi_rollout_quad.hip, mppi_device.h):
 
     kg   = k_off + (g * nw + wid) * R + sub,  g = blockIdx.x + it * nb     (looping kernel)
     t    = t0 + 64 c                                                         (H > 64)

@@ -1,5 +1,5 @@
 """Per-section static instruction mix of one kernel in a hipcc -S listing of a -DMPPI_SECTIONS
-build (tools/, not shipped): the rollout's SECTION() markers (mppi_rollout.h) split the kernel,
+build (tools/, not shipped): the rollout's SECTION() markers (mppi_diag.h; placed in mppi_rollout.h) split the kernel,
 and each section is classified with tools/isa_count.py (VALU by issue class, SALU, LDS, VMEM).
 
     python tools/isa_sections.py listing.s <kernel-name-substring>

@@ -1,26 +1,43 @@
-// Accuracy of the hardware v_sin_f32 / v_cos_f32 (argument in revolutions) for joint
-// angles, against double-precision sin/cos, next to the kernel's Cody-Waite + minimax
-// sincos_joint (fp32 and fp64 reduction).  tools/ only:
+// Accuracy of the kernels' sincos_joint (the hardware v_sin_f32 / v_cos_f32, argument in
+// revolutions; fp32 and fp64 reduction) for joint angles, against double-precision sin/cos, next
+// to a Cody-Waite + minimax polynomial (fp32 and fp64 reduction).  tools/ only:
 //   hipcc --offload-arch=gfx950 -O3 -I include -o /tmp/mb7 tools/microbench7.hip && /tmp/mb7
 #include <cmath>
 #include <cstdio>
 #include <vector>
-#include "../quadrotor_manipulator_mppi_amd/csrc/mppi_rollout.h"
+#include "../quadrotor_manipulator_mppi_amd/csrc/mppi_fk.h"
 
-// candidate: reduce to f in [-1/2, 1/2] revolutions in the angle's own precision, then
-// the hardware sin/cos of 2 pi f
-__device__ __forceinline__ void sincos_hw(double q, float& s, float& c) {
-    const double r = q * 0.15915494309189533577;
-    const float f = (float)(r - rint(r));
-    s = __builtin_amdgcn_sinf(f);
-    c = __builtin_amdgcn_cosf(f);
+// The polynomial alternative the kernels used before the hardware path (here only, as the yardstick):
+// Cody-Waite reduction by pi/2 (exact for |q| << 2^20), then minimax polynomials in fp32 on
+// [-pi/4, pi/4] (Cephes sinf/cosf): ~25 VALU ops, <= 2 ulp, no large-argument path (ocml sincosf
+// is ~130 ops with a Payne-Hanek branch).
+__device__ __forceinline__ void sincos_poly(float x, int qd, float& s, float& c) {
+    const float x2 = x * x;
+    float sp = fmaf(x2, -1.9515295891e-4f, 8.3321608736e-3f);
+    sp = fmaf(x2, sp, -1.6666654611e-1f);
+    const float sn = fmaf(x * x2, sp, x);
+    float cp = fmaf(x2, 2.443315711809948e-5f, -1.388731625493765e-3f);
+    cp = fmaf(x2, cp, 4.166664568298827e-2f);
+    const float cs = fmaf(x2 * x2, cp, fmaf(-0.5f, x2, 1.0f));
+    qd &= 3;
+    s = (qd & 1) ? cs : sn;
+    c = (qd & 1) ? sn : cs;
+    if (qd & 2) s = -s;
+    if ((qd + 1) & 2) c = -c;
 }
-__device__ __forceinline__ void sincos_hw(float q, float& s, float& c) {
-    const float n = __builtin_rintf(q * 0.15915494309189535f);
-    float f = fmaf(q, 0.15915494309189535f, -n);            // 1/2pi = C_HI + C_LO
-    f = fmaf(q, 6.4206382e-09f, f);
-    s = __builtin_amdgcn_sinf(f);
-    c = __builtin_amdgcn_cosf(f);
+// fp64 angle: the reduction in fp64
+__device__ __forceinline__ void sincos_poly_joint(double q, float& s, float& c) {
+    const double n = rint(q * 0.63661977236758134308);
+    double r = fma(-n, 1.5707963267948966192, q);
+    r = fma(-n, 6.123233995736766036e-17, r);
+    sincos_poly((float)r, (int)n, s, c);
+}
+// fp32 angle: a two-constant reduction, the dropped tail 1.8e-15 * n
+__device__ __forceinline__ void sincos_poly_joint(float q, float& s, float& c) {
+    const float n = __builtin_rintf(q * 0.636619772367581343f);
+    float r = fmaf(-n, 1.5707963705062866f, q);
+    r = fmaf(-n, -4.371138828673793e-08f, r);
+    sincos_poly(r, (int)n, s, c);
 }
 
 __global__ void k_sc(const float* xf, const double* xd, int n, float* out) {
@@ -28,13 +45,13 @@ __global__ void k_sc(const float* xf, const double* xd, int n, float* out) {
     if (i >= n) return;
     const float x = xf[i];
     float s, c;
-    sincos_hw(x, s, c);
+    sincos_joint(x, s, c);   // the kernels' own (mppi_fk.h): reduction to revolutions, hardware sin / cos
     out[8 * i + 0] = s; out[8 * i + 1] = c;
-    sincos_hw(xd[i], s, c);
-    out[8 * i + 2] = s; out[8 * i + 3] = c;
-    sincos_joint(x, s, c);
-    out[8 * i + 4] = s; out[8 * i + 5] = c;
     sincos_joint(xd[i], s, c);
+    out[8 * i + 2] = s; out[8 * i + 3] = c;
+    sincos_poly_joint(x, s, c);
+    out[8 * i + 4] = s; out[8 * i + 5] = c;
+    sincos_poly_joint(xd[i], s, c);
     out[8 * i + 6] = s; out[8 * i + 7] = c;
 }
 
