@@ -447,6 +447,51 @@ mppi_status mppi_get_weighted_noise(mppi_engine* e, float* raw, float* smoothed)
  * the control step: nothing the step reads or writes is touched. */
 mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos_err, float* S);
 
+/* ---- Obstacle avoidance: sphere scenes in the rollout cost (the project's own term; the reference
+ * has no counterpart).  ARM, WHOLEBODY and DRONE; a QUADROTOR config with a scene is
+ * MPPI_ERR_INVALID_ARG.
+ *
+ * Body spheres are the robot's geometry, engine-wide and fixed at creation (mppi_scene): sphere b
+ * has a frame f, an offset o in that frame and a radius r_b > 0.  f indexes cfg.joints: frame f is
+ * the world transform after joints 0..f of the chain, fixed joints included (forward_kinematics'
+ * tf_fk after joint f); f = -1 is the base transform alone, T(base xyz, quat) -- for WHOLEBODY its
+ * translation includes p_drone(k, t).  The world centre is T_f (o, 1).  DRONE has no chain: f = -1,
+ * the centre p(k, t) + o in world axes.
+ * Obstacles are per vehicle (mppi_set_obstacles), at most MPPI_MAX_OBSTACLES spheres: centre c
+ * (world, m), radius r_o > 0, velocity vel (m/s).  At horizon row t (the state after t + 1
+ * integration steps, as in mppi_set_target_trajectory) the centre is c + vel (t + 1) dt.  A batch
+ * (mppi_run_steps(n)) uses the same set, unadvanced, for all n steps.
+ * With d_bo the centre distance and g_bo = d_bo - r_b - r_o the clearance,
+ *   x_obs(k,t) = w_obs sum_{b,o} max(0, margin - g_bo) + penalty [min_{b,o} g_bo < 0]
+ *   S_k += sum_{t<H} x_obs(k,t)          (no discount; after the CostManager terms)
+ * and the per-sample clearance clr_k = min_{t,b,o} g_bo (+inf with no obstacle or no body sphere).
+ * Project constants (mppi_scene_default): w_obs = 100, margin = 0.05 m, penalty = 1e4; the default
+ * body spheres are placeholders for the user's collision model: 0.05 m at each arm joint frame
+ * origin, 0.30 m on frame -1 for WHOLEBODY and DRONE. */
+#define MPPI_MAX_OBSTACLES 16
+#define MPPI_MAX_BODY_SPHERES 16
+typedef struct { int32_t frame; float offset[3]; float radius; } mppi_body_sphere;
+typedef struct { int32_t n_body; mppi_body_sphere body[MPPI_MAX_BODY_SPHERES];
+                 float w_obs, margin, penalty; } mppi_scene;
+/* The project's default spheres and weights for the config's model and chain. */
+void mppi_scene_default(mppi_scene* scene, const mppi_config* cfg);
+/* mppi_create with a scene (NULL scene: mppi_create).  MPPI_ERR_INVALID_ARG: QUADROTOR, n_body
+ * outside 0..16, a frame outside [-1, n_joints) (DRONE: other than -1), a non-finite value, a
+ * radius <= 0, a negative weight.  Runs the scene kernels (k_rollout_ob; no quiet form). */
+mppi_status mppi_create_scene(const mppi_config* cfg, const mppi_scene* scene, mppi_engine** out);
+/* The obstacles of one vehicle: n in 0..16 (0 clears, the state after creation), center_n3 (n,3),
+ * radius_n (n), vel_n3 (n,3) or NULL = static.  MPPI_ERR_STATE on an engine created without a scene;
+ * MPPI_ERR_INVALID_ARG for n or the vehicle out of range, a non-finite value or a radius <= 0.  The
+ * rows are copied to the engine's staging memory (the caller's arrays are free on return) and
+ * uploaded on the engine's stream, ordered before the next step on either dispatch path. */
+mppi_status mppi_set_obstacles(mppi_engine* e, int32_t vehicle, int32_t n, const float* center_n3,
+                               const float* radius_n, const float* vel_n3);
+/* clr (V,K): the per-sample clearances of the last rollout, valid as mppi_get_costs is. */
+mppi_status mppi_get_clearances(mppi_engine* e, float* clr_vk);
+/* clr (V,H): min_{b,o} g_bo at step t of the nominal plan (mppi_get_plan's rollout, whose cost_t
+ * and S include the obstacle term on a scene engine). */
+mppi_status mppi_get_plan_clearance(mppi_engine* e, float* clr_vh);
+
 #define MPPI_MAX_ELITES 64
 /* The n lowest-cost samples of the last rollout of every vehicle, best first (synchronous).
  *   idx  (V,n) int32   sample index within this engine's K (a shard: local; global = shard_rank*K + idx)

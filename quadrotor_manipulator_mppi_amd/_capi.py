@@ -25,6 +25,8 @@ COST_TARGET_TRACK = 32   # the pose target moves along the horizon (mppi_set_tar
 ABI_VERSION = 10
 MAX_PEERS = 8
 MAX_ELITES = 64
+MAX_OBSTACLES = 16
+MAX_BODY_SPHERES = 16
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 64
 
@@ -56,6 +58,15 @@ class Config(C.Structure):
                 ("quad_mass", C.c_float), ("quad_inertia", C.c_float * 3), ("quad_kd", C.c_float),
                 ("quad_gravity", C.c_float), ("quad_literal_jinv", C.c_int32),
                 ("vehicle_offset", C.c_int32)]
+
+
+class BodySphere(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("offset", C.c_float * 3), ("radius", C.c_float)]
+
+
+class Scene(C.Structure):
+    _fields_ = [("n_body", C.c_int32), ("body", BodySphere * MAX_BODY_SPHERES),
+                ("w_obs", C.c_float), ("margin", C.c_float), ("penalty", C.c_float)]
 
 
 class Link(C.Structure):
@@ -131,6 +142,11 @@ PROTOTYPES = {
     "mppi_get_weighted_noise": (_ST, [_P, _F, _F]),
     "mppi_get_plan": (_ST, [_P, _F, _F, _F, _F]),
     "mppi_get_elites": (_ST, [_P, C.c_int32, _I32, _F, _F, _F]),
+    "mppi_scene_default": (None, [C.POINTER(Scene), _CFG]),
+    "mppi_create_scene": (_ST, [_CFG, C.POINTER(Scene), C.POINTER(_P)]),
+    "mppi_set_obstacles": (_ST, [_P, C.c_int32, C.c_int32, _F, _F, _F]),
+    "mppi_get_clearances": (_ST, [_P, _F]),
+    "mppi_get_plan_clearance": (_ST, [_P, _F]),
     "mppi_enable_timing": (_ST, [_P, C.c_int32]),
     "mppi_get_timing": (_ST, [_P, _D, _D, _I64, _I64]),
     "mppi_kernel_timing": (_ST, [_P, C.c_int32, _D, _D]),
@@ -156,6 +172,10 @@ PROTOTYPES = {
 # diagnostics entry points that are not in the header (csrc/mppi_debug.cpp); their users bind them
 DEBUG_PROTOTYPES = {
     "mppi_debug_step_launches": (C.c_int32, [_CFG, _I32, C.c_char_p, C.c_int32]),
+    "mppi_debug_scene_step_launches": (C.c_int32, [_CFG, C.POINTER(Scene), _I32, C.c_char_p, C.c_int32]),
+    "mppi_debug_scene_rollout_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_char_p, C.c_int32]),
+    "mppi_debug_scene_layout": (C.c_int32, [_CFG, C.POINTER(Scene), _F, _I32]),
+    "mppi_debug_obstacles": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, _F, _F, _F, _F]),
 }
 
 _lib = None

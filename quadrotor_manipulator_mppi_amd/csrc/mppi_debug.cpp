@@ -22,9 +22,9 @@ std::string fin_symbol(const FinParams& f, LaunchDesc* desc) {
     if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
-std::string roll_symbol(const DevParams& p, int threads, LaunchDesc* desc, const float* ttab) {
+std::string roll_symbol(const DevParams& p, int threads, LaunchDesc* desc, const float* ttab, float* scene) {
     LaunchDesc d{};
-    const int rc = describe(p, threads, &d, ttab);
+    const int rc = describe(p, threads, &d, ttab, scene);
     if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
@@ -232,7 +232,7 @@ int32_t mppi_debug_queue_ring(mppi_engine* e) {
 // lds <bytes> args <bytes> fnv <FNV-1a 64 of the argument bytes>" -- for a step before the last
 // (n > 1) and for the last step.  A path the engine would not take is refused (mppi_last_error says
 // why).  tests/test_capi_step_launches_cpu.py.
-int32_t mppi_debug_step_launches(const mppi_config* cfg, const int32_t* sw, char* buf, int32_t len) {
+static int32_t step_launches(const mppi_config* cfg, const int32_t* sw, char* buf, int32_t len, const mppi_scene* scene) {
     if (!cfg || !sw || !buf || len <= 0 || sw[0] < 0 || sw[0] > 3 || sw[1] < 1)
         return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_step_launches: bad arguments");
     mppi_status st = validate(*cfg);
@@ -258,6 +258,12 @@ int32_t mppi_debug_step_launches(const mppi_config* cfg, const int32_t* sw, char
     }
     if (sharded(e)) e->d_exchange = (float*)stand_in(0x100000);
     if (e->cfg.cost_terms & MPPI_COST_TARGET_TRACK) e->d_ttab = (float*)stand_in(0x6000);
+    if (scene) {   // a scene engine's (mppi_create_scene): its buffer and, always, a target table
+        if ((st = scene_validate(e->cfg, *scene)) != MPPI_OK) return st;
+        e->has_scene = true;
+        e->d_ttab = (float*)stand_in(0x6000);
+        e->d_scene = (float*)stand_in(0x7000);
+    }
     std::vector<VehicleConst> vc((size_t)e->V);
     e->h_vc = vc.data();
     e->tpos.assign((size_t)3 * e->V, 0.0f);
@@ -295,7 +301,7 @@ int32_t mppi_debug_step_launches(const mppi_config* cfg, const int32_t* sw, char
         const StepPath sp = path < 2 ? StepPath::Hip : path == 2 ? StepPath::Batch : StepPath::Call;
         DevParams p = rollout_params(e, sp, noise, !last);
         if (sp == StepPath::Hip) p.step_ctr = (uint32_t)i;   // (rollout_impl: the launch's own)
-        report(last, "rollout", describe(p, e->threads, &d, e->d_ttab), d);
+        report(last, "rollout", describe(p, e->threads, &d, e->d_ttab, e->d_scene), d);
         if (sp == StepPath::Hip && sharded(e)) {
             const FinParams f = finalize_params(e, FinKind::Pack);
             report(last, "pack", describe(f, &d), d);
@@ -311,6 +317,37 @@ int32_t mppi_debug_step_launches(const mppi_config* cfg, const int32_t* sw, char
     if ((int)all.size() >= len) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_step_launches: %zu bytes needed", all.size() + 1);
     snprintf(buf, (size_t)len, "%s", all.c_str());
     return MPPI_OK;
+}
+int32_t mppi_debug_step_launches(const mppi_config* cfg, const int32_t* sw, char* buf, int32_t len) {
+    return step_launches(cfg, sw, buf, len, nullptr);
+}
+// Likewise for an engine of mppi_create_scene(cfg, scene) (a null scene: mppi_debug_step_launches).
+// tests/test_capi_obstacles_cpu.py.
+int32_t mppi_debug_scene_step_launches(const mppi_config* cfg, const mppi_scene* scene, const int32_t* sw, char* buf,
+                                       int32_t len) {
+    return step_launches(cfg, sw, buf, len, scene);
+}
+
+// mppi_debug_rollout_kernels for a scene engine's launches (same g): the scene kernel into both.
+int32_t mppi_debug_scene_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len) {
+    if (!g || !full || !quiet || len <= 0) return MPPI_ERR_INVALID_ARG;
+    DevParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.model = g[0]; p.A = g[1]; p.H = g[2]; p.L = g[3]; p.nch = g[4]; p.iters = g[5]; p.V = g[7];
+    p.R = p.L > 0 ? 64 / p.L : 0;
+    p.state_f64 = g[8]; p.noise_mode = g[9]; p.store_noise = g[10]; p.cost_terms = g[11]; p.sigma_diag = !g[12];
+    p.nb = 16; p.K = 16; p.store_traj = 1;
+    p.chain_fast = 2;
+    p.kern = g[14] ? kRollKernGeneric : 0;
+    static float nowhere[4];   // described, not run: any non-null table and scene
+    LaunchDesc da{}, db{};
+    const std::string a = roll_symbol(p, g[6], &da, nowhere, nowhere);
+    p.kern = quiet_roll_kern(p.kern, g[14] ? kGenericAll : 0, false, g[13] != 0, false);
+    const std::string b = roll_symbol(p, g[6], &db, nowhere, nowhere);
+    snprintf(full, (size_t)len, "%s", a.c_str());
+    snprintf(quiet, (size_t)len, "%s", b.c_str());
+    note_launches(da, db, g_roll_launch);
+    return (a == "?" || b == "?") ? MPPI_ERR_INVALID_ARG : MPPI_OK;
 }
 
 }  // extern "C"

@@ -267,6 +267,8 @@ struct PlanParams {
     float* S;                // (V)
     const float* ttab;       // (V,H,12) the target table of a tracking engine (row t: p*, R*), else null:
                              //   cost_t, pos_err and S against the vehicle's fixed target
+    float* scene;            // a scene engine's buffer (mppi_obstacles.h), else null: the obstacle term in cost_t
+                             //   and S, the steps' clearances (V,H) written at its plan offset
 };
 
 // Finalize / pack kernel parameters.
@@ -328,6 +330,12 @@ int mppi_launch_rollout_arm64_h32_tt(const mppi::DevParams* p, const float* ttab
 int mppi_launch_rollout_arm32_tt(const mppi::DevParams* p, const float* ttab, int block_threads, void* stream);
 int mppi_launch_rollout_wb_tt(const mppi::DevParams* p, const float* ttab, int block_threads, void* stream);
 int mppi_launch_rollout_quad_tt(const mppi::DevParams* p, const float* ttab, int block_threads, void* stream);
+// the scene rollouts (an engine of mppi_create_scene): ttab as above, scene = the scene buffer (mppi_obstacles.h)
+int mppi_launch_rollout_scene(const mppi::DevParams* p, const float* ttab, float* scene, int block_threads, void* stream);
+int mppi_launch_rollout_arm64_ob(const mppi::DevParams* p, const float* ttab, float* scene, int block_threads, void* stream);
+int mppi_launch_rollout_arm64_h32_ob(const mppi::DevParams* p, const float* ttab, float* scene, int block_threads, void* stream);
+int mppi_launch_rollout_arm32_ob(const mppi::DevParams* p, const float* ttab, float* scene, int block_threads, void* stream);
+int mppi_launch_rollout_wb_ob(const mppi::DevParams* p, const float* ttab, float* scene, int block_threads, void* stream);
 int mppi_launch_finalize(const mppi::FinParams* p, void* stream);
 int mppi_launch_plan(const mppi::DevParams* p, const mppi::PlanParams* pp, void* stream);
 int mppi_launch_peer_probe(unsigned long long* const* peers, unsigned long long* local, int n, int me,

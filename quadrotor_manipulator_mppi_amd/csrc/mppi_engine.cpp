@@ -280,10 +280,15 @@ static mppi_status allocate(mppi_engine* e) {
     HIP_TRY(hipHostMalloc((void**)&e->h_out, e->out_bytes, hipHostMallocMapped | hipHostMallocCoherent));
     HIP_TRY(hipHostGetDevicePointer((void**)&e->h_out_dev, e->h_out, 0));
     HIP_TRY(hipMalloc(&e->d_sigma, sizeof(float) * kMaxA * kMaxA));
-    if (c.cost_terms & MPPI_COST_TARGET_TRACK) {   // the target table, its pinned staging copy and the uploads' event
+    if ((c.cost_terms & MPPI_COST_TARGET_TRACK) || e->has_scene) {   // the target table, its pinned staging copy and the uploads' event
         HIP_TRY(hipMalloc(&e->d_ttab, sizeof(float) * (size_t)e->V * e->H * 12));
         HIP_TRY(hipHostMalloc((void**)&e->h_ttab, sizeof(float) * (size_t)e->V * e->H * 12, hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&e->ev_tt, hipEventDisableTiming));
+    }
+    if (e->has_scene) {   // the scene buffer, the vehicles' obstacle blocks' pinned staging copy, the uploads' event
+        HIP_TRY(hipMalloc(&e->d_scene, sizeof(float) * (size_t)scene_words(e->V, e->K, e->H)));
+        HIP_TRY(hipHostMalloc((void**)&e->h_scene, sizeof(float) * (size_t)e->V * kSceneObsW, hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&e->ev_scene, hipEventDisableTiming));
     }
     if (c.cost_terms & ~MPPI_COST_TARGET_TRACK) {   // Sigma^-1, gamma^t, tracking target
         HIP_TRY(hipMalloc(&e->d_sinv, sizeof(float) * e->A * e->A));
@@ -339,6 +344,12 @@ static mppi_status upload(mppi_engine* e) {
         HIP_TRY(hipMemcpy(e->d_ttab, e->h_ttab, sizeof(float) * (size_t)e->V * e->H * 12, hipMemcpyHostToDevice));
         e->batch.ttab = e->call.ttab = e->d_ttab;
     }
+    if (e->d_scene) {   // the body table; every vehicle without obstacles (zero words: n = 0)
+        HIP_TRY(hipMemset(e->d_scene, 0, sizeof(float) * (size_t)scene_words(e->V, e->K, e->H)));
+        HIP_TRY(hipMemcpy(e->d_scene, e->scene_body.data(), sizeof(float) * kSceneBodyW, hipMemcpyHostToDevice));
+        std::memset(e->h_scene, 0, sizeof(float) * (size_t)e->V * kSceneObsW);
+        e->batch.scene = e->call.scene = e->d_scene;
+    }
     if (c.cost_terms & ~MPPI_COST_TARGET_TRACK) {
         HIP_TRY(hipMemcpy(e->d_sinv, e->sinv.data(), sizeof(float) * e->sinv.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(e->d_gamma, e->gamma_t.data(), sizeof(float) * e->gamma_t.size(), hipMemcpyHostToDevice));
@@ -358,17 +369,25 @@ using namespace mppi_host;
 
 extern "C" {
 
-mppi_status mppi_create(const mppi_config* cfg, mppi_engine** out) {
+mppi_status mppi_create(const mppi_config* cfg, mppi_engine** out) { return mppi_create_scene(cfg, nullptr, out); }
+
+mppi_status mppi_create_scene(const mppi_config* cfg, const mppi_scene* scene, mppi_engine** out) {
     if (!cfg || !out) return fail(MPPI_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     mppi_status st = validate(*cfg);
     if (st != MPPI_OK) return st;
+    if (scene && (st = scene_validate(*cfg, *scene)) != MPPI_OK) return st;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (cfg->device < 0 || cfg->device >= ndev)
         return fail(MPPI_ERR_INVALID_ARG, "device %d not present (%d HIP devices)", cfg->device, ndev);
     EngineLayout lay{};
     if ((st = layout_of(*cfg, lay)) != MPPI_OK) return st;
+    if (scene) {
+        lay.has_scene = true;
+        lay.scene_body.assign(kSceneBodyW, 0.0f);
+        scene_body_table(lay, *scene, lay.scene_body.data(), nullptr);
+    }
 
     mppi_engine* e = new mppi_engine();
     static_cast<EngineLayout&>(*e) = std::move(lay);
@@ -428,7 +447,7 @@ void mppi_destroy(mppi_engine* e) {
     exchange_release(e);   // the communicator and the other ranks' mapped regions
     void* dev[] = {e->d_xregion, e->d_xpeers, e->d_sigma, e->d_joints, e->d_vc, e->d_u_prev, e->d_noise_in, e->d_traj, e->d_noise_out,
                    e->d_S, e->d_hdr, e->d_rdata, e->d_out, e->d_wraw, e->d_wsmooth, e->d_w,
-                   e->d_sinv, e->d_gamma, e->d_jtraj, e->d_ttab, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec,
+                   e->d_sinv, e->d_gamma, e->d_jtraj, e->d_ttab, e->d_scene, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec,
                    e->d_plan_vc, e->d_plan, e->d_elite_cand, e->d_elites};
     for (void* p : dev) if (p) (void)hipFree(p);
     if (e->h_out) (void)hipHostFree(e->h_out);
@@ -436,6 +455,8 @@ void mppi_destroy(mppi_engine* e) {
     if (e->h_plan) (void)hipHostFree(e->h_plan);
     if (e->h_ttab) (void)hipHostFree(e->h_ttab);
     if (e->ev_tt) (void)hipEventDestroy(e->ev_tt);
+    if (e->h_scene) (void)hipHostFree(e->h_scene);
+    if (e->ev_scene) (void)hipEventDestroy(e->ev_scene);
     if (e->h_elites) (void)hipHostFree(e->h_elites);
     if (e->ev_vc) (void)hipEventDestroy(e->ev_vc);
     if (e->ev_out) (void)hipEventDestroy(e->ev_out);
@@ -483,7 +504,7 @@ mppi_status mppi_set_target(mppi_engine* e, int32_t v, const float* pos, const f
 
 mppi_status mppi_set_target_trajectory(mppi_engine* e, int32_t v, const float* pos, const float* quat) {
     if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
-    if (!e->d_ttab) return fail(MPPI_ERR_STATE, "engine created without MPPI_COST_TARGET_TRACK");
+    if (!(e->cfg.cost_terms & MPPI_COST_TARGET_TRACK)) return fail(MPPI_ERR_STATE, "engine created without MPPI_COST_TARGET_TRACK");
     if (v < 0 || v >= e->V) return fail(MPPI_ERR_INVALID_ARG, "mppi_set_target_trajectory: vehicle %d of %d", v, e->V);
     if (use_device(e)) return MPPI_ERR_HIP;
     const mppi_status st = target_rows_begin(e);
@@ -569,14 +590,14 @@ mppi_status mppi_kernel_timing_ex(mppi_engine* e, int32_t n, double* rollout_us,
     for (auto& x : ev) KT_TRY(hipEventCreate(&x));
     KT_TRY(hipMemcpyAsync(saved, e->d_u_prev, ub, hipMemcpyDeviceToDevice, e->stream));
     KT_TRY(hipEventRecord(ev[0], e->stream));
-    for (int i = 0; i < n && rc == 0; ++i) rc = launch_rollout(p, e->d_ttab, e->threads, e->stream);
+    for (int i = 0; i < n && rc == 0; ++i) rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene);
     KT_TRY(hipEventRecord(ev[1], e->stream));
     for (int i = 0; i < n && rc == 0; ++i) rc = mppi_launch_finalize(&f, e->stream);
     KT_TRY(hipEventRecord(ev[2], e->stream));
     // the kernels as a control step runs them: rollout after finalize (u_prev and the
     // records just written, cold in the other XCDs' L2)
     for (int i = 0; i < n && rc == 0 && pair_us; ++i) {
-        rc = launch_rollout(p, e->d_ttab, e->threads, e->stream);
+        rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene);
         if (rc == 0) rc = mppi_launch_finalize(&f, e->stream);
     }
     KT_TRY(hipEventRecord(ev[3], e->stream));
@@ -613,9 +634,9 @@ extern "C" mppi_status mppi_probe_sequence(mppi_engine* e, int32_t n, int32_t mo
     (void)hipEventCreate(&a); (void)hipEventCreate(&b);
     (void)hipEventRecord(a, e->stream);
     for (int i = 0; i < n; ++i) {
-        if (mode <= 2 || mode == 5) launch_rollout(p, e->d_ttab, e->threads, e->stream);
+        if (mode <= 2 || mode == 5) launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene);
         if (mode == 0 || mode == 3) mppi_launch_boundary((float*)e->d_out, fb, e->stream);
-        if (mode == 1 || mode == 4) launch_rollout(p1, e->d_ttab, e->threads, e->stream);
+        if (mode == 1 || mode == 4) launch_rollout(p1, e->d_ttab, e->threads, e->stream, e->d_scene);
         if (mode == 2) mppi_launch_finalize(&f, e->stream);
     }
     (void)hipEventRecord(b, e->stream);
@@ -636,6 +657,42 @@ mppi_status mppi_get_costs(mppi_engine* e, float* S) {
     if (!e || !S) return fail(MPPI_ERR_INVALID_ARG, "null argument");
     if (use_device(e)) return MPPI_ERR_HIP;
     return download(e, S, e->d_S, sizeof(float) * e->V * e->K);
+}
+
+// The obstacles of one vehicle: validated, staged and uploaded as a tracking engine's target rows are
+// (upload_target_rows: stream-ordered before the next step on both dispatch paths).
+mppi_status mppi_set_obstacles(mppi_engine* e, int32_t v, int32_t n, const float* center, const float* radius, const float* vel) {
+    if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
+    if (!e->d_scene) return fail(MPPI_ERR_STATE, "engine created without a scene (mppi_create_scene)");
+    mppi_status st = obstacles_validate(e->V, v, n, center, radius, vel);
+    if (st != MPPI_OK) return st;
+    if (use_device(e)) return MPPI_ERR_HIP;
+    if (e->scene_pending) {   // the previous copy out of the staging blocks must be done
+        HIP_TRY(hipEventSynchronize(e->ev_scene));
+        e->scene_pending = false;
+    }
+    float* const block = e->h_scene + (size_t)v * kSceneObsW;
+    obstacles_fill(block, n, center, radius, vel);
+    HIP_TRY(hipMemcpyAsync(e->d_scene + kSceneBodyW + (size_t)v * kSceneObsW, block, sizeof(float) * kSceneObsW,
+                           hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipEventRecord(e->ev_scene, e->stream));
+    e->scene_pending = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_clearances(mppi_engine* e, float* clr) {
+    if (!e || !clr) return fail(MPPI_ERR_INVALID_ARG, "null argument");
+    if (!e->d_scene) return fail(MPPI_ERR_STATE, "engine created without a scene (mppi_create_scene)");
+    if (use_device(e)) return MPPI_ERR_HIP;
+    return download(e, clr, e->d_scene + scene_clr_off(e->V), sizeof(float) * e->V * e->K);
+}
+
+mppi_status mppi_get_plan_clearance(mppi_engine* e, float* clr) {
+    if (!e || !clr) return fail(MPPI_ERR_INVALID_ARG, "null argument");
+    if (!e->d_scene) return fail(MPPI_ERR_STATE, "engine created without a scene (mppi_create_scene)");
+    const mppi_status st = mppi_get_plan(e, nullptr, nullptr, nullptr, nullptr);   // k_plan writes the steps' clearances
+    if (st != MPPI_OK) return st;
+    return download(e, clr, e->d_scene + scene_plan_off(e->V, e->K), sizeof(float) * e->V * e->H);
 }
 
 mppi_status mppi_get_weights(mppi_engine* e, float* w) {
@@ -709,6 +766,7 @@ mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos
     PlanParams pp;
     pp.vc = e->d_plan_vc;
     pp.ttab = e->d_ttab;
+    pp.scene = e->d_scene;
     pp.traj = e->d_plan; pp.cost_t = pp.traj + n_traj; pp.pos_err = pp.cost_t + n_vh; pp.S = pp.pos_err + n_vh;
     HIP_TRY(hipMemcpyAsync(e->d_plan_vc, e->h_vc, sizeof(VehicleConst) * V, hipMemcpyHostToDevice, e->stream));
     const int rc = mppi_launch_plan(&e->dp, &pp, e->stream);

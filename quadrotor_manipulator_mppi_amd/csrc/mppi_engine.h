@@ -54,6 +54,7 @@ struct DescCache {
     mppi::FinParams f{};
     mppi::LaunchDesc roll{}, fin{}, roll_quiet{}, fin_quiet{};
     const float* ttab = nullptr;   // a tracking engine's target table (its rollouts' extra argument; fixed per engine)
+    float* scene = nullptr;        // a scene engine's buffer (likewise)
     // ignore_vc0: the vehicle constants (the state) may differ -- a control call patches them in
     bool matches(const mppi::DevParams& p, const mppi::FinParams& f, int threads, bool ignore_vc0) const;
     // describes (p, f) and, where given, the quiet pair; the launchers' status (0: valid again)
@@ -118,6 +119,14 @@ struct mppi_engine : mppi_host::EngineLayout {
     hipEvent_t ev_tt = nullptr;
     bool tt_pending = false;
     std::vector<unsigned char> ttab_set;
+    // the scene of an obstacle-avoiding engine (mppi_create_scene; else none): the device buffer
+    // (mppi_obstacles.h: body table, the vehicles' obstacle blocks, the clearances), the pinned staging
+    // copy of the obstacle blocks (V, kSceneObsW) and the event recorded behind the last upload.  Such an
+    // engine always owns a target table (d_ttab; clear without the tracking bit).
+    float* d_scene = nullptr;
+    float* h_scene = nullptr;
+    hipEvent_t ev_scene = nullptr;
+    bool scene_pending = false;
     float* d_exchange = nullptr;
     // mppi_get_plan's buffers (allocated at its first call): the host's vehicle constants; the
     // planes (V,C,H), cost_t (V,H), pos_err (V,H) and S (V) in one block, and its pinned host copy
@@ -284,11 +293,13 @@ inline int32_t quiet_roll_kern(int32_t kern, int generic, bool diag, bool peer, 
 // a launch described into d instead of made (mppi_device.h go(); the launchers' status)
 // The rollout's launch: the tracking kernels (cost_terms & MPPI_COST_TARGET_TRACK) take the engine's
 // target table as an extra argument; every other launch is mppi_launch_rollout's.
-inline int launch_rollout(const mppi::DevParams& p, const float* ttab, int threads, void* stream) {
+// A scene engine's (scene non-null) run the scene kernels, with or without the tracking bit.
+inline int launch_rollout(const mppi::DevParams& p, const float* ttab, int threads, void* stream, float* scene = nullptr) {
+    if (scene) return mppi_launch_rollout_scene(&p, ttab, scene, threads, stream);
     return (p.cost_terms & MPPI_COST_TARGET_TRACK) ? mppi_launch_rollout_track(&p, ttab, threads, stream)
                                                    : mppi_launch_rollout(&p, threads, stream);
 }
-int describe(const mppi::DevParams& p, int threads, mppi::LaunchDesc* d, const float* ttab = nullptr);
+int describe(const mppi::DevParams& p, int threads, mppi::LaunchDesc* d, const float* ttab = nullptr, float* scene = nullptr);
 int describe(const mppi::FinParams& f, mppi::LaunchDesc* d);
 // -------------------------------------------------------------- step (mppi_step.cpp)
 // why this engine's steps cannot go native (nullptr: they can).  A batch may carry the stamps /
@@ -299,7 +310,8 @@ const char* aql_ineligible(const mppi_engine* e, bool batch = false);
 // ------------------------------------------------------- diagnostics (mppi_debug.cpp)
 // the symbol a launch would run, by the launchers' own description of it ("?": none)
 std::string fin_symbol(const mppi::FinParams& f, mppi::LaunchDesc* desc = nullptr);
-std::string roll_symbol(const mppi::DevParams& p, int threads, mppi::LaunchDesc* desc = nullptr, const float* ttab = nullptr);
+std::string roll_symbol(const mppi::DevParams& p, int threads, mppi::LaunchDesc* desc = nullptr, const float* ttab = nullptr,
+                        float* scene = nullptr);
 
 // ------------------------------------------------------ exchange (mppi_exchange.cpp)
 // RCCL, resolved at the first mppi_comm_* call (dlopen: the library loads and its single-GPU

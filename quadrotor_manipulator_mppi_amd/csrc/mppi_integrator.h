@@ -29,6 +29,27 @@ __device__ __forceinline__ float seg_scan_f32(float x) {
     return x;
 }
 
+// The min of an L-lane segment (L = 32, 64) in every lane of it: the four in-row levels of
+// wave_fold_all, then the row-pair swap (rows 0-1, 2-3: the 32-lane halves) and, for L = 64, the
+// half swap.  Symmetric pairings: every lane of a segment ends with the same bits.
+template <int L>
+__device__ __forceinline__ float seg_min_f32(float x) {
+    static_assert(L == 32 || L == 64, "segments of 32 or 64 lanes");
+    x = fminf(x, dpp_all<0xB1>(x));
+    x = fminf(x, dpp_all<0x4E>(x));
+    x = fminf(x, dpp_all<0x141>(x));
+    x = fminf(x, dpp_all<0x140>(x));
+    {
+        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+        x = fminf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    }
+    if constexpr (L == 64) {
+        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+        x = fminf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+    }
+    return x;
+}
+
 // fp32 inclusive scans of NA independent dims inside L-lane segments, step-major
 // (the DPP wait states of one dim are filled by the others).  Each step is one
 // v_add_f32_dpp: x + dpp(x), where out-of-row sources read 0 (row_shr with

@@ -204,6 +204,93 @@ mppi_status layout_of(const mppi_config& cfg, EngineLayout& l) {
     return MPPI_OK;
 }
 
+// ------------------------------------------------------------------ the sphere scene
+mppi_status scene_validate(const mppi_config& c, const mppi_scene& s) {
+    if (c.model == MPPI_MODEL_QUADROTOR)
+        return fail(MPPI_ERR_INVALID_ARG, "a scene needs the ARM, WHOLEBODY or DRONE model (no QUADROTOR scene kernel)");
+    if (s.n_body < 0 || s.n_body > MPPI_MAX_BODY_SPHERES)
+        return fail(MPPI_ERR_INVALID_ARG, "scene: n_body %d outside 0..%d", s.n_body, MPPI_MAX_BODY_SPHERES);
+    const float w[3] = {s.w_obs, s.margin, s.penalty};
+    for (const float x : w)
+        if (!std::isfinite(x) || x < 0.0f) return fail(MPPI_ERR_INVALID_ARG, "scene: w_obs, margin and penalty are finite and >= 0");
+    const int nj = c.model == MPPI_MODEL_DRONE ? 0 : c.n_joints;
+    for (int b = 0; b < s.n_body; ++b) {
+        const mppi_body_sphere& sp = s.body[b];
+        if (sp.frame < -1 || sp.frame >= nj)
+            return fail(MPPI_ERR_INVALID_ARG, "scene: body sphere %d on frame %d, outside [-1, %d)", b, sp.frame, nj);
+        if (!std::isfinite(sp.offset[0]) || !std::isfinite(sp.offset[1]) || !std::isfinite(sp.offset[2]) ||
+            !std::isfinite(sp.radius))
+            return fail(MPPI_ERR_INVALID_ARG, "scene: body sphere %d has a non-finite value", b);
+        if (!(sp.radius > 0.0f)) return fail(MPPI_ERR_INVALID_ARG, "scene: body sphere %d radius %g <= 0", b, sp.radius);
+    }
+    return MPPI_OK;
+}
+
+void scene_body_table(const EngineLayout& l, const mppi_scene& s, float* table, int* order) {
+    std::memset(table, 0, sizeof(float) * kSceneBodyW);
+    const auto put = [&](int i, int32_t x) { std::memcpy(table + i, &x, sizeof(x)); };
+    const int j0 = l.cfg.model == MPPI_MODEL_DRONE ? 0 : l.dp.j0;
+    int slot[MPPI_MAX_BODY_SPHERES];
+    double off[MPPI_MAX_BODY_SPHERES][3];
+    for (int b = 0; b < s.n_body; ++b) {
+        const mppi_body_sphere& sp = s.body[b];
+        for (int d = 0; d < 3; ++d) off[b][d] = sp.offset[d];
+        if (sp.frame >= j0) { slot[b] = sp.frame - j0 + 1; continue; }
+        // a frame the base swallowed: o' = (O_{f+1} .. O_{j0-1})^-1 (o, 1), the rigid inverses applied
+        // from the left-most factor on, in double
+        slot[b] = 0;
+        for (int j = sp.frame + 1; j < j0; ++j) {
+            const float* O = l.joints[j].O;
+            const double d[3] = {off[b][0] - O[3], off[b][1] - O[7], off[b][2] - O[11]};
+            for (int i = 0; i < 3; ++i) off[b][i] = (double)O[i] * d[0] + (double)O[4 + i] * d[1] + (double)O[8 + i] * d[2];
+        }
+    }
+    int n = 0;
+    for (int sl = 0; sl <= kSceneSlots; ++sl) {   // stable by slot; the last word: n_body
+        put(kSceneRng + sl, n);
+        for (int b = 0; b < s.n_body && sl < kSceneSlots; ++b)
+            if (slot[b] == sl) {
+                float* w = table + kSceneSph + 4 * n;
+                for (int d = 0; d < 3; ++d) w[d] = (float)off[b][d];
+                w[3] = s.body[b].radius;
+                if (order) order[n] = b;
+                ++n;
+            }
+    }
+    put(0, s.n_body);
+    table[1] = s.w_obs; table[2] = s.margin; table[3] = s.penalty;
+    put(4, (int32_t)scene_clr_off(l.V));
+    put(5, (int32_t)scene_plan_off(l.V, l.K));
+    put(6, l.K);
+}
+
+mppi_status obstacles_validate(int n_vehicles, int vehicle, int n, const float* center, const float* radius, const float* vel) {
+    if (vehicle < 0 || vehicle >= n_vehicles) return fail(MPPI_ERR_INVALID_ARG, "mppi_set_obstacles: vehicle %d of %d", vehicle, n_vehicles);
+    if (n < 0 || n > MPPI_MAX_OBSTACLES) return fail(MPPI_ERR_INVALID_ARG, "mppi_set_obstacles: n %d outside 0..%d", n, MPPI_MAX_OBSTACLES);
+    if (n > 0 && (!center || !radius)) return fail(MPPI_ERR_INVALID_ARG, "mppi_set_obstacles: null centres or radii");
+    for (int o = 0; o < n; ++o) {
+        bool fin = std::isfinite(radius[o]);
+        for (int d = 0; d < 3; ++d) fin = fin && std::isfinite(center[3 * o + d]) && (!vel || std::isfinite(vel[3 * o + d]));
+        if (!fin) return fail(MPPI_ERR_INVALID_ARG, "mppi_set_obstacles: obstacle %d has a non-finite value", o);
+        if (!(radius[o] > 0.0f)) return fail(MPPI_ERR_INVALID_ARG, "mppi_set_obstacles: obstacle %d radius %g <= 0", o, radius[o]);
+    }
+    return MPPI_OK;
+}
+
+void obstacles_fill(float* block, int n, const float* center, const float* radius, const float* vel) {
+    std::memset(block, 0, sizeof(float) * kSceneObsW);
+    const int32_t n32 = n;
+    std::memcpy(block, &n32, sizeof(n32));
+    for (int o = 0; o < n; ++o) {
+        float* r = block + 4 + 8 * o;
+        for (int d = 0; d < 3; ++d) {
+            r[d] = center[3 * o + d];
+            r[4 + d] = vel ? vel[3 * o + d] : 0.0f;
+        }
+        r[3] = radius[o];
+    }
+}
+
 void set_generic(EngineLayout& l, int generic) {
     l.generic = generic;
     l.fp.kern = (generic & 1) ? kFinKernGeneric : 0;
@@ -213,6 +300,50 @@ void set_generic(EngineLayout& l, int generic) {
 }  // namespace mppi_host
 
 using namespace mppi_host;
+
+// The project's default scene (include/mppi_hip.h; the Python twin: robot/body_spheres.py): placeholders
+// for the user's collision model -- 0.05 m at the frame origin of every actuated chain joint, 0.30 m on
+// the base frame of a flying vehicle; w_obs = 100, margin = 0.05 m, penalty = 1e4.
+extern "C" void mppi_scene_default(mppi_scene* s, const mppi_config* cfg) {
+    if (!s) return;
+    std::memset(s, 0, sizeof(*s));
+    s->w_obs = 100.0f; s->margin = 0.05f; s->penalty = 1e4f;
+    if (!cfg || cfg->model == MPPI_MODEL_QUADROTOR) return;
+    const auto add = [&](int frame, float r) {
+        if (s->n_body < MPPI_MAX_BODY_SPHERES) s->body[s->n_body++] = mppi_body_sphere{frame, {0.0f, 0.0f, 0.0f}, r};
+    };
+    if (cfg->model != MPPI_MODEL_ARM) add(-1, 0.30f);
+    if (cfg->model != MPPI_MODEL_DRONE)
+        for (int j = 0; j < cfg->n_joints && j < MPPI_MAX_JOINTS; ++j)
+            if (cfg->joints[j].type != MPPI_JOINT_FIXED) add(j, 0.05f);
+}
+
+// Diagnostic (no GPU): validate, scene_validate and the body table of a configuration and a scene.
+// table: kSceneBodyW words; order: n_body ints (either may be null).  Returns the first failing status.
+// tests/test_capi_obstacles_cpu.py.
+extern "C" int32_t mppi_debug_scene_layout(const mppi_config* cfg, const mppi_scene* scene, float* table, int32_t* order) {
+    if (!cfg || !scene) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_scene_layout: bad arguments");
+    mppi_status st = validate(*cfg);
+    if (st != MPPI_OK) return st;
+    if ((st = scene_validate(*cfg, *scene)) != MPPI_OK) return st;
+    EngineLayout l;
+    if ((st = layout_of(*cfg, l)) != MPPI_OK) return st;
+    float t[kSceneBodyW];
+    int ord[MPPI_MAX_BODY_SPHERES] = {0};
+    scene_body_table(l, *scene, t, ord);
+    if (table) std::memcpy(table, t, sizeof(t));
+    if (order) std::memcpy(order, ord, sizeof(int32_t) * (size_t)scene->n_body);
+    return MPPI_OK;
+}
+
+// Diagnostic (no GPU): the errors of mppi_set_obstacles for an engine of n_vehicles, and (block non-null)
+// the vehicle block the call would stage (kSceneObsW words).
+extern "C" int32_t mppi_debug_obstacles(int32_t n_vehicles, int32_t vehicle, int32_t n, const float* center,
+                                        const float* radius, const float* vel, float* block) {
+    const mppi_status st = obstacles_validate(n_vehicles, vehicle, n, center, radius, vel);
+    if (st == MPPI_OK && block) obstacles_fill(block, n, center, radius, vel);
+    return st;
+}
 
 // Diagnostic (not part of the public header): the layout of a configuration without a device.
 // out[0..27]: threads, L, R, nch, nb, iters, P, C, hp, fin_tsz, fin_ts, j0, chain_fast, sigma_diag,

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "mppi_dev.h"
+#include "mppi_obstacles.h"
 
 // mppi_engine::generic with every part switched back (MPPI_GENERIC_KERNELS=1)
 constexpr int kGenericAll = 15;
@@ -48,6 +49,8 @@ struct EngineLayout {
     float fixedM[12];                   // product of the leading fixed joints (folded into base)
     mppi::JointDev joints[mppi::kMaxJ]; // the baked chain table
     std::vector<float> sinv, gamma_t;   // cost_terms: Sigma^-1 (A,A) and gamma^t (H), else empty
+    bool has_scene = false;             // mppi_create_scene: the scene kernels; its body table (kSceneBodyW words)
+    std::vector<float> scene_body;
     int fin_ts = 1, fin_tsz = 8;        // finalize t-slices
     int generic = 0;                    // MPPI_GENERIC_KERNELS=1 (tests, A/B): the kernels as before the role and
                                         // fixed-block ones.  Bits: 1 the finalize of every role with run-time
@@ -58,6 +61,19 @@ struct EngineLayout {
 // Reads MPPI_FIN_TSZ, MPPI_NO_KINOVA_PATH and MPPI_GENERIC_KERNELS, the switches that change the
 // layout.  `c` has passed validate(); a configuration past a limit fails with its status and message.
 mppi_status layout_of(const mppi_config& c, EngineLayout& l);
+
+// ------------------------------------------------- the sphere scene (mppi_layout.cpp; mppi_obstacles.h)
+// scene_validate: the errors of mppi_create_scene, for a configuration that passed validate().
+// scene_body_table: the engine-wide part of the scene buffer (kSceneBodyW words) for a layout: the
+// spheres on frames before the first unfolded joint (l.dp.j0) re-expressed in the folded frame (in
+// double), all of them sorted by frame slot (stable), the slots' ranges, the weights and the offsets
+// of the clearance outputs.  order (n_body ints, may be null): sorted position -> the caller's index.
+// obstacles_validate / obstacles_fill: the errors of mppi_set_obstacles and one vehicle's block
+// (kSceneObsW words) from the caller's arrays.
+mppi_status scene_validate(const mppi_config& c, const mppi_scene& s);
+void scene_body_table(const EngineLayout& l, const mppi_scene& s, float* table, int* order);
+mppi_status obstacles_validate(int n_vehicles, int vehicle, int n, const float* center, const float* radius, const float* vel);
+void obstacles_fill(float* block, int n, const float* center, const float* radius, const float* vel);
 // the MPPI_GENERIC_KERNELS bits (EngineLayout::generic) and what they set in dp and fp
 void set_generic(EngineLayout& l, int generic);
 

@@ -16,6 +16,7 @@
 // (V, C, H), cost_t (V, H), pos_err (V, H), S (V).
 #include "mppi_fk.h"
 #include "mppi_integrator.h"   // seg_scan_f32_multi
+#include "mppi_obstacles.h"
 #include "mppi_quad_step.h"
 
 namespace {
@@ -26,9 +27,12 @@ namespace {
 // own: lifted out of rollout_body into functions both kernels call, they changed the rollout's
 // register allocation (the step's code objects must stay as they are), so rollout_body keeps its
 // copy.  T = base (whole-body: its position added) times the joints at pf (pd: the fp64 angles).
-template <int MODEL, int NA, bool F64>
+// at_frame(slot): called as each frame of the chain completes (slot 0: the folded base, slot 1 + j:
+// after chain joint j0 + j) -- a scene engine's obstacle term (mppi_obstacles.h).
+template <int MODEL, int NA, bool F64, typename AtFrame>
 __device__ __forceinline__ void plan_fk(Mat34& T, const float (&pf)[NA], const double (&pd)[F64 ? NA : 1],
-                                        const VehicleConst& vc, const JointDev* jnt, const DevParams& p) {
+                                        const VehicleConst& vc, const JointDev* jnt, const DevParams& p,
+                                        AtFrame&& at_frame) {
     constexpr int QOFF = (MODEL == MPPI_MODEL_WHOLEBODY) ? 3 : 0;
     constexpr int NQ = NA - QOFF;
     auto qang = [&](int j) {   // joint angle j in the state dtype
@@ -39,14 +43,22 @@ __device__ __forceinline__ void plan_fk(Mat34& T, const float (&pf)[NA], const d
     if (MODEL == MPPI_MODEL_WHOLEBODY) {
         T.m[3] += pf[0]; T.m[7] += pf[1]; T.m[11] += pf[2];
     }
+    at_frame(0);
     if (NQ == 7 && p.chain_fast == 2) {   // Kinova
         kin_joint<0>(T, jnt[p.j0 + 0].O, qang(0));
+        at_frame(1);
         kin_joint<1>(T, jnt[p.j0 + 1].O, qang(1));
+        at_frame(2);
         kin_joint<2>(T, jnt[p.j0 + 2].O, qang(2));
+        at_frame(3);
         kin_joint<3>(T, jnt[p.j0 + 3].O, qang(3));
+        at_frame(4);
         kin_joint<4>(T, jnt[p.j0 + 4].O, qang(4));
+        at_frame(5);
         kin_joint<5>(T, jnt[p.j0 + 5].O, qang(5));
+        at_frame(6);
         kin_joint<6>(T, jnt[p.j0 + 6].O, qang(6));
+        at_frame(7);
     } else if (p.chain_fast) {   // nq revolute-z joints, q_index = 0..nq-1 in order
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
@@ -62,12 +74,16 @@ __device__ __forceinline__ void plan_fk(Mat34& T, const float (&pf)[NA], const d
                 T.m[4 * i + 1] = a1 * cc - a0 * s;
                 T.m[4 * i + 2] = T.m[4 * i + 2] * r22;
             }
+            at_frame(j + 1);
         }
     } else {
         for (int jn = p.j0; jn < p.nj; ++jn) {
             const JointDev& J = jnt[jn];
             mul_affine(T, J.O);
-            if (J.type == MPPI_JOINT_FIXED) continue;
+            if (J.type == MPPI_JOINT_FIXED) {
+                at_frame(jn - p.j0 + 1);
+                continue;
+            }
             double qd = 0.0;
             float qf = 0.0f;
 #pragma unroll
@@ -83,6 +99,7 @@ __device__ __forceinline__ void plan_fk(Mat34& T, const float (&pf)[NA], const d
             } else {
                 mul_prismatic(T, J, qf);
             }
+            at_frame(jn - p.j0 + 1);
         }
     }
 }
@@ -146,6 +163,7 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     __shared__ VehicleConst vcv;
     __shared__ float tot1[kMaxWaves][NA], tot2[kMaxWaves][NA];   // the waves' scan totals (the chunk carries)
     __shared__ float wsum[kMaxWaves];
+    __shared__ __attribute__((aligned(16))) float scn[kSceneLdsW];   // a scene engine's body table and obstacles
     const DevParams& p = pk;
     const int v = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int nthr = blockDim.x, nw = nthr >> 6;
@@ -164,6 +182,8 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     if (MODEL != MPPI_MODEL_DRONE)
         for (int i = tid; i < kJW; i += nthr) ((int*)jnt)[i] = ((const int*)jtab)[i];
     for (int i = tid; i < kVCW; i += nthr) ((int*)&vcv)[i] = ((const int*)(pp.vc + v))[i];
+    if (pp.scene)
+        for (int i = tid; i < kSceneLdsW; i += nthr) scn[i] = pp.scene[i < kSceneBodyW ? i : i + v * kSceneObsW];
     const VehicleConst& vc = vcv;
 
     // ---- double integrator (standard_normal_noise.py:41-48), k_rollout's NCH > 1 arithmetic
@@ -225,17 +245,26 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
         for (int i = 0; i < 9; ++i) tg[3 + i] = vc.tR[i];
     }
     float cost, perr;
+    // a scene engine's term of this step: the hinge sum and the min clearance at row time (t + 1) dt
+    float oh = 0.0f, og = INFINITY;
+    const float otau = (float)(t + 1) * p.dt;
     if (MODEL == MPPI_MODEL_DRONE) {
         const float dx = posf[0] - tg[0], dy = posf[1] - tg[1], dz = posf[2] - tg[2];
         cost = (term ? p.w_tp : p.w_sp) * (dx * dx + dy * dy + dz * dz);
         perr = fabsf(dx) + fabsf(dy) + fabsf(dz);
+        if (pp.scene) {
+            const float Td[12] = {1.0f, 0.0f, 0.0f, posf[0], 0.0f, 1.0f, 0.0f, posf[1], 0.0f, 0.0f, 1.0f, posf[2]};
+            obs_frame(Td, scn, scn + kSceneBodyW, 0, otau, oh, og);
+        }
         if (val) {
 #pragma unroll
             for (int a = 0; a < 3; ++a) planes[(size_t)a * H + t] = posf[a];
         }
     } else {
         Mat34 T;
-        plan_fk<MODEL, NA, F64>(T, posf, posd, vc, jnt, p);
+        plan_fk<MODEL, NA, F64>(T, posf, posd, vc, jnt, p, [&](int slot) {
+            if (pp.scene) obs_frame(T.m, scn, scn + kSceneBodyW, slot, otau, oh, og);
+        });
         cost = pose_cost_row(T, tg, term ? p.w_tp : p.w_sp, term ? p.w_to : p.w_so);
         perr = fabsf(T.m[3] - tg[0]) + fabsf(T.m[7] - tg[1]) + fabsf(T.m[11] - tg[2]);
         if (val) {
@@ -257,6 +286,10 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
             if (p.cost_terms & MPPI_COST_ACTION) cost += (p.w_act * action_sumsq<NA>(act)) * g;
             if ((p.cost_terms & MPPI_COST_JOINT_LIMIT) && out) cost += p.lim_pen * g;
         }
+    }
+    if (pp.scene) {   // after the CostManager terms, as the rollout adds it
+        cost += obs_step_cost(scn, oh, og);
+        if (val) pp.scene[(size_t)scene_int(scn + 5) + (size_t)v * H + t] = og;
     }
     if (val) {
         pp.cost_t[(size_t)v * H + t] = cost;

@@ -26,6 +26,7 @@
 #include "mppi_fk.h"
 #include "mppi_stores.h"
 #include "mppi_integrator.h"
+#include "mppi_obstacles.h"
 
 // The leading scalar arguments are preloaded into SGPRs at wave launch on gfx950
 // (-mllvm -amdgpu-kernarg-preload-count, build.py): the first group's Philox
@@ -51,6 +52,9 @@
 // The extended (XC) NCH == 2 kernels likewise run best at 2 (whole-body K=8192 H=128 full
 // Sigma 72.1 -> 43.6 us, arm 21.8 -> 19.3); XC NCH == 1 keeps 4 (2 and 3 measured slower;
 // profiles/r02/ab_rollout_occupancy_xc.txt)
+// the scene body's accumulators (a hinge or cost sum, a min clearance); nothing in the other bodies
+template <bool OBS> struct ObsAcc {};
+template <> struct ObsAcc<true> { float sum = 0.0f, gmin = INFINITY; };
 template <int NCH, bool F64, bool XC, bool ONEG>
 constexpr int roll_occ() {
     return (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH == 2 ? (XC ? 2 : 4) : 4);
@@ -66,16 +70,24 @@ constexpr int roll_occ() {
 // (V, H, 12), one per 64-lane chunk, once, with the prologue's other global loads, and the pose cost
 // (the drone branch: the position cost) takes p*_t and R*_t from those registers instead of the
 // vehicle constants.  An extended (XC) body: extra terms, a full Sigma and generic chains go with it.
+// OBS (k_rollout_ob; mppi_create_scene): the sphere scene's term (mppi_obstacles.h).  A tracking (TRK)
+// body -- a scene engine always owns a target table -- whose block stages the engine's body table and
+// the vehicle's obstacle rows in static LDS with the prologue's other loads; as each frame of the FK
+// chain completes, the lane runs that frame's spheres against the obstacles at its own row time
+// (wave-uniform LDS reads), and the step's term joins the extra terms' segment sums.  The per-sample
+// clearance, a segment min, is staged and written through beside S (into the scene buffer).
 template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG, bool B512, bool QUIET = false,
-          bool TRK = false>
+          bool TRK = false, bool OBS = false>
 __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint32_t seed_hi,
                                              const uint32_t step_arg, const uint32_t k_off,
                                              const int32_t noise_arg, const int32_t H_arg,
                                              const int32_t geo_arg,
                                              const float* __restrict__ u_prev,
                                              const JointDev* __restrict__ jtab, const DevParams& pk,
-                                             const float* __restrict__ ttab = nullptr) {
+                                             const float* __restrict__ ttab = nullptr,
+                                             float* __restrict__ scene = nullptr) {
     static_assert(!B512 || ONEG, "the fixed-block body is a single-group one");
+    static_assert(!OBS || (TRK && !B512), "the scene body is a tracking one of every block size");
     static_assert(!TRK || (XC && !QUIET), "the tracking body is an extended one, and has no quiet form");
     static_assert(!QUIET || (!XC && NCH == 1), "the quiet body exists for the common one-chunk kernels");
     constexpr bool kTraj = !QUIET && !(MPPI_KO & 16);      // trajectory planes
@@ -95,6 +107,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     // phases); the joint table and (V > 1) the vehicle block go to LDS.
     __shared__ JointDev jnt[kMaxJ];
     __shared__ VehicleConst vcv;
+    __shared__ __attribute__((aligned(16))) float scn[OBS ? kSceneLdsW : 4];   // OBS: the body table, then the vehicle's obstacles
     const DevParams& p = pk;
     const int v = blockIdx.y;
     // block size and groups per block as one preloaded argument (threads | iters << 16): blockDim
@@ -152,6 +165,12 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             load_target_row<MODEL == MPPI_MODEL_DRONE>(ttab + ((size_t)v * H_arg + tc) * 12, tgt[c]);
         }
     }
+    // the scene word this thread stages (the body table, then vehicle v's block)
+    auto scene_word = [&](int i) __attribute__((always_inline)) {
+        return scene[i < kSceneBodyW ? i : i + v * kSceneObsW];
+    };
+    float scr = 0.0f;
+    if constexpr (OBS) scr = (tid < kSceneLdsW) ? scene_word(tid) : 0.0f;
     // touch every kernel-argument line the hot phases read (one s_load per 64 B): they
     // land in the scalar cache while the first group's Philox draw runs below
     // (an integer fold: uniform, so SALU -- a float sum took one VALU op per line)
@@ -265,6 +284,10 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                                    __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+    if constexpr (OBS) {
+        if (tid < kSceneLdsW) scn[tid] = scr;
+        for (int i = tid + nthr; i < kSceneLdsW; i += nthr) scn[i] = scene_word(i);   // nthr < 224
+    }
     STAMPW(8);
     if (!(MPPI_KO & 256)) lds_barrier();
     const VehicleConst& vc = vcv;
@@ -274,6 +297,8 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     // the block's costs, nw * R consecutive k per group, staged in LDS for write-through store runs
     // after the combine barrier (st_dev_run)
     float* const s_stage = smem + ((HA + 3) & ~3) + 8 * kWs;
+    // OBS: the block's clearances, staged the same way behind the costs
+    float* const c_stage = OBS ? s_stage + iters * cost_run_stride(nw * R) : nullptr;
     STAMP(1);
 
     // trajectory planes of vehicle v (from kernel arguments and blockIdx only, so the
@@ -484,18 +509,25 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         // ---- A4-A10: FK + per-step cost, trajectory planes
         float xs[NCH];
         float ecen = 0.0f, ejt = 0.0f, elim = 0.0f;
+        ObsAcc<OBS> oacc;   // OBS: the lane's obstacle term and min clearance over its steps
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             const int t = t0 + 64 * c;
             const bool val = kval && t < H;
             const bool term = (t == H - 1);
             float x;
+            // OBS: this step's hinge sum and min clearance (the obstacles at their row time (t + 1) dt)
+            ObsAcc<OBS> ostep;
             const uint32_t toff = ((uint32_t)k * (uint32_t)hp + (uint32_t)t) * 4u;   // byte offset in a plane
             const bool stv = kTraj && HOT(store_traj) && kval && t < hp;   // row incl. its pad (finite values)
             if (MODEL == MPPI_MODEL_DRONE) {
                 const float dx = posf[c][0] - (TRK ? tgt[c][0] : vc.tpos[0]), dy = posf[c][1] - (TRK ? tgt[c][1] : vc.tpos[1]),
                             dz = posf[c][2] - (TRK ? tgt[c][2] : vc.tpos[2]);
                 x = dx * dx + dy * dy + dz * dz;
+                if constexpr (OBS) {   // no chain: the spheres ride on p(k,t) in world axes
+                    const float Td[12] = {1.0f, 0.0f, 0.0f, posf[c][0], 0.0f, 1.0f, 0.0f, posf[c][1], 0.0f, 0.0f, 1.0f, posf[c][2]};
+                    obs_frame(Td, scn, scn + kSceneBodyW, 0, (float)(t + 1) * p.dt, ostep.sum, ostep.gmin);
+                }
                 if (stv) {
 #pragma unroll
                     for (int a = 0; a < 3; ++a) traj_store(trs, toff, (uint32_t)a * plane_b, posf[c][a]);
@@ -515,6 +547,11 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 if (MODEL == MPPI_MODEL_WHOLEBODY) {   // [R(rpy) | p_drone(k,t)] * M_fixed
                     T.m[3] += posf[c][0]; T.m[7] += posf[c][1]; T.m[11] += posf[c][2];
                 }
+                // OBS: the spheres of a frame slot as soon as T is that frame (slot 0: the folded base)
+                auto obs_at = [&](int slot) __attribute__((always_inline)) {
+                    if constexpr (OBS) obs_frame(T.m, scn, scn + kSceneBodyW, slot, (float)(t + 1) * p.dt, ostep.sum, ostep.gmin);
+                };
+                obs_at(0);
                 if (MPPI_KO & 4) {
                     T.m[3] += posf[c][QOFF]; T.m[7] += posf[c][QOFF + 1];
                 } else if (NQ == 7 && (!XC || p.chain_fast == 2)) {   // Kinova: origin rotations are signed
@@ -537,12 +574,19 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                         kin_joint_sc<6>(T, jnt[HOT(j0) + 6].O, sj[6], cj[6]);
                     } else {
                         kin_joint<0>(T, jnt[HOT(j0) + 0].O, qang(c, 0));
+                        obs_at(1);
                         kin_joint<1>(T, jnt[HOT(j0) + 1].O, qang(c, 1));
+                        obs_at(2);
                         kin_joint<2>(T, jnt[HOT(j0) + 2].O, qang(c, 2));
+                        obs_at(3);
                         kin_joint<3>(T, jnt[HOT(j0) + 3].O, qang(c, 3));
+                        obs_at(4);
                         kin_joint<4>(T, jnt[HOT(j0) + 4].O, qang(c, 4));
+                        obs_at(5);
                         kin_joint<5>(T, jnt[HOT(j0) + 5].O, qang(c, 5));
+                        obs_at(6);
                         kin_joint<6>(T, jnt[HOT(j0) + 6].O, qang(c, 6));
+                        obs_at(7);
                     }
                 } else if (!XC) {   // (unreachable: the common kernel is dispatched for Kinova chains only)
                 } else if (p.chain_fast) {   // nq revolute-z joints, q_index = 0..nq-1 in order
@@ -560,12 +604,16 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                             T.m[4 * i + 1] = a1 * cc - a0 * s;
                             T.m[4 * i + 2] = T.m[4 * i + 2] * r22;
                         }
+                        obs_at(j + 1);
                     }
                 } else {
                     for (int jn = HOT(j0); jn < p.nj; ++jn) {
                         const JointDev& J = jnt[jn];
                         mul_affine(T, J.O);
-                        if (J.type == MPPI_JOINT_FIXED) continue;
+                        if (J.type == MPPI_JOINT_FIXED) {
+                            obs_at(jn - HOT(j0) + 1);
+                            continue;
+                        }
                         double qd = 0.0;
                         float qf = 0.0f;
 #pragma unroll
@@ -581,6 +629,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                         } else {
                             mul_prismatic(T, J, qf);
                         }
+                        obs_at(jn - HOT(j0) + 1);
                     }
                 }
                 // the four weights as SGPR values: selecting between two kernel-argument
@@ -597,6 +646,10 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 }
             }
             xs[c] = val ? x : 0.0f;
+            if constexpr (OBS) {
+                oacc.sum += val ? obs_step_cost(scn, ostep.sum, ostep.gmin) : 0.0f;
+                oacc.gmin = fminf(oacc.gmin, val ? ostep.gmin : INFINITY);
+            }
             // extra joint-space terms (cost_manager.py:84,85,87; joint_space_cost.py)
             if (XC && (p.cost_terms & (MPPI_COST_CENTER | MPPI_COST_JOINT_TRACK | MPPI_COST_JOINT_LIMIT))) {
                 const int tc = (t < H) ? t : H - 1;
@@ -657,6 +710,13 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                     S_seg[s] += add;
                 }
             }
+        }
+        if constexpr (OBS) {   // S += the obstacle term (after the CostManager terms); the sample's clearance
+            const float ts = seg_scan_f32<LSEG>(oacc.sum);
+#pragma unroll
+            for (int s = 0; s < R; ++s) S_seg[s] += read_lane_f32(ts, s * LSEG + LSEG - 1);
+            const float clr = seg_min_f32<LSEG>(oacc.gmin);
+            if (kCosts && kval && t0 == 0) c_stage[it * cost_run_stride(nw * R) + wid * R + sub] = clr;
         }
         float S_mine = S_seg[0];
 #pragma unroll
@@ -790,6 +850,13 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             const int it = i / q, k0 = (blockIdx.x + it * HOT(nb)) * nS;
             st_dev_run(Sv, (uint32_t)k0, s_stage + it * cost_run_stride(nS), min(nS, K - k0), i - it * q);
         }
+        if constexpr (OBS) {   // the clearances beside them: (V, K) in the scene buffer
+            float* const Cv = uniform_ptr(scene + (size_t)scene_int(scn + 4) + (size_t)v * K);
+            for (int i = lane; i < iters * q; i += 64) {
+                const int it = i / q, k0 = (blockIdx.x + it * HOT(nb)) * nS;
+                st_dev_run(Cv, (uint32_t)k0, c_stage + it * cost_run_stride(nS), min(nS, K - k0), i - it * q);
+            }
+        }
     }
     // rho_b = the min of the 8 wave slots, which every thread reads for f_w anyway (an LDS
     // atomicMin before the barrier cost a waterfall loop and a ds_min per wave)
@@ -911,4 +978,20 @@ __global__ void __launch_bounds__(512, (roll_occ<NCH, F64, true, false>())) k_ro
                                                  const float* __restrict__ ttab, const DevParams pk) {
     rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, true, false, false, false, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg,
                                                                                    H_arg, geo_arg, u_prev, jtab, pk, ttab);
+}
+
+// The scene rollout (rollout_body OBS): the tracking kernel with the obstacle term, under a symbol of
+// its own.  The scene buffer (mppi_obstacles.h; read, and written with the clearances) is one more
+// pointer argument, next to the target table and before the trailing DevParams.
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE>
+__global__ void __launch_bounds__(512, (roll_occ<NCH, F64, true, false>())) k_rollout_ob(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                 const uint32_t step_arg, const uint32_t k_off,
+                                                 const int32_t noise_arg, const int32_t H_arg,
+                                                 const int32_t geo_arg,
+                                                 const float* __restrict__ u_prev,
+                                                 const JointDev* __restrict__ jtab,
+                                                 const float* __restrict__ ttab, float* __restrict__ scene,
+                                                 const DevParams pk) {
+    rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, true, false, false, false, true, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg,
+                                                                                         H_arg, geo_arg, u_prev, jtab, pk, ttab, scene);
 }

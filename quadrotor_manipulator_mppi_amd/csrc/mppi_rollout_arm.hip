@@ -18,3 +18,11 @@ extern "C" int mppi_launch_rollout_arm64_tt(const DevParams* p, const float* tta
         return launch_rollout_tt<MPPI_MODEL_ARM, 7, nch(), l(), true>(*p, ttab, threads, s);
     });
 }
+// the scene kernels (k_rollout_ob; mppi_create_scene), the H <= 32 one from its own unit
+extern "C" int mppi_launch_rollout_arm64_ob(const DevParams* p, const float* ttab, float* scene, int threads, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
+    if (p->nch == 1 && p->L == 32) return mppi_launch_rollout_arm64_h32_ob(p, ttab, scene, threads, stream);
+    return pick_geom<false>(*p, [&](auto nch, auto l) {
+        return launch_rollout_ob<MPPI_MODEL_ARM, 7, nch(), l(), true>(*p, ttab, scene, threads, s);
+    });
+}

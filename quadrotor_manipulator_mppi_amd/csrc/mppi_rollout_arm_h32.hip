@@ -12,3 +12,7 @@ extern "C" int mppi_launch_rollout_arm64_h32(const DevParams* p, int threads, vo
 extern "C" int mppi_launch_rollout_arm64_h32_tt(const DevParams* p, const float* ttab, int threads, void* stream) {
     return launch_rollout_tt<MPPI_MODEL_ARM, 7, 1, 32, true>(*p, ttab, threads, (hipStream_t)stream);
 }
+// the scene kernel of the same geometry (k_rollout_ob; mppi_create_scene)
+extern "C" int mppi_launch_rollout_arm64_h32_ob(const DevParams* p, const float* ttab, float* scene, int threads, void* stream) {
+    return launch_rollout_ob<MPPI_MODEL_ARM, 7, 1, 32, true>(*p, ttab, scene, threads, (hipStream_t)stream);
+}

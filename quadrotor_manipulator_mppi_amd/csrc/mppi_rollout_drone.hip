@@ -73,6 +73,27 @@ extern "C" int mppi_launch_rollout_track(const DevParams* p, const float* ttab, 
     return -1;
 }
 
+// The scene launch (an engine of mppi_create_scene): the same dispatch over the scene kernels
+// (k_rollout_ob), handed the target table and the scene buffer.  No quadrotor form.
+extern "C" int mppi_launch_rollout_scene(const DevParams* p, const float* ttab, float* scene, int threads, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    switch (p->model) {
+        case MPPI_MODEL_DRONE:
+            if (p->A == 3) return dispatch_geom_ob<MPPI_MODEL_DRONE, 3, false>(*p, ttab, scene, threads, s);
+            break;
+        case MPPI_MODEL_ARM:
+            if (p->A == 7) return p->state_f64 ? mppi_launch_rollout_arm64_ob(p, ttab, scene, threads, stream)
+                                               : mppi_launch_rollout_arm32_ob(p, ttab, scene, threads, stream);
+            break;
+        case MPPI_MODEL_WHOLEBODY:
+            if (p->A == 10) return mppi_launch_rollout_wb_ob(p, ttab, scene, threads, stream);
+            break;
+        default:
+            break;
+    }
+    return -1;
+}
+
 extern "C" int mppi_launch_philox(uint64_t seed, uint32_t step, int vehicle, int64_t k0, int K, int H, int A,
                                   float* z, uint32_t* raw, void* stream) {
     const int n = K * H;

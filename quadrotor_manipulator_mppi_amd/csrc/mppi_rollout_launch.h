@@ -128,3 +128,25 @@ template <int MODEL, int NA, bool F64>
 inline int dispatch_geom_tt(const DevParams& p, const float* ttab, int threads, hipStream_t s) {
     return pick_geom(p, [&](auto nch, auto l) { return launch_rollout_tt<MODEL, NA, nch(), l(), F64>(p, ttab, threads, s); });
 }
+
+// The scene launch (an engine of mppi_create_scene: a scene buffer, mppi_obstacles.h): k_rollout_ob on
+// every step of a batch (no quiet form), with and without the tracking bit.  LDS as the tracking
+// kernel's plus a second run stage, the block's clearances behind its costs.
+template <int MODEL, int NA, int NCH, int LSEG, bool F64>
+inline int launch_rollout_ob(const DevParams& p, const float* ttab, float* scene, int threads, hipStream_t s) {
+    size_t lds;
+    int32_t geo;
+    if (!ttab || !scene || !rollout_block<NA, NCH, LSEG>(p, threads, p.iters, false, lds, geo)) return -1;
+    lds += (size_t)p.iters * cost_run_stride((threads / 64) * (64 / LSEG)) * sizeof(float);
+    return pick<true, false>(p.V == 1, [&](auto vone) {
+        const auto k = k_rollout_ob<MODEL, NA, NCH, LSEG, F64, vone()>;
+        static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+        return go(k, dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
+                  p.noise_mode, p.H, geo, p.u_prev, p.joints, ttab, scene, p);
+    });
+}
+
+template <int MODEL, int NA, bool F64>
+inline int dispatch_geom_ob(const DevParams& p, const float* ttab, float* scene, int threads, hipStream_t s) {
+    return pick_geom(p, [&](auto nch, auto l) { return launch_rollout_ob<MODEL, NA, nch(), l(), F64>(p, ttab, scene, threads, s); });
+}

@@ -8,3 +8,7 @@ extern "C" int mppi_launch_rollout_wb(const DevParams* p, int threads, void* str
 extern "C" int mppi_launch_rollout_wb_tt(const DevParams* p, const float* ttab, int threads, void* stream) {
     return dispatch_geom_tt<MPPI_MODEL_WHOLEBODY, 10, false>(*p, ttab, threads, (hipStream_t)stream);
 }
+// the scene kernels (k_rollout_ob; mppi_create_scene)
+extern "C" int mppi_launch_rollout_wb_ob(const DevParams* p, const float* ttab, float* scene, int threads, void* stream) {
+    return dispatch_geom_ob<MPPI_MODEL_WHOLEBODY, 10, false>(*p, ttab, scene, threads, (hipStream_t)stream);
+}

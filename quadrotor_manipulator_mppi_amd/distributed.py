@@ -241,6 +241,9 @@ class ShardedEngine:
             raise ValueError(f"exchange mode {self.mode!r}")
         self.native = self.mode != "torch"
         device = engine_kw.pop("device", 0)
+        # an engine.Scene: every rank's engine is an obstacle-avoiding one with the same body spheres
+        scene = engine_kw.pop("scene", None)
+        make_engine = lambda c: Engine(c) if scene is None else Engine(c, scene=scene)  # noqa: E731
         self.local = int(os.environ.get("LOCAL_RANK", device))
         self.local %= max(1, torch.cuda.device_count())   # more ranks than devices: wrap
         torch.cuda.set_device(self.local)
@@ -251,7 +254,7 @@ class ShardedEngine:
             cfg = make_config(device=self.local, shard_rank=0, shard_count=1, **engine_kw)
         else:
             cfg = make_config(device=self.local, shard_rank=self.rank, shard_count=self.world, **engine_kw)
-        self.engine = Engine(cfg)
+        self.engine = make_engine(cfg)
         # one dedicated stream carries rollout -> collective -> finalize (the default
         # stream's handle is 0, which mppi_set_stream reads as "engine-owned stream")
         self.stream = torch.cuda.Stream(device=self.local)
@@ -269,7 +272,7 @@ class ShardedEngine:
 
         def fresh_engine():
             self.engine.close()
-            self.engine = Engine(cfg)
+            self.engine = make_engine(cfg)
             self.engine.set_stream(self.stream.cuda_stream)
 
         if self.mode == "peer":
@@ -409,6 +412,15 @@ class ShardedEngine:
         """This rank's engine's target table (Engine.set_target_trajectory).  Every rank is given the
         same table, like the state."""
         self.engine.set_target_trajectory(pos, quat, vehicle)
+
+    def set_obstacles(self, centers=None, radii=None, velocities=None, vehicle: int = 0):
+        """This rank's engine's obstacles (Engine.set_obstacles).  Every rank is given the same set,
+        like the state."""
+        self.engine.set_obstacles(centers, radii, velocities, vehicle)
+
+    def get_clearances(self):
+        """This rank's samples' clearances (Engine.get_clearances)."""
+        return self.engine.get_clearances()
 
     def get_plan(self):
         """The nominal plan (``Engine.get_plan``): the warm start is the same on every rank, so each

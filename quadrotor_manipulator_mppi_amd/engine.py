@@ -41,6 +41,7 @@ class Plan:
     pos_err: np.ndarray   # (V, H): L1 distance of the EE / vehicle position to the target
     S: np.ndarray         # (V,)
     ee_path: np.ndarray   # (V, H, 3): the EE (arm, whole-body) or vehicle (drone, quadrotor) positions
+    clearance: Optional[np.ndarray] = None   # (V, H): min clearance to the obstacles at each step (scene engines)
 
     def first_reach(self, tol: float = 0.005):
         """The first t with pos_err < tol (check_reach's measure), -1 if none: per vehicle."""
@@ -49,7 +50,8 @@ class Plan:
         return int(t) if t.ndim == 0 else t
 
     def vehicle(self, v: int = 0) -> "Plan":
-        return Plan(self.traj[v], self.cost_t[v], self.pos_err[v], self.S[v], self.ee_path[v])
+        return Plan(self.traj[v], self.cost_t[v], self.pos_err[v], self.S[v], self.ee_path[v],
+                    None if self.clearance is None else self.clearance[v])
 
 
 @dataclass(slots=True)
@@ -66,6 +68,48 @@ class Elites:
     def vehicle(self, v: int = 0) -> "Elites":
         return Elites(self.idx[v], self.S[v], self.w[v], None if self.traj is None else self.traj[v],
                       None if self.ee_path is None else self.ee_path[v])
+
+
+@dataclass
+class Scene:
+    """The sphere scene of an obstacle-avoiding engine (``Engine(cfg, scene=...)``, mppi_create_scene):
+    the robot's body spheres -- ``(frame, (ox, oy, oz), radius)``, frame an index into the config's
+    chain joints (-1: the base transform; the only frame of a drone) -- and the term's weights
+    (project constants: w_obs = 100, margin = 0.05 m, penalty = 1e4).  Hashable by value, so it can be
+    part of an engine key."""
+    body: tuple = ()
+    w_obs: float = 100.0
+    margin: float = 0.05
+    penalty: float = 1e4
+
+    def __post_init__(self):
+        self.body = tuple((int(f), tuple(float(x) for x in o), float(r)) for f, o, r in self.body)
+
+    def __hash__(self):
+        return hash((self.body, self.w_obs, self.margin, self.penalty))
+
+    @staticmethod
+    def default(cfg: capi.Config) -> "Scene":
+        """The project's placeholder spheres for the config's model and chain (mppi_scene_default)."""
+        c = capi.Scene()
+        capi.lib().mppi_scene_default(C.byref(c), C.byref(cfg))
+        return Scene.from_c(c)
+
+    @staticmethod
+    def from_c(c: capi.Scene) -> "Scene":
+        return Scene(tuple((c.body[i].frame, tuple(c.body[i].offset), c.body[i].radius) for i in range(c.n_body)),
+                     c.w_obs, c.margin, c.penalty)
+
+    def to_c(self) -> capi.Scene:
+        if len(self.body) > capi.MAX_BODY_SPHERES:
+            raise ValueError(f"{len(self.body)} body spheres (max {capi.MAX_BODY_SPHERES})")
+        c = capi.Scene()
+        c.n_body = len(self.body)
+        for i, (f, o, r) in enumerate(self.body):
+            c.body[i].frame, c.body[i].radius = f, r
+            c.body[i].offset[:] = o
+        c.w_obs, c.margin, c.penalty = self.w_obs, self.margin, self.penalty
+        return c
 
 
 def fill_joints(cfg: capi.Config, chain: Sequence[Dict]) -> None:
@@ -183,11 +227,18 @@ def cost_term_bits(terms) -> int:
 class Engine:
     """One MPPI engine on one GPU (V vehicles x K samples x H steps)."""
 
-    def __init__(self, cfg: Optional[capi.Config] = None, **kw):
+    def __init__(self, cfg: Optional[capi.Config] = None, scene: Optional[Scene] = None, **kw):
+        """``scene``: a ``Scene`` makes this an obstacle-avoiding engine (``set_obstacles``,
+        ``get_clearances``, ``Plan.clearance``); None: the engine as before."""
         self._L = capi.lib()
         self.cfg = cfg if cfg is not None else make_config(**kw)
+        self.scene = scene
         h = C.c_void_p()
-        capi.check(self._L.mppi_create(C.byref(self.cfg), C.byref(h)), "mppi_create")
+        if scene is None:
+            capi.check(self._L.mppi_create(C.byref(self.cfg), C.byref(h)), "mppi_create")
+        else:
+            sc = scene.to_c()
+            capi.check(self._L.mppi_create_scene(C.byref(self.cfg), C.byref(sc), C.byref(h)), "mppi_create_scene")
         self._h = h
         c = self.cfg
         self.V, self.K, self.H, self.A = c.n_vehicles, c.n_samples, c.n_horizon, c.n_action
@@ -431,6 +482,26 @@ class Engine:
         capi.check(self._L.mppi_get_costs(self._h, capi.fptr(S)), "get_costs")
         return S
 
+    def set_obstacles(self, centers=None, radii=None, velocities=None, vehicle: int = 0):
+        """The sphere obstacles of one vehicle of a scene engine: ``centers`` (n, 3) world positions
+        now, ``radii`` (n,), ``velocities`` (n, 3) m/s or None for static ones; at horizon index t an
+        obstacle stands at centre + velocity (t + 1) dt.  n = 0 (or ``centers=None``) clears them."""
+        c = np.zeros((0, 3), np.float32) if centers is None else np.ascontiguousarray(centers, np.float32).reshape(-1, 3)
+        n = c.shape[0]
+        r = np.zeros(0, np.float32) if radii is None else np.ascontiguousarray(radii, np.float32).reshape(-1)
+        if r.shape[0] != n:
+            raise ValueError(f"{n} centres and {r.shape[0]} radii")
+        w = None if velocities is None else np.ascontiguousarray(velocities, np.float32).reshape(n, 3)
+        capi.check(self._L.mppi_set_obstacles(self._h, vehicle, n, capi.fptr(c), capi.fptr(r), capi.fptr(w)),
+                   "set_obstacles")
+
+    def get_clearances(self) -> np.ndarray:
+        """(V, K): every sample's min clearance to the obstacles over the horizon and the body
+        spheres (+inf without obstacles); valid as ``get_costs`` is."""
+        c = np.empty((self.V, self.K), np.float32)
+        capi.check(self._L.mppi_get_clearances(self._h, capi.fptr(c)), "get_clearances")
+        return c
+
     def get_weights(self) -> np.ndarray:
         w = np.empty((self.V, self.K), np.float32)
         capi.check(self._L.mppi_get_weights(self._h, capi.fptr(w)), "get_weights")
@@ -461,7 +532,11 @@ class Engine:
         S = np.empty(self.V, np.float32)
         capi.check(self._L.mppi_get_plan(self._h, capi.fptr(traj), capi.fptr(cost_t), capi.fptr(pos_err),
                                          capi.fptr(S)), "get_plan")
-        return Plan(traj, cost_t, pos_err, S, self._ee_path(traj))
+        clr = None
+        if self.scene is not None:   # (k_plan wrote them with the plan above; a second, small launch and copy)
+            clr = np.empty((self.V, self.H), np.float32)
+            capi.check(self._L.mppi_get_plan_clearance(self._h, capi.fptr(clr)), "get_plan_clearance")
+        return Plan(traj, cost_t, pos_err, S, self._ee_path(traj), clr)
 
     def _ee_path(self, traj: np.ndarray) -> np.ndarray:
         """(..., H, 3) positions out of (..., H, C) rows: the EE matrix's translation column (arm,

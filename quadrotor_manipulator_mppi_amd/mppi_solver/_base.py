@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import _capi as capi
-from ..engine import Engine, cost_term_bits, make_config
+from ..engine import Engine, Scene, cost_term_bits, make_config
 
 
 class OutputRing:
@@ -113,14 +113,16 @@ class SolverBase:
         """The engine made for ``key``: the one at hand, or a new one that takes over the warm
         start (and the prewarm window, mppi_set_prewarm: for a loop ticking with idle gaps)."""
         e = self._engine
-        if e is not None and key == self._engine_key:
+        full_key = (key, self._scene)   # (the scene is fixed per engine: a new one, a new engine)
+        if e is not None and full_key == self._engine_key:
             return e
         u = self._u_prev_host if e is None else e.get_u_prev()[0]
         if e is not None:
             e.close()
         cfg = self._config(key)
-        e = self._engine = Engine(cfg)
-        self._engine_key = key
+        scene = Scene.default(cfg) if self._scene is True else self._scene
+        e = self._engine = Engine(cfg) if scene is None else Engine(cfg, scene=scene)
+        self._engine_key = full_key
         e.set_u_prev(u)
         if self._prewarm_us:
             e.set_prewarm(self._prewarm_us)
@@ -193,6 +195,39 @@ class SolverBase:
                 eng.set_target_trajectory(rows[0], rows[1])
             self._rows_sent = (eng, rows)
 
+    # ------------------------------------------------------------ obstacles
+    # ``scene=`` (a constructor keyword of the arm and drone classes): an ``engine.Scene``, or True for
+    # the project's placeholder spheres (``Scene.default``), makes the engine an obstacle-avoiding one.
+    _scene = None
+    _obstacles = None      # (centers, radii, velocities) of set_obstacles; None: none
+    _obs_sent = None       # (engine, obstacles) last written (_sync_obstacles)
+
+    def set_obstacles(self, centers, radii, velocities=None) -> None:
+        """Sphere obstacles (``Engine.set_obstacles``): (n, 3) centres now, (n,) radii, (n, 3)
+        velocities or None.  Used from the next control call on, until set or cleared again."""
+        if self._scene is None:
+            raise RuntimeError("set_obstacles needs scene=... at construction")
+        c = np.ascontiguousarray(centers, np.float32).reshape(-1, 3).copy()
+        r = np.ascontiguousarray(radii, np.float32).reshape(-1).copy()
+        w = None if velocities is None else np.ascontiguousarray(velocities, np.float32).reshape(-1, 3).copy()
+        self._obstacles = (c, r, w)
+
+    def clear_obstacles(self) -> None:
+        if self._scene is None:
+            raise RuntimeError("clear_obstacles needs scene=... at construction")
+        self._obstacles = None
+
+    def _sync_obstacles(self, eng: Engine) -> None:
+        if self._scene is None:
+            return
+        obs, sent = self._obstacles, self._obs_sent
+        if sent is None or sent[0] is not eng or sent[1] is not obs:
+            if obs is None:
+                eng.set_obstacles(None)
+            else:
+                eng.set_obstacles(*obs)
+            self._obs_sent = (eng, obs)
+
     def compute_weights(self, S: torch.Tensor, _lambda) -> torch.Tensor:
         """mppi.py:173-193 / drone_mppi.py:111-130 (host helper; the engine computes the same
         weights on device)."""
@@ -227,9 +262,10 @@ class VehicleSolver(SolverBase):
     _horizon_attr = "n_timestep"
 
     def __init__(self, width: int, sigma: torch.Tensor, n_samples: int, n_timestep: int, *base_args,
-                 track_target: bool = False):
+                 track_target: bool = False, scene=None):
         super().__init__(sigma.shape[0], n_timestep, *base_args)
         self._track_target = bool(track_target)
+        self._scene = scene
         self.n_samples = n_samples
         self.n_timestep = n_timestep
         self.x_prev = torch.zeros(width)
@@ -263,6 +299,7 @@ class VehicleSolver(SolverBase):
         eng = self._ensure_engine((noise is not None or self._noise == "injected", self.n_samples, self.n_timestep))
         self._sync_target(eng, np.asarray(self.target, np.float32))
         self._sync_target_rows(eng)
+        self._sync_obstacles(eng)
         out, u0, stats = eng.step(row, noise)
         st = self._after_step(u0, stats)   # (u: the tensor is made on first read)
         if self.verbose:

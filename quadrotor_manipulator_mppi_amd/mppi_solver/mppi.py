@@ -55,7 +55,8 @@ class MPPI(SolverBase):
     def __init__(self, n_samples: int = 100, n_horizon: int = 32, device: Optional[int] = None,
                  noise: str = "philox", seed: int = 0x5EED, urdf_path: Optional[str] = None,
                  root_link: str = "base", end_link: str = "j2s7s300_link_7", verbose: bool = True,
-                 cost_terms=(), cost_weights=None, prewarm_us: int = 0, track_target: bool = False):
+                 cost_terms=(), cost_weights=None, prewarm_us: int = 0, track_target: bool = False,
+                 scene=None):
         """``track_target``: a pose target that may move along the horizon
         (``set_target_trajectory`` with (H, 7) rows xyz + xyzw, ``clear_target_trajectory``); while
         no table is set, ``target_pose`` is the target of every step as before.  ``cost_terms``: CostManager terms to switch on beyond the pose cost the
@@ -66,6 +67,9 @@ class MPPI(SolverBase):
         kinova.py:101's rospy.Rate(100); results are unchanged."""
         super().__init__(7, n_horizon, device, noise, seed, verbose, prewarm_us)
         self._track_target = bool(track_target)
+        # an engine.Scene (True: the placeholder spheres, engine.Scene.default) for obstacle avoidance:
+        # set_obstacles / clear_obstacles
+        self._scene = scene
         # mppi.py:37-42
         self.n_manipulator_dof = 7
         self.n_mobile_dof = 0
@@ -137,6 +141,7 @@ class MPPI(SolverBase):
             views = self._target_views = (pt, qt, pt.numpy(), qt.numpy())
         self._sync_target(eng, views[2], views[3])
         self._sync_target_rows(eng)
+        self._sync_obstacles(eng)
         out, u0, stats = eng.step(self._state_row(q, qd, base), noise)
         dt = np.float64 if f64 else np.float32
         self.qdes = out[0, :7].astype(dt)
