@@ -492,6 +492,45 @@ mppi_status mppi_get_clearances(mppi_engine* e, float* clr_vk);
  * and S include the obstacle term on a scene engine). */
 mppi_status mppi_get_plan_clearance(mppi_engine* e, float* clr_vh);
 
+/* ---- Distance-field environments: a voxel signed distance field as one more obstacle of a scene
+ * engine (walls, shelves, floors: what a planning stack hands over as an ESDF).  ARM, WHOLEBODY and
+ * DRONE; QUADROTOR is MPPI_ERR_INVALID_ARG, as for a scene.
+ *
+ * The field is engine-wide: one world, shared by all V vehicles.  It is a nodal grid d[iz][iy][ix]
+ * of fp32 signed distances in metres (negative inside), C order (nz, ny, nx); node (ix, iy, iz)
+ * stands at origin + voxel (ix, iy, iz) in world axes.  Dims and voxel are fixed at creation; the
+ * data and the origin are replaceable (a local map window that moves with the vehicle).
+ * Sampling at a world point c: u = (c - origin) (1 / voxel), clamped per axis to [0, n - 1];
+ * i = min(floor(u), n - 2), f = u - i; trilinear interpolation of the 8 nodes, x, then y, then z,
+ * each lerp a + f (b - a).  A point outside the grid reads the value at its clamped position -- the
+ * field does not extrapolate, so pad the grid by the distance the robot may leave it.  The clamp
+ * comes before the integer conversion and maps NaN and +-inf coordinates onto the grid: no input
+ * can form an address outside it.
+ * The term: for body sphere b at row t, g_b,field = d(c_b(k,t)) - r_b joins the obstacle
+ * accumulators above as one more obstacle:
+ *   x_obs(k,t) = w_obs sum_{b, o in obstacles U {field}} max(0, margin - g_bo) + penalty [min g < 0]
+ * and clr_k, the plan's cost_t, S and mppi_get_plan_clearance take the min / sum over the same
+ * set.  No new weights; the field is static over the horizon and over a batch.  Before a field is
+ * set, and after it is cleared, it contributes nothing (the engine equals a scene engine). */
+#define MPPI_FIELD_MAX_VOXELS (1 << 21)
+typedef struct { int32_t dims[3];   /* nx, ny, nz: each 2..512, product <= MPPI_FIELD_MAX_VOXELS */
+                 float voxel;       /* m, > 0 */
+                 float origin[3];
+                 int32_t reserved;  /* 0 (the struct is 32 bytes) */ } mppi_field_desc;
+/* mppi_create_scene with a field of these dims (scene NULL: mppi_scene_default).  The field buffer
+ * and its pinned staging copy are allocated here; the field starts cleared.  MPPI_ERR_INVALID_ARG:
+ * what mppi_create_scene refuses, a NULL descriptor, dims outside 2..512 or their product past
+ * MPPI_FIELD_MAX_VOXELS, a voxel that is not finite and > 0, a non-finite origin.  Runs the field
+ * kernels (k_rollout_df; no quiet form). */
+mppi_status mppi_create_scene_field(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field,
+                                    mppi_engine** out);
+/* Replaces the field: origin3 (NULL: keep the current one), d_zyx (nz,ny,nx) (NULL: clear -- the
+ * field contributes nothing until the next set).  MPPI_ERR_STATE on an engine not created by
+ * mppi_create_scene_field; MPPI_ERR_INVALID_ARG for a non-finite origin or value.  The data is
+ * packed into the engine's staging memory (the caller's array is free on return) and uploaded on
+ * the engine's stream, ordered before the next step on either dispatch path; no allocation. */
+mppi_status mppi_set_distance_field(mppi_engine* e, const float* origin3, const float* d_zyx);
+
 #define MPPI_MAX_ELITES 64
 /* The n lowest-cost samples of the last rollout of every vehicle, best first (synchronous).
  *   idx  (V,n) int32   sample index within this engine's K (a shard: local; global = shard_rank*K + idx)

@@ -69,6 +69,13 @@ class Scene(C.Structure):
                 ("w_obs", C.c_float), ("margin", C.c_float), ("penalty", C.c_float)]
 
 
+FIELD_MAX_VOXELS = 1 << 21
+
+
+class FieldDesc(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("voxel", C.c_float), ("origin", C.c_float * 3), ("reserved", C.c_int32)]
+
+
 class Link(C.Structure):
     _fields_ = [("parent", C.c_int32), ("type", C.c_int32), ("xyz", C.c_double * 3), ("rpy", C.c_double * 3),
                 ("axis", C.c_double * 3), ("mass", C.c_double), ("com", C.c_double * 3),
@@ -147,6 +154,8 @@ PROTOTYPES = {
     "mppi_set_obstacles": (_ST, [_P, C.c_int32, C.c_int32, _F, _F, _F]),
     "mppi_get_clearances": (_ST, [_P, _F]),
     "mppi_get_plan_clearance": (_ST, [_P, _F]),
+    "mppi_create_scene_field": (_ST, [_CFG, C.POINTER(Scene), C.POINTER(FieldDesc), C.POINTER(_P)]),
+    "mppi_set_distance_field": (_ST, [_P, _F, _F]),
     "mppi_enable_timing": (_ST, [_P, C.c_int32]),
     "mppi_get_timing": (_ST, [_P, _D, _D, _I64, _I64]),
     "mppi_kernel_timing": (_ST, [_P, C.c_int32, _D, _D]),
@@ -176,6 +185,11 @@ DEBUG_PROTOTYPES = {
     "mppi_debug_scene_rollout_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_char_p, C.c_int32]),
     "mppi_debug_scene_layout": (C.c_int32, [_CFG, C.POINTER(Scene), _F, _I32]),
     "mppi_debug_obstacles": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, _F, _F, _F, _F]),
+    "mppi_debug_field_layout": (C.c_int32, [_CFG, C.POINTER(FieldDesc), _F, _F, _F]),
+    "mppi_debug_field_sample": (C.c_int32, [_F, C.c_int32, _F, _F, _I32]),
+    "mppi_debug_field_step_launches": (C.c_int32, [_CFG, C.POINTER(Scene), C.POINTER(FieldDesc), _I32, C.c_char_p,
+                                                   C.c_int32, C.POINTER(C.c_uint64)]),
+    "mppi_debug_field_rollout_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_char_p, C.c_int32]),
 }
 
 _lib = None

@@ -22,9 +22,9 @@ std::string fin_symbol(const FinParams& f, LaunchDesc* desc) {
     if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
-std::string roll_symbol(const DevParams& p, int threads, LaunchDesc* desc, const float* ttab, float* scene) {
+std::string roll_symbol(const DevParams& p, int threads, LaunchDesc* desc, const float* ttab, float* scene, const float* field) {
     LaunchDesc d{};
-    const int rc = describe(p, threads, &d, ttab, scene);
+    const int rc = describe(p, threads, &d, ttab, scene, field);
     if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
@@ -232,7 +232,8 @@ int32_t mppi_debug_queue_ring(mppi_engine* e) {
 // lds <bytes> args <bytes> fnv <FNV-1a 64 of the argument bytes>" -- for a step before the last
 // (n > 1) and for the last step.  A path the engine would not take is refused (mppi_last_error says
 // why).  tests/test_capi_step_launches_cpu.py.
-static int32_t step_launches(const mppi_config* cfg, const int32_t* sw, char* buf, int32_t len, const mppi_scene* scene) {
+static int32_t step_launches(const mppi_config* cfg, const int32_t* sw, char* buf, int32_t len, const mppi_scene* scene,
+                             const mppi_field_desc* field = nullptr, uint64_t* field_arg = nullptr) {
     if (!cfg || !sw || !buf || len <= 0 || sw[0] < 0 || sw[0] > 3 || sw[1] < 1)
         return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_step_launches: bad arguments");
     mppi_status st = validate(*cfg);
@@ -263,6 +264,13 @@ static int32_t step_launches(const mppi_config* cfg, const int32_t* sw, char* bu
         e->has_scene = true;
         e->d_ttab = (float*)stand_in(0x6000);
         e->d_scene = (float*)stand_in(0x7000);
+    }
+    if (field) {   // a field engine's (mppi_create_scene_field; with a scene): its field buffer
+        if (!scene) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_field_step_launches: a field engine has a scene");
+        if ((st = field_validate(field)) != MPPI_OK) return st;
+        e->has_field = true;
+        e->field = *field;
+        e->d_field = (float*)stand_in(0x8000);
     }
     std::vector<VehicleConst> vc((size_t)e->V);
     e->h_vc = vc.data();
@@ -301,7 +309,8 @@ static int32_t step_launches(const mppi_config* cfg, const int32_t* sw, char* bu
         const StepPath sp = path < 2 ? StepPath::Hip : path == 2 ? StepPath::Batch : StepPath::Call;
         DevParams p = rollout_params(e, sp, noise, !last);
         if (sp == StepPath::Hip) p.step_ctr = (uint32_t)i;   // (rollout_impl: the launch's own)
-        report(last, "rollout", describe(p, e->threads, &d, e->d_ttab, e->d_scene), d);
+        report(last, "rollout", describe(p, e->threads, &d, e->d_ttab, e->d_scene, e->d_field), d);
+        if (field_arg) std::memcpy(field_arg, d.args + kRollFieldOff, sizeof(*field_arg));   // (the last rollout's)
         if (sp == StepPath::Hip && sharded(e)) {
             const FinParams f = finalize_params(e, FinKind::Pack);
             report(last, "pack", describe(f, &d), d);
@@ -328,8 +337,25 @@ int32_t mppi_debug_scene_step_launches(const mppi_config* cfg, const mppi_scene*
     return step_launches(cfg, sw, buf, len, scene);
 }
 
+// Likewise for an engine of mppi_create_scene_field(cfg, scene, field); field_arg (may be null): the 8 bytes
+// at the field pointer's offset (kRollFieldOff) of the last rollout's argument block -- the stand-in
+// field buffer is at 0x8000.  tests/test_capi_field_cpu.py.
+int32_t mppi_debug_field_step_launches(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field,
+                                       const int32_t* sw, char* buf, int32_t len, uint64_t* field_arg) {
+    if (!scene || !field) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_field_step_launches: bad arguments");
+    return step_launches(cfg, sw, buf, len, scene, field, field_arg);
+}
+
+static int32_t scene_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len, bool field);
 // mppi_debug_rollout_kernels for a scene engine's launches (same g): the scene kernel into both.
 int32_t mppi_debug_scene_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len) {
+    return scene_rollout_kernels(g, full, quiet, len, false);
+}
+// and for a field engine's: the field kernel into both.
+int32_t mppi_debug_field_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len) {
+    return scene_rollout_kernels(g, full, quiet, len, true);
+}
+static int32_t scene_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len, bool field) {
     if (!g || !full || !quiet || len <= 0) return MPPI_ERR_INVALID_ARG;
     DevParams p;
     std::memset(&p, 0, sizeof(p));
@@ -341,9 +367,9 @@ int32_t mppi_debug_scene_rollout_kernels(const int32_t* g, char* full, char* qui
     p.kern = g[14] ? kRollKernGeneric : 0;
     static float nowhere[4];   // described, not run: any non-null table and scene
     LaunchDesc da{}, db{};
-    const std::string a = roll_symbol(p, g[6], &da, nowhere, nowhere);
+    const std::string a = roll_symbol(p, g[6], &da, nowhere, nowhere, field ? nowhere : nullptr);
     p.kern = quiet_roll_kern(p.kern, g[14] ? kGenericAll : 0, false, g[13] != 0, false);
-    const std::string b = roll_symbol(p, g[6], &db, nowhere, nowhere);
+    const std::string b = roll_symbol(p, g[6], &db, nowhere, nowhere, field ? nowhere : nullptr);
     snprintf(full, (size_t)len, "%s", a.c_str());
     snprintf(quiet, (size_t)len, "%s", b.c_str());
     note_launches(da, db, g_roll_launch);

@@ -149,6 +149,8 @@ constexpr int32_t kNoiseOverlap = 0x200;
 // seed_hi, step, ...) of every rollout kernel (mppi_rollout.h, mppi_rollout_quad.hip: their
 // launchers assert it).  Native dispatch rewrites it per batch or call.
 constexpr uint32_t kRollStepOff = 8;
+// the field rollout's field pointer (k_rollout_df): after seven 4-byte scalars and four pointers
+constexpr uint32_t kRollFieldOff = 64;
 
 // The finalize tail's parameters, device-resident: written once at create (one copy per
 // launch kind), read by k_finalize through a preloaded pointer.  Read from the kernel
@@ -269,6 +271,7 @@ struct PlanParams {
                              //   cost_t, pos_err and S against the vehicle's fixed target
     float* scene;            // a scene engine's buffer (mppi_obstacles.h), else null: the obstacle term in cost_t
                              //   and S, the steps' clearances (V,H) written at its plan offset
+    const float* field;      // a field engine's buffer (mppi_field.h; with scene), else null: one more obstacle in that term
 };
 
 // Finalize / pack kernel parameters.
@@ -336,6 +339,12 @@ int mppi_launch_rollout_arm64_ob(const mppi::DevParams* p, const float* ttab, fl
 int mppi_launch_rollout_arm64_h32_ob(const mppi::DevParams* p, const float* ttab, float* scene, int block_threads, void* stream);
 int mppi_launch_rollout_arm32_ob(const mppi::DevParams* p, const float* ttab, float* scene, int block_threads, void* stream);
 int mppi_launch_rollout_wb_ob(const mppi::DevParams* p, const float* ttab, float* scene, int block_threads, void* stream);
+// the field rollouts (an engine of mppi_create_scene_field): field = the field buffer (mppi_field.h)
+int mppi_launch_rollout_field(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int block_threads, void* stream);
+int mppi_launch_rollout_arm64_df(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int block_threads, void* stream);
+int mppi_launch_rollout_arm64_h32_df(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int block_threads, void* stream);
+int mppi_launch_rollout_arm32_df(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int block_threads, void* stream);
+int mppi_launch_rollout_wb_df(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int block_threads, void* stream);
 int mppi_launch_finalize(const mppi::FinParams* p, void* stream);
 int mppi_launch_plan(const mppi::DevParams* p, const mppi::PlanParams* pp, void* stream);
 int mppi_launch_peer_probe(unsigned long long* const* peers, unsigned long long* local, int n, int me,

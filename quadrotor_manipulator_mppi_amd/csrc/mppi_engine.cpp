@@ -290,6 +290,12 @@ static mppi_status allocate(mppi_engine* e) {
         HIP_TRY(hipHostMalloc((void**)&e->h_scene, sizeof(float) * (size_t)e->V * kSceneObsW, hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&e->ev_scene, hipEventDisableTiming));
     }
+    if (e->has_field) {   // the field buffer and its pinned staging copy (header and cells), the uploads' event
+        const size_t bytes = sizeof(float) * (size_t)field_words(field_voxels(e->field));
+        HIP_TRY(hipMalloc(&e->d_field, bytes));
+        HIP_TRY(hipHostMalloc((void**)&e->h_field, bytes, hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&e->ev_field, hipEventDisableTiming));
+    }
     if (c.cost_terms & ~MPPI_COST_TARGET_TRACK) {   // Sigma^-1, gamma^t, tracking target
         HIP_TRY(hipMalloc(&e->d_sinv, sizeof(float) * e->A * e->A));
         HIP_TRY(hipMalloc(&e->d_gamma, sizeof(float) * e->H));
@@ -350,6 +356,12 @@ static mppi_status upload(mppi_engine* e) {
         std::memset(e->h_scene, 0, sizeof(float) * (size_t)e->V * kSceneObsW);
         e->batch.scene = e->call.scene = e->d_scene;
     }
+    if (e->d_field) {   // cleared: the header with the set flag off, zero cells
+        std::memset(e->h_field, 0, sizeof(float) * (size_t)field_words(field_voxels(e->field)));
+        field_header(e->field, e->field.origin, false, e->h_field);
+        HIP_TRY(hipMemcpy(e->d_field, e->h_field, sizeof(float) * (size_t)field_words(field_voxels(e->field)), hipMemcpyHostToDevice));
+        e->batch.field = e->call.field = e->d_field;
+    }
     if (c.cost_terms & ~MPPI_COST_TARGET_TRACK) {
         HIP_TRY(hipMemcpy(e->d_sinv, e->sinv.data(), sizeof(float) * e->sinv.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(e->d_gamma, e->gamma_t.data(), sizeof(float) * e->gamma_t.size(), hipMemcpyHostToDevice));
@@ -367,16 +379,34 @@ static mppi_status upload(mppi_engine* e) {
 
 using namespace mppi_host;
 
+static mppi_status create_engine(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field, mppi_engine** out);
+
 extern "C" {
 
 mppi_status mppi_create(const mppi_config* cfg, mppi_engine** out) { return mppi_create_scene(cfg, nullptr, out); }
 
 mppi_status mppi_create_scene(const mppi_config* cfg, const mppi_scene* scene, mppi_engine** out) {
+    return create_engine(cfg, scene, nullptr, out);
+}
+
+mppi_status mppi_create_scene_field(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field,
+                                    mppi_engine** out) {
+    if (!cfg || !out) return fail(MPPI_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    mppi_status st = validate(*cfg);
+    if (st != MPPI_OK) return st;
+    mppi_scene use;
+    if ((st = field_engine_validate(*cfg, scene, field, use)) != MPPI_OK) return st;
+    return create_engine(cfg, &use, field, out);
+}
+
+static mppi_status create_engine(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field, mppi_engine** out) {
     if (!cfg || !out) return fail(MPPI_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     mppi_status st = validate(*cfg);
     if (st != MPPI_OK) return st;
     if (scene && (st = scene_validate(*cfg, *scene)) != MPPI_OK) return st;
+    if (field && (st = field_validate(field)) != MPPI_OK) return st;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (cfg->device < 0 || cfg->device >= ndev)
@@ -387,6 +417,10 @@ mppi_status mppi_create_scene(const mppi_config* cfg, const mppi_scene* scene, m
         lay.has_scene = true;
         lay.scene_body.assign(kSceneBodyW, 0.0f);
         scene_body_table(lay, *scene, lay.scene_body.data(), nullptr);
+    }
+    if (field) {
+        lay.has_field = true;
+        lay.field = *field;
     }
 
     mppi_engine* e = new mppi_engine();
@@ -447,7 +481,7 @@ void mppi_destroy(mppi_engine* e) {
     exchange_release(e);   // the communicator and the other ranks' mapped regions
     void* dev[] = {e->d_xregion, e->d_xpeers, e->d_sigma, e->d_joints, e->d_vc, e->d_u_prev, e->d_noise_in, e->d_traj, e->d_noise_out,
                    e->d_S, e->d_hdr, e->d_rdata, e->d_out, e->d_wraw, e->d_wsmooth, e->d_w,
-                   e->d_sinv, e->d_gamma, e->d_jtraj, e->d_ttab, e->d_scene, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec,
+                   e->d_sinv, e->d_gamma, e->d_jtraj, e->d_ttab, e->d_scene, e->d_field, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec,
                    e->d_plan_vc, e->d_plan, e->d_elite_cand, e->d_elites};
     for (void* p : dev) if (p) (void)hipFree(p);
     if (e->h_out) (void)hipHostFree(e->h_out);
@@ -457,6 +491,8 @@ void mppi_destroy(mppi_engine* e) {
     if (e->ev_tt) (void)hipEventDestroy(e->ev_tt);
     if (e->h_scene) (void)hipHostFree(e->h_scene);
     if (e->ev_scene) (void)hipEventDestroy(e->ev_scene);
+    if (e->h_field) (void)hipHostFree(e->h_field);
+    if (e->ev_field) (void)hipEventDestroy(e->ev_field);
     if (e->h_elites) (void)hipHostFree(e->h_elites);
     if (e->ev_vc) (void)hipEventDestroy(e->ev_vc);
     if (e->ev_out) (void)hipEventDestroy(e->ev_out);
@@ -590,14 +626,14 @@ mppi_status mppi_kernel_timing_ex(mppi_engine* e, int32_t n, double* rollout_us,
     for (auto& x : ev) KT_TRY(hipEventCreate(&x));
     KT_TRY(hipMemcpyAsync(saved, e->d_u_prev, ub, hipMemcpyDeviceToDevice, e->stream));
     KT_TRY(hipEventRecord(ev[0], e->stream));
-    for (int i = 0; i < n && rc == 0; ++i) rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene);
+    for (int i = 0; i < n && rc == 0; ++i) rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field);
     KT_TRY(hipEventRecord(ev[1], e->stream));
     for (int i = 0; i < n && rc == 0; ++i) rc = mppi_launch_finalize(&f, e->stream);
     KT_TRY(hipEventRecord(ev[2], e->stream));
     // the kernels as a control step runs them: rollout after finalize (u_prev and the
     // records just written, cold in the other XCDs' L2)
     for (int i = 0; i < n && rc == 0 && pair_us; ++i) {
-        rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene);
+        rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field);
         if (rc == 0) rc = mppi_launch_finalize(&f, e->stream);
     }
     KT_TRY(hipEventRecord(ev[3], e->stream));
@@ -634,9 +670,9 @@ extern "C" mppi_status mppi_probe_sequence(mppi_engine* e, int32_t n, int32_t mo
     (void)hipEventCreate(&a); (void)hipEventCreate(&b);
     (void)hipEventRecord(a, e->stream);
     for (int i = 0; i < n; ++i) {
-        if (mode <= 2 || mode == 5) launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene);
+        if (mode <= 2 || mode == 5) launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field);
         if (mode == 0 || mode == 3) mppi_launch_boundary((float*)e->d_out, fb, e->stream);
-        if (mode == 1 || mode == 4) launch_rollout(p1, e->d_ttab, e->threads, e->stream, e->d_scene);
+        if (mode == 1 || mode == 4) launch_rollout(p1, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field);
         if (mode == 2) mppi_launch_finalize(&f, e->stream);
     }
     (void)hipEventRecord(b, e->stream);
@@ -677,6 +713,28 @@ mppi_status mppi_set_obstacles(mppi_engine* e, int32_t v, int32_t n, const float
                            hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipEventRecord(e->ev_scene, e->stream));
     e->scene_pending = true;
+    return MPPI_OK;
+}
+
+// The engine's distance field: validated, packed into the pinned staging copy (header, then -- with data --
+// the cells) and uploaded as the obstacles are.  A clear or an origin-only change moves the header alone.
+mppi_status mppi_set_distance_field(mppi_engine* e, const float* origin3, const float* d_zyx) {
+    if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
+    if (!e->d_field) return fail(MPPI_ERR_STATE, "engine created without a field (mppi_create_scene_field)");
+    mppi_status st = field_data_validate(e->field, origin3, d_zyx);
+    if (st != MPPI_OK) return st;
+    if (use_device(e)) return MPPI_ERR_HIP;
+    if (e->field_pending) {   // the previous copy out of the staging buffer must be done
+        HIP_TRY(hipEventSynchronize(e->ev_field));
+        e->field_pending = false;
+    }
+    if (origin3) std::memcpy(e->field.origin, origin3, sizeof(e->field.origin));
+    field_header(e->field, e->field.origin, d_zyx != nullptr, e->h_field);
+    if (d_zyx) field_pack(e->field, d_zyx, e->h_field + kFieldHdrW);
+    const size_t words = d_zyx ? (size_t)field_words(field_voxels(e->field)) : (size_t)kFieldHdrW;
+    HIP_TRY(hipMemcpyAsync(e->d_field, e->h_field, sizeof(float) * words, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipEventRecord(e->ev_field, e->stream));
+    e->field_pending = true;
     return MPPI_OK;
 }
 
@@ -767,6 +825,7 @@ mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos
     pp.vc = e->d_plan_vc;
     pp.ttab = e->d_ttab;
     pp.scene = e->d_scene;
+    pp.field = e->d_field;
     pp.traj = e->d_plan; pp.cost_t = pp.traj + n_traj; pp.pos_err = pp.cost_t + n_vh; pp.S = pp.pos_err + n_vh;
     HIP_TRY(hipMemcpyAsync(e->d_plan_vc, e->h_vc, sizeof(VehicleConst) * V, hipMemcpyHostToDevice, e->stream));
     const int rc = mppi_launch_plan(&e->dp, &pp, e->stream);

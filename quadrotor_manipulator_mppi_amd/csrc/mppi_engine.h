@@ -55,6 +55,7 @@ struct DescCache {
     mppi::LaunchDesc roll{}, fin{}, roll_quiet{}, fin_quiet{};
     const float* ttab = nullptr;   // a tracking engine's target table (its rollouts' extra argument; fixed per engine)
     float* scene = nullptr;        // a scene engine's buffer (likewise)
+    const float* field = nullptr;  // a field engine's field buffer (likewise)
     // ignore_vc0: the vehicle constants (the state) may differ -- a control call patches them in
     bool matches(const mppi::DevParams& p, const mppi::FinParams& f, int threads, bool ignore_vc0) const;
     // describes (p, f) and, where given, the quiet pair; the launchers' status (0: valid again)
@@ -127,6 +128,13 @@ struct mppi_engine : mppi_host::EngineLayout {
     float* h_scene = nullptr;
     hipEvent_t ev_scene = nullptr;
     bool scene_pending = false;
+    // the distance field of a field engine (mppi_create_scene_field; else none; such an engine has a scene):
+    // the device buffer (mppi_field.h: header, cells), its pinned staging copy of the same size, both
+    // allocated at creation, and the event recorded behind the last upload
+    float* d_field = nullptr;
+    float* h_field = nullptr;
+    hipEvent_t ev_field = nullptr;
+    bool field_pending = false;
     float* d_exchange = nullptr;
     // mppi_get_plan's buffers (allocated at its first call): the host's vehicle constants; the
     // planes (V,C,H), cost_t (V,H), pos_err (V,H) and S (V) in one block, and its pinned host copy
@@ -294,12 +302,16 @@ inline int32_t quiet_roll_kern(int32_t kern, int generic, bool diag, bool peer, 
 // The rollout's launch: the tracking kernels (cost_terms & MPPI_COST_TARGET_TRACK) take the engine's
 // target table as an extra argument; every other launch is mppi_launch_rollout's.
 // A scene engine's (scene non-null) run the scene kernels, with or without the tracking bit.
-inline int launch_rollout(const mppi::DevParams& p, const float* ttab, int threads, void* stream, float* scene = nullptr) {
+// A field engine's (field non-null, with its scene) run the field kernels.
+inline int launch_rollout(const mppi::DevParams& p, const float* ttab, int threads, void* stream, float* scene = nullptr,
+                          const float* field = nullptr) {
+    if (field) return mppi_launch_rollout_field(&p, ttab, scene, field, threads, stream);
     if (scene) return mppi_launch_rollout_scene(&p, ttab, scene, threads, stream);
     return (p.cost_terms & MPPI_COST_TARGET_TRACK) ? mppi_launch_rollout_track(&p, ttab, threads, stream)
                                                    : mppi_launch_rollout(&p, threads, stream);
 }
-int describe(const mppi::DevParams& p, int threads, mppi::LaunchDesc* d, const float* ttab = nullptr, float* scene = nullptr);
+int describe(const mppi::DevParams& p, int threads, mppi::LaunchDesc* d, const float* ttab = nullptr, float* scene = nullptr,
+             const float* field = nullptr);
 int describe(const mppi::FinParams& f, mppi::LaunchDesc* d);
 // -------------------------------------------------------------- step (mppi_step.cpp)
 // why this engine's steps cannot go native (nullptr: they can).  A batch may carry the stamps /
@@ -311,7 +323,7 @@ const char* aql_ineligible(const mppi_engine* e, bool batch = false);
 // the symbol a launch would run, by the launchers' own description of it ("?": none)
 std::string fin_symbol(const mppi::FinParams& f, mppi::LaunchDesc* desc = nullptr);
 std::string roll_symbol(const mppi::DevParams& p, int threads, mppi::LaunchDesc* desc = nullptr, const float* ttab = nullptr,
-                        float* scene = nullptr);
+                        float* scene = nullptr, const float* field = nullptr);
 
 // ------------------------------------------------------ exchange (mppi_exchange.cpp)
 // RCCL, resolved at the first mppi_comm_* call (dlopen: the library loads and its single-GPU

@@ -291,6 +291,72 @@ void obstacles_fill(float* block, int n, const float* center, const float* radiu
     }
 }
 
+// ------------------------------------------------------------------ the distance field
+mppi_status field_validate(const mppi_field_desc* f) {
+    if (!f) return fail(MPPI_ERR_INVALID_ARG, "field: null descriptor");
+    int64_t nvox = 1;
+    for (int d = 0; d < 3; ++d) {
+        if (f->dims[d] < 2 || f->dims[d] > kFieldMaxDim)
+            return fail(MPPI_ERR_INVALID_ARG, "field: dims[%d] = %d outside 2..%d", d, f->dims[d], kFieldMaxDim);
+        nvox *= f->dims[d];
+    }
+    if (nvox > MPPI_FIELD_MAX_VOXELS)
+        return fail(MPPI_ERR_INVALID_ARG, "field: %lld voxels, more than MPPI_FIELD_MAX_VOXELS", (long long)nvox);
+    if (!std::isfinite(f->voxel) || !(f->voxel > 0.0f) || !std::isfinite(1.0f / f->voxel))
+        return fail(MPPI_ERR_INVALID_ARG, "field: voxel %g is not finite and > 0", f->voxel);
+    for (int d = 0; d < 3; ++d)
+        if (!std::isfinite(f->origin[d])) return fail(MPPI_ERR_INVALID_ARG, "field: non-finite origin");
+    if (f->reserved != 0) return fail(MPPI_ERR_INVALID_ARG, "field: reserved word %d is not 0", f->reserved);
+    return MPPI_OK;
+}
+
+mppi_status field_engine_validate(const mppi_config& c, const mppi_scene* scene, const mppi_field_desc* f, mppi_scene& use) {
+    if (!f) return fail(MPPI_ERR_INVALID_ARG, "field: null descriptor");
+    if (scene) use = *scene;
+    else mppi_scene_default(&use, &c);
+    mppi_status st = scene_validate(c, use);
+    if (st != MPPI_OK) return st;
+    return field_validate(f);
+}
+
+mppi_status field_data_validate(const mppi_field_desc& f, const float* origin3, const float* d_zyx) {
+    for (int d = 0; origin3 && d < 3; ++d)
+        if (!std::isfinite(origin3[d])) return fail(MPPI_ERR_INVALID_ARG, "mppi_set_distance_field: non-finite origin");
+    const int64_t nvox = field_voxels(f);
+    for (int64_t i = 0; d_zyx && i < nvox; ++i)
+        if (!std::isfinite(d_zyx[i]))
+            return fail(MPPI_ERR_INVALID_ARG, "mppi_set_distance_field: non-finite value at voxel %lld", (long long)i);
+    return MPPI_OK;
+}
+
+void field_header(const mppi_field_desc& f, const float* origin3, bool set, float* hdr) {
+    std::memset(hdr, 0, sizeof(float) * kFieldHdrW);
+    const auto put = [&](int i, int32_t x) { std::memcpy(hdr + i, &x, sizeof(x)); };
+    for (int d = 0; d < 3; ++d) {
+        hdr[d] = origin3[d];
+        put(4 + d, f.dims[d]);
+    }
+    hdr[3] = 1.0f / f.voxel;
+    put(7, set ? 1 : 0);
+    put(8, f.dims[0]);
+    put(9, f.dims[0] * f.dims[1]);
+    put(10, (int32_t)field_voxels(f));
+    hdr[11] = f.voxel;
+}
+
+void field_pack(const mppi_field_desc& f, const float* d_zyx, float* cells) {
+    const int nx = f.dims[0];
+    const int64_t rows = (int64_t)f.dims[1] * f.dims[2];
+    for (int64_t r = 0; r < rows; ++r) {
+        const float* src = d_zyx + r * nx;
+        float* dst = cells + 2 * r * nx;
+        for (int x = 0; x < nx; ++x) {
+            dst[2 * x] = src[x];
+            dst[2 * x + 1] = src[x + 1 < nx ? x + 1 : nx - 1];
+        }
+    }
+}
+
 void set_generic(EngineLayout& l, int generic) {
     l.generic = generic;
     l.fp.kern = (generic & 1) ? kFinKernGeneric : 0;
@@ -343,6 +409,35 @@ extern "C" int32_t mppi_debug_obstacles(int32_t n_vehicles, int32_t vehicle, int
     const mppi_status st = obstacles_validate(n_vehicles, vehicle, n, center, radius, vel);
     if (st == MPPI_OK && block) obstacles_fill(block, n, center, radius, vel);
     return st;
+}
+
+// Diagnostic (no GPU): the errors of mppi_create_scene_field's descriptor and mppi_set_distance_field's
+// arrays (either may be null), and (words non-null) the buffer they make: field_words(nvox) words, the
+// header -- set when d_zyx is given -- then the cells.  tests/test_capi_field_cpu.py.
+extern "C" int32_t mppi_debug_field_layout(const mppi_config* cfg, const mppi_field_desc* field, const float* origin3,
+                                           const float* d_zyx, float* words) {
+    if (!cfg) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_field_layout: bad arguments");
+    mppi_status st = validate(*cfg);
+    if (st != MPPI_OK) return st;
+    mppi_scene use;
+    if ((st = field_engine_validate(*cfg, nullptr, field, use)) != MPPI_OK) return st;   // (as mppi_create_scene_field with a null scene)
+    if ((st = field_data_validate(*field, origin3, d_zyx)) != MPPI_OK) return st;
+    if (words) {
+        field_header(*field, origin3 ? origin3 : field->origin, d_zyx != nullptr, words);
+        if (d_zyx) field_pack(*field, d_zyx, words + kFieldHdrW);
+        else std::memset(words + kFieldHdrW, 0, sizeof(float) * 2 * (size_t)field_voxels(*field));
+    }
+    return MPPI_OK;
+}
+
+// Diagnostic (no GPU): field_sample, the kernels' own inline, on n points (n, 3) over a packed buffer
+// (mppi_debug_field_layout's words): the values (n) and the eight nodes' linear indices (n, 8).
+extern "C" int32_t mppi_debug_field_sample(const float* words, int32_t n, const float* pts, float* val, int32_t* idx8) {
+    if (!words || n < 0 || (n > 0 && (!pts || !val))) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_field_sample: bad arguments");
+    for (int32_t i = 0; i < n; ++i)
+        val[i] = mppi::field_sample(words, words + kFieldHdrW, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2],
+                                    idx8 ? idx8 + 8 * (size_t)i : nullptr);
+    return MPPI_OK;
 }
 
 // Diagnostic (not part of the public header): the layout of a configuration without a device.

@@ -7,6 +7,7 @@
 
 #include "mppi_dev.h"
 #include "mppi_obstacles.h"
+#include "mppi_field.h"
 
 // mppi_engine::generic with every part switched back (MPPI_GENERIC_KERNELS=1)
 constexpr int kGenericAll = 15;
@@ -51,6 +52,8 @@ struct EngineLayout {
     std::vector<float> sinv, gamma_t;   // cost_terms: Sigma^-1 (A,A) and gamma^t (H), else empty
     bool has_scene = false;             // mppi_create_scene: the scene kernels; its body table (kSceneBodyW words)
     std::vector<float> scene_body;
+    bool has_field = false;             // mppi_create_scene_field (with has_scene): the field kernels; its descriptor
+    mppi_field_desc field{};
     int fin_ts = 1, fin_tsz = 8;        // finalize t-slices
     int generic = 0;                    // MPPI_GENERIC_KERNELS=1 (tests, A/B): the kernels as before the role and
                                         // fixed-block ones.  Bits: 1 the finalize of every role with run-time
@@ -74,6 +77,19 @@ mppi_status scene_validate(const mppi_config& c, const mppi_scene& s);
 void scene_body_table(const EngineLayout& l, const mppi_scene& s, float* table, int* order);
 mppi_status obstacles_validate(int n_vehicles, int vehicle, int n, const float* center, const float* radius, const float* vel);
 void obstacles_fill(float* block, int n, const float* center, const float* radius, const float* vel);
+// ------------------------------------------------- the distance field (mppi_layout.cpp; mppi_field.h)
+// field_validate: the descriptor's errors of mppi_create_scene_field (the model's are scene_validate's).
+// field_data_validate: those of mppi_set_distance_field's arrays (either may be null).
+// field_header: the kFieldHdrW header words for a descriptor, an origin and the set flag.
+// field_pack: d (nz, ny, nx) into the x-pair cells (2 * nvox words).
+inline int64_t field_voxels(const mppi_field_desc& f) { return (int64_t)f.dims[0] * f.dims[1] * f.dims[2]; }
+mppi_status field_validate(const mppi_field_desc* f);
+// the whole of mppi_create_scene_field's argument check after validate(): the scene (null: the default one,
+// returned in `use`) through scene_validate -- which refuses QUADROTOR -- then the descriptor
+mppi_status field_engine_validate(const mppi_config& c, const mppi_scene* scene, const mppi_field_desc* f, mppi_scene& use);
+mppi_status field_data_validate(const mppi_field_desc& f, const float* origin3, const float* d_zyx);
+void field_header(const mppi_field_desc& f, const float* origin3, bool set, float* hdr);
+void field_pack(const mppi_field_desc& f, const float* d_zyx, float* cells);
 // the MPPI_GENERIC_KERNELS bits (EngineLayout::generic) and what they set in dp and fp
 void set_generic(EngineLayout& l, int generic);
 

@@ -17,6 +17,7 @@
 #include "mppi_fk.h"
 #include "mppi_integrator.h"   // seg_scan_f32_multi
 #include "mppi_obstacles.h"
+#include "mppi_field.h"
 #include "mppi_quad_step.h"
 
 namespace {
@@ -163,7 +164,7 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     __shared__ VehicleConst vcv;
     __shared__ float tot1[kMaxWaves][NA], tot2[kMaxWaves][NA];   // the waves' scan totals (the chunk carries)
     __shared__ float wsum[kMaxWaves];
-    __shared__ __attribute__((aligned(16))) float scn[kSceneLdsW];   // a scene engine's body table and obstacles
+    __shared__ __attribute__((aligned(16))) float scn[kSceneLdsW + kFieldHdrW];   // a scene engine's body table and obstacles, a field engine's field header
     const DevParams& p = pk;
     const int v = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int nthr = blockDim.x, nw = nthr >> 6;
@@ -184,6 +185,7 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     for (int i = tid; i < kVCW; i += nthr) ((int*)&vcv)[i] = ((const int*)(pp.vc + v))[i];
     if (pp.scene)
         for (int i = tid; i < kSceneLdsW; i += nthr) scn[i] = pp.scene[i < kSceneBodyW ? i : i + v * kSceneObsW];
+    if (pp.field && tid < kFieldHdrW) scn[kSceneLdsW + tid] = pp.field[tid];   // (a field engine has a scene)
     const VehicleConst& vc = vcv;
 
     // ---- double integrator (standard_normal_noise.py:41-48), k_rollout's NCH > 1 arithmetic
@@ -254,7 +256,8 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
         perr = fabsf(dx) + fabsf(dy) + fabsf(dz);
         if (pp.scene) {
             const float Td[12] = {1.0f, 0.0f, 0.0f, posf[0], 0.0f, 1.0f, 0.0f, posf[1], 0.0f, 0.0f, 1.0f, posf[2]};
-            obs_frame(Td, scn, scn + kSceneBodyW, 0, otau, oh, og);
+            if (pp.field) obs_frame_field(Td, scn, scn + kSceneBodyW, 0, otau, scn + kSceneLdsW, pp.field + kFieldHdrW, oh, og);
+            else obs_frame(Td, scn, scn + kSceneBodyW, 0, otau, oh, og);
         }
         if (val) {
 #pragma unroll
@@ -263,7 +266,8 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     } else {
         Mat34 T;
         plan_fk<MODEL, NA, F64>(T, posf, posd, vc, jnt, p, [&](int slot) {
-            if (pp.scene) obs_frame(T.m, scn, scn + kSceneBodyW, slot, otau, oh, og);
+            if (pp.field) obs_frame_field(T.m, scn, scn + kSceneBodyW, slot, otau, scn + kSceneLdsW, pp.field + kFieldHdrW, oh, og);
+            else if (pp.scene) obs_frame(T.m, scn, scn + kSceneBodyW, slot, otau, oh, og);
         });
         cost = pose_cost_row(T, tg, term ? p.w_tp : p.w_sp, term ? p.w_to : p.w_so);
         perr = fabsf(T.m[3] - tg[0]) + fabsf(T.m[7] - tg[1]) + fabsf(T.m[11] - tg[2]);

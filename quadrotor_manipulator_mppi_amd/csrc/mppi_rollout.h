@@ -27,6 +27,7 @@
 #include "mppi_stores.h"
 #include "mppi_integrator.h"
 #include "mppi_obstacles.h"
+#include "mppi_field.h"
 
 // The leading scalar arguments are preloaded into SGPRs at wave launch on gfx950
 // (-mllvm -amdgpu-kernarg-preload-count, build.py): the first group's Philox
@@ -76,8 +77,13 @@ constexpr int roll_occ() {
 // chain completes, the lane runs that frame's spheres against the obstacles at its own row time
 // (wave-uniform LDS reads), and the step's term joins the extra terms' segment sums.  The per-sample
 // clearance, a segment min, is staged and written through beside S (into the scene buffer).
+// FLD (k_rollout_df; mppi_create_scene_field): a scene (OBS) body with the engine's distance field
+// (mppi_field.h) as one more obstacle.  The field's header rides in LDS behind the staged scene; per body
+// sphere the lane samples the field at the centre it has just formed (four 8 B loads of x-pairs; the
+// lanes of a segment are consecutive t of one sample, so neighbouring centres share lines) and feeds
+// g = d(c) - r_b into the same hinge sum and min.  A field not set is a wave-uniform skip.
 template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG, bool B512, bool QUIET = false,
-          bool TRK = false, bool OBS = false>
+          bool TRK = false, bool OBS = false, bool FLD = false>
 __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint32_t seed_hi,
                                              const uint32_t step_arg, const uint32_t k_off,
                                              const int32_t noise_arg, const int32_t H_arg,
@@ -85,8 +91,10 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                                              const float* __restrict__ u_prev,
                                              const JointDev* __restrict__ jtab, const DevParams& pk,
                                              const float* __restrict__ ttab = nullptr,
-                                             float* __restrict__ scene = nullptr) {
+                                             float* __restrict__ scene = nullptr,
+                                             const float* __restrict__ field = nullptr) {
     static_assert(!B512 || ONEG, "the fixed-block body is a single-group one");
+    static_assert(!FLD || OBS, "the field body is a scene one");
     static_assert(!OBS || (TRK && !B512), "the scene body is a tracking one of every block size");
     static_assert(!TRK || (XC && !QUIET), "the tracking body is an extended one, and has no quiet form");
     static_assert(!QUIET || (!XC && NCH == 1), "the quiet body exists for the common one-chunk kernels");
@@ -107,7 +115,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     // phases); the joint table and (V > 1) the vehicle block go to LDS.
     __shared__ JointDev jnt[kMaxJ];
     __shared__ VehicleConst vcv;
-    __shared__ __attribute__((aligned(16))) float scn[OBS ? kSceneLdsW : 4];   // OBS: the body table, then the vehicle's obstacles
+    __shared__ __attribute__((aligned(16))) float scn[OBS ? kSceneLdsW + (FLD ? kFieldHdrW : 0) : 4];   // OBS: the body table, then the vehicle's obstacles (FLD: then the field's header)
     const DevParams& p = pk;
     const int v = blockIdx.y;
     // block size and groups per block as one preloaded argument (threads | iters << 16): blockDim
@@ -171,6 +179,8 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     };
     float scr = 0.0f;
     if constexpr (OBS) scr = (tid < kSceneLdsW) ? scene_word(tid) : 0.0f;
+    float fhr = 0.0f;   // FLD: the field header word this thread stages (the block's last wave: nthr >= 64 > kFieldHdrW)
+    if constexpr (FLD) fhr = (tid >= nthr - kFieldHdrW) ? field[tid - (nthr - kFieldHdrW)] : 0.0f;
     // touch every kernel-argument line the hot phases read (one s_load per 64 B): they
     // land in the scalar cache while the first group's Philox draw runs below
     // (an integer fold: uniform, so SALU -- a float sum took one VALU op per line)
@@ -288,6 +298,8 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         if (tid < kSceneLdsW) scn[tid] = scr;
         for (int i = tid + nthr; i < kSceneLdsW; i += nthr) scn[i] = scene_word(i);   // nthr < 224
     }
+    if constexpr (FLD)
+        if (tid >= nthr - kFieldHdrW) scn[kSceneLdsW + tid - (nthr - kFieldHdrW)] = fhr;
     STAMPW(8);
     if (!(MPPI_KO & 256)) lds_barrier();
     const VehicleConst& vc = vcv;
@@ -526,7 +538,8 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 x = dx * dx + dy * dy + dz * dz;
                 if constexpr (OBS) {   // no chain: the spheres ride on p(k,t) in world axes
                     const float Td[12] = {1.0f, 0.0f, 0.0f, posf[c][0], 0.0f, 1.0f, 0.0f, posf[c][1], 0.0f, 0.0f, 1.0f, posf[c][2]};
-                    obs_frame(Td, scn, scn + kSceneBodyW, 0, (float)(t + 1) * p.dt, ostep.sum, ostep.gmin);
+                    if constexpr (FLD) obs_frame_field(Td, scn, scn + kSceneBodyW, 0, (float)(t + 1) * p.dt, scn + kSceneLdsW, field + kFieldHdrW, ostep.sum, ostep.gmin);
+                    else obs_frame(Td, scn, scn + kSceneBodyW, 0, (float)(t + 1) * p.dt, ostep.sum, ostep.gmin);
                 }
                 if (stv) {
 #pragma unroll
@@ -549,7 +562,8 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 }
                 // OBS: the spheres of a frame slot as soon as T is that frame (slot 0: the folded base)
                 auto obs_at = [&](int slot) __attribute__((always_inline)) {
-                    if constexpr (OBS) obs_frame(T.m, scn, scn + kSceneBodyW, slot, (float)(t + 1) * p.dt, ostep.sum, ostep.gmin);
+                    if constexpr (FLD) obs_frame_field(T.m, scn, scn + kSceneBodyW, slot, (float)(t + 1) * p.dt, scn + kSceneLdsW, field + kFieldHdrW, ostep.sum, ostep.gmin);
+                    else if constexpr (OBS) obs_frame(T.m, scn, scn + kSceneBodyW, slot, (float)(t + 1) * p.dt, ostep.sum, ostep.gmin);
                 };
                 obs_at(0);
                 if (MPPI_KO & 4) {
@@ -994,4 +1008,20 @@ __global__ void __launch_bounds__(512, (roll_occ<NCH, F64, true, false>())) k_ro
                                                  const DevParams pk) {
     rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, true, false, false, false, true, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg,
                                                                                          H_arg, geo_arg, u_prev, jtab, pk, ttab, scene);
+}
+
+// The field rollout (rollout_body FLD): the scene kernel with the engine's distance field (mppi_field.h)
+// as one more obstacle, under a symbol of its own.  The field buffer is one more pointer argument after
+// the scene pointer and before the trailing DevParams.
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE>
+__global__ void __launch_bounds__(512, (roll_occ<NCH, F64, true, false>())) k_rollout_df(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                 const uint32_t step_arg, const uint32_t k_off,
+                                                 const int32_t noise_arg, const int32_t H_arg,
+                                                 const int32_t geo_arg,
+                                                 const float* __restrict__ u_prev,
+                                                 const JointDev* __restrict__ jtab,
+                                                 const float* __restrict__ ttab, float* __restrict__ scene,
+                                                 const float* __restrict__ field, const DevParams pk) {
+    rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, true, false, false, false, true, true, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg,
+                                                                                               H_arg, geo_arg, u_prev, jtab, pk, ttab, scene, field);
 }

@@ -18,6 +18,16 @@ extern "C" int mppi_launch_rollout_arm64_tt(const DevParams* p, const float* tta
         return launch_rollout_tt<MPPI_MODEL_ARM, 7, nch(), l(), true>(*p, ttab, threads, s);
     });
 }
+// the field kernels (k_rollout_df; mppi_create_scene_field), the H <= 32 one from its own unit.  Ahead of the
+// scene launcher on purpose: kernels are emitted in this order, and the scene kernels stay the unit's
+// last, as in the builds before the field (the code object's last kernel has no alignment fill behind it).
+extern "C" int mppi_launch_rollout_arm64_df(const DevParams* p, const float* ttab, float* scene, const float* field, int threads, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
+    if (p->nch == 1 && p->L == 32) return mppi_launch_rollout_arm64_h32_df(p, ttab, scene, field, threads, stream);
+    return pick_geom<false>(*p, [&](auto nch, auto l) {
+        return launch_rollout_df<MPPI_MODEL_ARM, 7, nch(), l(), true>(*p, ttab, scene, field, threads, s);
+    });
+}
 // the scene kernels (k_rollout_ob; mppi_create_scene), the H <= 32 one from its own unit
 extern "C" int mppi_launch_rollout_arm64_ob(const DevParams* p, const float* ttab, float* scene, int threads, void* stream) {
     const hipStream_t s = (hipStream_t)stream;

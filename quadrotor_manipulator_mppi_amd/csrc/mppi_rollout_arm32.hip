@@ -12,3 +12,7 @@ extern "C" int mppi_launch_rollout_arm32_tt(const DevParams* p, const float* tta
 extern "C" int mppi_launch_rollout_arm32_ob(const DevParams* p, const float* ttab, float* scene, int threads, void* stream) {
     return dispatch_geom_ob<MPPI_MODEL_ARM, 7, false>(*p, ttab, scene, threads, (hipStream_t)stream);
 }
+// the field kernels (k_rollout_df; mppi_create_scene_field)
+extern "C" int mppi_launch_rollout_arm32_df(const DevParams* p, const float* ttab, float* scene, const float* field, int threads, void* stream) {
+    return dispatch_geom_df<MPPI_MODEL_ARM, 7, false>(*p, ttab, scene, field, threads, (hipStream_t)stream);
+}

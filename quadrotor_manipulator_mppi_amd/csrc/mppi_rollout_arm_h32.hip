@@ -16,3 +16,7 @@ extern "C" int mppi_launch_rollout_arm64_h32_tt(const DevParams* p, const float*
 extern "C" int mppi_launch_rollout_arm64_h32_ob(const DevParams* p, const float* ttab, float* scene, int threads, void* stream) {
     return launch_rollout_ob<MPPI_MODEL_ARM, 7, 1, 32, true>(*p, ttab, scene, threads, (hipStream_t)stream);
 }
+// the field kernel of the same geometry (k_rollout_df; mppi_create_scene_field)
+extern "C" int mppi_launch_rollout_arm64_h32_df(const DevParams* p, const float* ttab, float* scene, const float* field, int threads, void* stream) {
+    return launch_rollout_df<MPPI_MODEL_ARM, 7, 1, 32, true>(*p, ttab, scene, field, threads, (hipStream_t)stream);
+}

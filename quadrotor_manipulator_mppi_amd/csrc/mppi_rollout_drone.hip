@@ -94,6 +94,27 @@ extern "C" int mppi_launch_rollout_scene(const DevParams* p, const float* ttab, 
     return -1;
 }
 
+// The field launch (an engine of mppi_create_scene_field): the same dispatch over the field kernels
+// (k_rollout_df), handed the target table, the scene buffer and the field buffer.  No quadrotor form.
+extern "C" int mppi_launch_rollout_field(const DevParams* p, const float* ttab, float* scene, const float* field, int threads, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    switch (p->model) {
+        case MPPI_MODEL_DRONE:
+            if (p->A == 3) return dispatch_geom_df<MPPI_MODEL_DRONE, 3, false>(*p, ttab, scene, field, threads, s);
+            break;
+        case MPPI_MODEL_ARM:
+            if (p->A == 7) return p->state_f64 ? mppi_launch_rollout_arm64_df(p, ttab, scene, field, threads, stream)
+                                               : mppi_launch_rollout_arm32_df(p, ttab, scene, field, threads, stream);
+            break;
+        case MPPI_MODEL_WHOLEBODY:
+            if (p->A == 10) return mppi_launch_rollout_wb_df(p, ttab, scene, field, threads, stream);
+            break;
+        default:
+            break;
+    }
+    return -1;
+}
+
 extern "C" int mppi_launch_philox(uint64_t seed, uint32_t step, int vehicle, int64_t k0, int K, int H, int A,
                                   float* z, uint32_t* raw, void* stream) {
     const int n = K * H;

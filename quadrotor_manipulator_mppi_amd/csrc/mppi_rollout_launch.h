@@ -150,3 +150,25 @@ template <int MODEL, int NA, bool F64>
 inline int dispatch_geom_ob(const DevParams& p, const float* ttab, float* scene, int threads, hipStream_t s) {
     return pick_geom(p, [&](auto nch, auto l) { return launch_rollout_ob<MODEL, NA, nch(), l(), F64>(p, ttab, scene, threads, s); });
 }
+
+// The field launch (an engine of mppi_create_scene_field: a scene buffer and a field buffer, mppi_field.h):
+// k_rollout_df on every step of a batch (no quiet form); LDS as the scene kernel's.
+template <int MODEL, int NA, int NCH, int LSEG, bool F64>
+inline int launch_rollout_df(const DevParams& p, const float* ttab, float* scene, const float* field, int threads, hipStream_t s) {
+    size_t lds;
+    int32_t geo;
+    if (!ttab || !scene || !field || threads < 64 || !rollout_block<NA, NCH, LSEG>(p, threads, p.iters, false, lds, geo)) return -1;
+    lds += (size_t)p.iters * cost_run_stride((threads / 64) * (64 / LSEG)) * sizeof(float);
+    return pick<true, false>(p.V == 1, [&](auto vone) {
+        const auto k = k_rollout_df<MODEL, NA, NCH, LSEG, F64, vone()>;
+        static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+        static_assert(arg_offset<11>(decltype(k)()) == kRollFieldOff, "the field pointer follows the scene pointer");
+        return go(k, dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
+                  p.noise_mode, p.H, geo, p.u_prev, p.joints, ttab, scene, field, p);
+    });
+}
+
+template <int MODEL, int NA, bool F64>
+inline int dispatch_geom_df(const DevParams& p, const float* ttab, float* scene, const float* field, int threads, hipStream_t s) {
+    return pick_geom(p, [&](auto nch, auto l) { return launch_rollout_df<MODEL, NA, nch(), l(), F64>(p, ttab, scene, field, threads, s); });
+}

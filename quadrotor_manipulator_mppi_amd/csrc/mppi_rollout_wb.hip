@@ -12,3 +12,7 @@ extern "C" int mppi_launch_rollout_wb_tt(const DevParams* p, const float* ttab, 
 extern "C" int mppi_launch_rollout_wb_ob(const DevParams* p, const float* ttab, float* scene, int threads, void* stream) {
     return dispatch_geom_ob<MPPI_MODEL_WHOLEBODY, 10, false>(*p, ttab, scene, threads, (hipStream_t)stream);
 }
+// the field kernels (k_rollout_df; mppi_create_scene_field)
+extern "C" int mppi_launch_rollout_wb_df(const DevParams* p, const float* ttab, float* scene, const float* field, int threads, void* stream) {
+    return dispatch_geom_df<MPPI_MODEL_WHOLEBODY, 10, false>(*p, ttab, scene, field, threads, (hipStream_t)stream);
+}

@@ -243,7 +243,9 @@ class ShardedEngine:
         device = engine_kw.pop("device", 0)
         # an engine.Scene: every rank's engine is an obstacle-avoiding one with the same body spheres
         scene = engine_kw.pop("scene", None)
-        make_engine = lambda c: Engine(c) if scene is None else Engine(c, scene=scene)  # noqa: E731
+        # an engine.DistanceField: every rank's engine holds the whole field
+        field = engine_kw.pop("field", None)
+        make_engine = lambda c: Engine(c) if scene is None and field is None else Engine(c, scene=scene, field=field)  # noqa: E731
         self.local = int(os.environ.get("LOCAL_RANK", device))
         self.local %= max(1, torch.cuda.device_count())   # more ranks than devices: wrap
         torch.cuda.set_device(self.local)
@@ -417,6 +419,14 @@ class ShardedEngine:
         """This rank's engine's obstacles (Engine.set_obstacles).  Every rank is given the same set,
         like the state."""
         self.engine.set_obstacles(centers, radii, velocities, vehicle)
+
+    def set_distance_field(self, d, origin=None):
+        """This rank's engine's distance field (Engine.set_distance_field).  Every rank holds the whole
+        field and is given the same one, like the state."""
+        self.engine.set_distance_field(d, origin)
+
+    def clear_distance_field(self):
+        self.engine.clear_distance_field()
 
     def get_clearances(self):
         """This rank's samples' clearances (Engine.get_clearances)."""

@@ -112,6 +112,65 @@ class Scene:
         return c
 
 
+class DistanceField:
+    """The voxel signed distance field of a field engine (``Engine(cfg, field=...)``,
+    mppi_create_scene_field): ``dims`` = (nx, ny, nz) nodes, ``voxel`` in metres, ``origin`` the world
+    position of node (0, 0, 0).  ``d`` (nz, ny, nx) float32, metres, negative inside -- None: the
+    engine starts with the field cleared.  Points outside the grid read the clamped position's
+    value, so pad the grid."""
+
+    def __init__(self, dims, voxel: float, origin=(0.0, 0.0, 0.0), d=None):
+        self.dims = tuple(int(n) for n in dims)
+        self.voxel = float(voxel)
+        self.origin = tuple(float(x) for x in origin)
+        if len(self.dims) != 3 or len(self.origin) != 3:
+            raise ValueError("dims and origin have three entries (x, y, z)")
+        self.d = None if d is None else self.check(d)
+
+    @property
+    def shape(self):
+        return self.dims[::-1]   # (nz, ny, nx)
+
+    def check(self, d) -> np.ndarray:
+        d = np.ascontiguousarray(d, np.float32)
+        if d.shape != self.shape:
+            raise ValueError(f"field data {d.shape}, expected (nz, ny, nx) = {self.shape}")
+        return d
+
+    def nodes(self):
+        """The nodes' world coordinates X, Y, Z, each (nz, ny, nx), float64."""
+        ax = [self.origin[a] + self.voxel * np.arange(self.dims[a], dtype=np.float64) for a in range(3)]
+        Z, Y, X = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+        return X, Y, Z
+
+    def to_c(self) -> capi.FieldDesc:
+        c = capi.FieldDesc()
+        c.dims[:] = self.dims
+        c.voxel = self.voxel
+        c.origin[:] = self.origin
+        return c
+
+    @staticmethod
+    def from_function(fn, dims, voxel, origin=(0.0, 0.0, 0.0)) -> "DistanceField":
+        """``fn(X, Y, Z) -> d``, vectorised over the nodes' world coordinates."""
+        f = DistanceField(dims, voxel, origin)
+        f.d = f.check(np.asarray(fn(*f.nodes()), np.float64))
+        return f
+
+    @staticmethod
+    def from_boxes(boxes, dims, voxel, origin=(0.0, 0.0, 0.0)) -> "DistanceField":
+        """The exact SDF of a union of axis-aligned boxes ``(lo3, hi3)``: the min over the boxes."""
+        def sdf(X, Y, Z):
+            P = np.stack([X, Y, Z], -1)
+            out = np.full(X.shape, np.inf)
+            for lo, hi in boxes:
+                lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+                q = np.abs(P - 0.5 * (lo + hi)) - 0.5 * (hi - lo)
+                out = np.minimum(out, np.linalg.norm(np.maximum(q, 0.0), axis=-1) + np.minimum(q.max(-1), 0.0))
+            return out
+        return DistanceField.from_function(sdf, dims, voxel, origin)
+
+
 def fill_joints(cfg: capi.Config, chain: Sequence[Dict]) -> None:
     if len(chain) > capi.MAX_JOINTS:
         raise ValueError(f"chain has {len(chain)} joints (max {capi.MAX_JOINTS})")
@@ -227,14 +286,24 @@ def cost_term_bits(terms) -> int:
 class Engine:
     """One MPPI engine on one GPU (V vehicles x K samples x H steps)."""
 
-    def __init__(self, cfg: Optional[capi.Config] = None, scene: Optional[Scene] = None, **kw):
+    def __init__(self, cfg: Optional[capi.Config] = None, scene: Optional[Scene] = None,
+                 field: Optional[DistanceField] = None, **kw):
         """``scene``: a ``Scene`` makes this an obstacle-avoiding engine (``set_obstacles``,
-        ``get_clearances``, ``Plan.clearance``); None: the engine as before."""
+        ``get_clearances``, ``Plan.clearance``); None: the engine as before.  ``field``: a
+        ``DistanceField`` adds a voxel distance field as one more obstacle (``set_distance_field``,
+        ``clear_distance_field``); without ``scene`` it uses ``Scene.default(cfg)``."""
         self._L = capi.lib()
         self.cfg = cfg if cfg is not None else make_config(**kw)
+        if field is not None and scene is None:
+            scene = Scene.default(self.cfg)
         self.scene = scene
+        self.field = field
         h = C.c_void_p()
-        if scene is None:
+        if field is not None:
+            sc, fd = scene.to_c(), field.to_c()
+            capi.check(self._L.mppi_create_scene_field(C.byref(self.cfg), C.byref(sc), C.byref(fd), C.byref(h)),
+                       "mppi_create_scene_field")
+        elif scene is None:
             capi.check(self._L.mppi_create(C.byref(self.cfg), C.byref(h)), "mppi_create")
         else:
             sc = scene.to_c()
@@ -257,6 +326,8 @@ class Engine:
         self._p_state = capi.dptr(self._state_buf)
         self._state_flat = self._state_buf.reshape(-1)   # a view: the per-call fast path below
         self._p_tpos, self._p_tquat = capi.fptr(self._tgt_pos), capi.fptr(self._tgt_quat)
+        if field is not None and field.d is not None:
+            self.set_distance_field(field.d)
 
     # ------------------------------------------------------------------ admin
     def close(self):
@@ -494,6 +565,21 @@ class Engine:
         w = None if velocities is None else np.ascontiguousarray(velocities, np.float32).reshape(n, 3)
         capi.check(self._L.mppi_set_obstacles(self._h, vehicle, n, capi.fptr(c), capi.fptr(r), capi.fptr(w)),
                    "set_obstacles")
+
+    def set_distance_field(self, d, origin=None):
+        """Replaces a field engine's distance field: ``d`` (nz, ny, nx) metres, negative inside;
+        ``origin`` (3,) moves node (0, 0, 0) (None: where it is).  Takes effect on the next step."""
+        if self.field is None:
+            raise RuntimeError("engine created without a field (Engine(cfg, field=DistanceField(...)))")
+        d = self.field.check(d)
+        o = None if origin is None else np.ascontiguousarray(origin, np.float32).reshape(3)
+        capi.check(self._L.mppi_set_distance_field(self._h, capi.fptr(o), capi.fptr(d)), "set_distance_field")
+
+    def clear_distance_field(self):
+        """The field contributes nothing until the next ``set_distance_field``."""
+        if self.field is None:
+            raise RuntimeError("engine created without a field (Engine(cfg, field=DistanceField(...)))")
+        capi.check(self._L.mppi_set_distance_field(self._h, None, None), "clear_distance_field")
 
     def get_clearances(self) -> np.ndarray:
         """(V, K): every sample's min clearance to the obstacles over the horizon and the body

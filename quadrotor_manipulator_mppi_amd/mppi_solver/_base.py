@@ -113,7 +113,7 @@ class SolverBase:
         """The engine made for ``key``: the one at hand, or a new one that takes over the warm
         start (and the prewarm window, mppi_set_prewarm: for a loop ticking with idle gaps)."""
         e = self._engine
-        full_key = (key, self._scene)   # (the scene is fixed per engine: a new one, a new engine)
+        full_key = (key, self._scene, self._field)   # (the scene and the field's grid are fixed per engine)
         if e is not None and full_key == self._engine_key:
             return e
         u = self._u_prev_host if e is None else e.get_u_prev()[0]
@@ -121,7 +121,7 @@ class SolverBase:
             e.close()
         cfg = self._config(key)
         scene = Scene.default(cfg) if self._scene is True else self._scene
-        e = self._engine = Engine(cfg) if scene is None else Engine(cfg, scene=scene)
+        e = self._engine = Engine(cfg) if scene is None and self._field is None else Engine(cfg, scene=scene, field=self._field)
         self._engine_key = full_key
         e.set_u_prev(u)
         if self._prewarm_us:
@@ -217,7 +217,43 @@ class SolverBase:
             raise RuntimeError("clear_obstacles needs scene=... at construction")
         self._obstacles = None
 
+    # ``field=`` (a constructor keyword of the arm and drone classes): an ``engine.DistanceField`` makes
+    # the engine a field engine (with ``scene``, or the placeholder spheres); its data, when it has some,
+    # is the field until set_distance_field / clear_distance_field.
+    _field = None
+    _field_data = None     # (d, origin or None) of set_distance_field; None: cleared
+    _field_sent = None     # (engine, data) last written (_sync_field)
+
+    def set_distance_field(self, d, origin=None) -> None:
+        """The distance field (``Engine.set_distance_field``): (nz, ny, nx) metres, negative inside;
+        ``origin`` moves node (0, 0, 0).  Used from the next control call on."""
+        if self._field is None:
+            raise RuntimeError("set_distance_field needs field=... at construction")
+        o = None if origin is None else np.ascontiguousarray(origin, np.float32).reshape(3).copy()
+        self._field_data = (self._field.check(d).copy(), o)
+
+    def clear_distance_field(self) -> None:
+        if self._field is None:
+            raise RuntimeError("clear_distance_field needs field=... at construction")
+        self._field_data = None
+
+    def _init_field(self, field) -> None:
+        self._field = field
+        self._field_data = None if field is None or field.d is None else (field.d, None)
+
+    def _sync_field(self, eng: Engine) -> None:
+        if self._field is None:
+            return
+        data, sent = self._field_data, self._field_sent
+        if sent is None or sent[0] is not eng or sent[1] is not data:
+            if data is None:
+                eng.clear_distance_field()
+            else:
+                eng.set_distance_field(*data)
+            self._field_sent = (eng, data)
+
     def _sync_obstacles(self, eng: Engine) -> None:
+        self._sync_field(eng)
         if self._scene is None:
             return
         obs, sent = self._obstacles, self._obs_sent
@@ -262,10 +298,11 @@ class VehicleSolver(SolverBase):
     _horizon_attr = "n_timestep"
 
     def __init__(self, width: int, sigma: torch.Tensor, n_samples: int, n_timestep: int, *base_args,
-                 track_target: bool = False, scene=None):
+                 track_target: bool = False, scene=None, field=None):
         super().__init__(sigma.shape[0], n_timestep, *base_args)
         self._track_target = bool(track_target)
         self._scene = scene
+        self._init_field(field)
         self.n_samples = n_samples
         self.n_timestep = n_timestep
         self.x_prev = torch.zeros(width)
