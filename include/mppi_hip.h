@@ -531,6 +531,36 @@ mppi_status mppi_create_scene_field(const mppi_config* cfg, const mppi_scene* sc
  * the engine's stream, ordered before the next step on either dispatch path; no allocation. */
 mppi_status mppi_set_distance_field(mppi_engine* e, const float* origin3, const float* d_zyx);
 
+/* Occupancy grids: the field built on the device from the map a node actually holds (octomap, a
+ * depth-camera voxel map, a local window).  A grid of nodes, each occupied or free, becomes a signed
+ * field as follows.  D2_occ(n) is the smallest squared index distance from node n to an occupied node,
+ * D2_free(n) the same to a free node: integers, at most 3 * 511^2.  Outside the grid is unknown and
+ * supplies no seeds of either kind.  Nodes are the centres of cubes of side voxel:
+ *   free node      d = +voxel (sqrt(D2_occ)  - 0.5)
+ *   occupied node  d = -voxel (sqrt(D2_free) - 0.5)
+ * so the zero of the trilinear interpolation falls on the face between an occupied node and its free
+ * neighbour.  d is then clamped to [-cap, +cap]: cap = max_dist when max_dist > 0, else
+ * voxel (nx + ny + nz), more than any in-grid distance.  A grid with no occupied node reads +cap
+ * everywhere, one with no free node -cap.  Arithmetic: t = sqrtf((float)D2); d = voxel * (t - 0.5f), then
+ * the clamp, all in fp32 with a correctly rounded square root -- the host and the device compute it with
+ * the same inline, every operation is exactly rounded, and the two agree bit for bit.
+ *
+ * mppi_set_occupancy replaces the field by the one of occ_zyx (nz,ny,nx) uint8, C order, nonzero =
+ * occupied; origin3 NULL keeps the current origin.  MPPI_ERR_STATE on an engine not created by
+ * mppi_create_scene_field; MPPI_ERR_INVALID_ARG for a NULL occ_zyx, a non-finite origin, a max_dist that
+ * is NaN or +inf.  The bytes are copied into the engine's staging memory (the caller's array is free on
+ * return; one byte per node crosses the bus) and an exact separable distance transform in int32
+ * squared distances (k_edt_x, k_edt_axis for y and z, k_edt_finish) runs on the engine's stream,
+ * ordered before the next step on either dispatch path.  Its device scratch (9 bytes per node) is
+ * allocated at the first call and never grows.  mppi_set_distance_field, with data or NULL, keeps
+ * working on the same engine in any order. */
+mppi_status mppi_set_occupancy(mppi_engine* e, const float* origin3, const uint8_t* occ_zyx, float max_dist);
+/* The field as it stands on the device (synchronous): is_set (0: cleared), its origin, d_zyx (nz,ny,nx)
+ * = the first word of every x-pair.  Any pointer may be NULL.  After mppi_set_distance_field(d) it
+ * returns d bit for bit; after mppi_set_occupancy what the controller sees.  MPPI_ERR_STATE on an
+ * engine not created by mppi_create_scene_field. */
+mppi_status mppi_get_distance_field(mppi_engine* e, int32_t* is_set, float* origin3, float* d_zyx);
+
 #define MPPI_MAX_ELITES 64
 /* The n lowest-cost samples of the last rollout of every vehicle, best first (synchronous).
  *   idx  (V,n) int32   sample index within this engine's K (a shard: local; global = shard_rank*K + idx)
@@ -591,6 +621,12 @@ int32_t mppi_savgol_coefficients(int32_t window, int32_t order, float* c); /* sv
 /* Host FK of one joint vector (check_reach, urdf_fk.py:60-75); base as xyzquat. */
 mppi_status mppi_host_fk(const mppi_joint* joints, int32_t n_joints, const double* q, const double* xyzquat,
                          int32_t f64, float* T16);
+
+/* mppi_set_occupancy's field on the host, by the same definition and the same inline for the value:
+ * desc as mppi_create_scene_field validates it, occ_zyx and d_zyx (nz,ny,nx).  Separable, at worst
+ * O(n) per line per output node.  MPPI_ERR_INVALID_ARG for a NULL pointer, a descriptor
+ * mppi_create_scene_field refuses, a max_dist that is NaN or +inf. */
+mppi_status mppi_occupancy_field(const mppi_field_desc* desc, const uint8_t* occ_zyx, float max_dist, float* d_zyx);
 
 /* Device RNG check: standard normals z (K,H,A) and the raw Philox words (K,H,W),
  * W = mppi_philox_words(A), exactly as the rollout kernel draws them for (seed, step,

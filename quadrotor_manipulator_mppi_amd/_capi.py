@@ -156,6 +156,9 @@ PROTOTYPES = {
     "mppi_get_plan_clearance": (_ST, [_P, _F]),
     "mppi_create_scene_field": (_ST, [_CFG, C.POINTER(Scene), C.POINTER(FieldDesc), C.POINTER(_P)]),
     "mppi_set_distance_field": (_ST, [_P, _F, _F]),
+    "mppi_set_occupancy": (_ST, [_P, _F, C.POINTER(C.c_uint8), C.c_float]),
+    "mppi_get_distance_field": (_ST, [_P, _I32, _F, _F]),
+    "mppi_occupancy_field": (_ST, [C.POINTER(FieldDesc), C.POINTER(C.c_uint8), C.c_float, _F]),
     "mppi_enable_timing": (_ST, [_P, C.c_int32]),
     "mppi_get_timing": (_ST, [_P, _D, _D, _I64, _I64]),
     "mppi_kernel_timing": (_ST, [_P, C.c_int32, _D, _D]),
@@ -190,6 +193,8 @@ DEBUG_PROTOTYPES = {
     "mppi_debug_field_step_launches": (C.c_int32, [_CFG, C.POINTER(Scene), C.POINTER(FieldDesc), _I32, C.c_char_p,
                                                    C.c_int32, C.POINTER(C.c_uint64)]),
     "mppi_debug_field_rollout_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_char_p, C.c_int32]),
+    "mppi_debug_edt_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_int32]),
+    "mppi_debug_field_words": (C.c_int32, [_P, _F]),
 }
 
 _lib = None

@@ -159,6 +159,45 @@ int32_t mppi_debug_elite_kernel(const int32_t* g, char* sym, int32_t len) {
     return MPPI_OK;
 }
 
+// Likewise the occupancy transform's launches (mppi_edt.hip; mppi_set_occupancy) -- g = {nx, ny, nz}:
+// "<symbol> grid <x>x<y> block <threads> lds <bytes>" per launch, joined by "; ": the x pass, the y pass,
+// the z pass, the finish.  tests/test_capi_occupancy_cpu.py.
+int32_t mppi_debug_edt_kernels(const int32_t* g, char* sym, int32_t len) {
+    if (!g || !sym || len <= 0) return MPPI_ERR_INVALID_ARG;
+    static uint8_t nowhere8 = 0;   // the launches are described, not run: any non-null pointers
+    static int32_t nowhere32 = 0;
+    static float nowheref = 0.0f;
+    EdtParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.occ = &nowhere8; p.g_occ = p.g_free = &nowhere32; p.cells = &nowheref;
+    p.nx = g[0]; p.ny = g[1]; p.nz = g[2];
+    p.voxel = 1.0f; p.cap = 1.0f; p.window = 2;
+    std::string all;
+    for (int stage = 0; stage < 4; ++stage) {
+        LaunchDesc d{};
+        int rc;
+        {   const mppi_aql::Capture c(&d);
+            rc = mppi_launch_edt_stage(&p, stage, nullptr); }
+        if (rc != 0) return MPPI_ERR_INVALID_ARG;
+        char one[256];
+        snprintf(one, sizeof(one), "%s%s grid %ux%u block %u lds %u", all.empty() ? "" : "; ", d.symbol, d.grid[0], d.grid[1],
+                 d.block[0], d.lds);
+        all += one;
+    }
+    if ((int)all.size() >= len) return MPPI_ERR_INVALID_ARG;
+    snprintf(sym, (size_t)len, "%s", all.c_str());
+    return MPPI_OK;
+}
+
+// Diagnostic (GPU): a field engine's whole field buffer as it stands on the device -- field_words(nvox)
+// words, the header and both words of every x-pair (mppi_get_distance_field hands out the first of each).
+// tests/test_gpu_occupancy.py.
+int32_t mppi_debug_field_words(mppi_engine* e, float* words) {
+    if (!e || !words || !e->d_field) return MPPI_ERR_INVALID_ARG;
+    if (use_device(e)) return MPPI_ERR_HIP;
+    return download(e, words, e->d_field, sizeof(float) * (size_t)field_words(field_voxels(e->field)));
+}
+
 // The host twin of the elites' order: the n first sample indices of S (K) under mppi_elites.h's key,
 // the one the kernels select and sort by.  tests/test_capi_elites_cpu.py.
 int32_t mppi_debug_elite_order(const float* S, int32_t K, int32_t n, int32_t* idx) {

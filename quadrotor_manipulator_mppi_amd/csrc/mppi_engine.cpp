@@ -482,7 +482,7 @@ void mppi_destroy(mppi_engine* e) {
     void* dev[] = {e->d_xregion, e->d_xpeers, e->d_sigma, e->d_joints, e->d_vc, e->d_u_prev, e->d_noise_in, e->d_traj, e->d_noise_out,
                    e->d_S, e->d_hdr, e->d_rdata, e->d_out, e->d_wraw, e->d_wsmooth, e->d_w,
                    e->d_sinv, e->d_gamma, e->d_jtraj, e->d_ttab, e->d_scene, e->d_field, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec,
-                   e->d_plan_vc, e->d_plan, e->d_elite_cand, e->d_elites};
+                   e->d_plan_vc, e->d_plan, e->d_elite_cand, e->d_elites, e->d_edt};
     for (void* p : dev) if (p) (void)hipFree(p);
     if (e->h_out) (void)hipHostFree(e->h_out);
     if (e->h_vc) (void)hipHostFree(e->h_vc);
@@ -735,6 +735,68 @@ mppi_status mppi_set_distance_field(mppi_engine* e, const float* origin3, const 
     HIP_TRY(hipMemcpyAsync(e->d_field, e->h_field, sizeof(float) * words, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipEventRecord(e->ev_field, e->stream));
     e->field_pending = true;
+    return MPPI_OK;
+}
+
+// The field from an occupancy grid: the bytes go into the pinned staging copy behind the header (it holds
+// 8 bytes per node, the occupancy needs one) and from there to the transform's scratch; the four launches
+// of mppi_edt.hip write the cells, and the header's small copy -- set flag on -- is queued behind them.
+// Ordered before the next step as an uploaded field is: the event guards the staging copy, and native
+// dispatch drains the stream before its first packet.
+mppi_status mppi_set_occupancy(mppi_engine* e, const float* origin3, const uint8_t* occ_zyx, float max_dist) {
+    if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
+    if (!e->d_field) return fail(MPPI_ERR_STATE, "engine created without a field (mppi_create_scene_field)");
+    mppi_status st = occupancy_validate(origin3, occ_zyx, max_dist);
+    if (st != MPPI_OK) return st;
+    if (use_device(e)) return MPPI_ERR_HIP;
+    const int64_t nvox = field_voxels(e->field);
+    if (!e->d_edt) HIP_TRY(hipMalloc(&e->d_edt, edt_scratch_bytes(nvox)));
+    if (e->field_pending) {   // the previous copy out of the staging buffer must be done
+        HIP_TRY(hipEventSynchronize(e->ev_field));
+        e->field_pending = false;
+    }
+    if (origin3) std::memcpy(e->field.origin, origin3, sizeof(e->field.origin));
+    field_header(e->field, e->field.origin, true, e->h_field);
+    std::memcpy(e->h_field + kFieldHdrW, occ_zyx, (size_t)nvox);
+    EdtParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.g_occ = (int32_t*)e->d_edt;
+    p.g_free = p.g_occ + nvox;
+    uint8_t* const d_occ = (uint8_t*)(p.g_free + nvox);
+    p.occ = d_occ;
+    p.cells = e->d_field + kFieldHdrW;
+    p.nx = e->field.dims[0]; p.ny = e->field.dims[1]; p.nz = e->field.dims[2];
+    p.voxel = e->field.voxel;
+    p.cap = edt_cap(e->field.dims, e->field.voxel, max_dist);
+    p.window = edt_window(p.voxel, p.cap);
+    HIP_TRY(hipMemcpyAsync(d_occ, e->h_field + kFieldHdrW, (size_t)nvox, hipMemcpyHostToDevice, e->stream));
+    const int rc = mppi_launch_edt(&p, e->stream);
+    if (rc != 0) return fail(MPPI_ERR_HIP, "occupancy transform launch failed (%d: %s)", rc,
+                             rc > 0 ? hipGetErrorString((hipError_t)rc) : "no kernel for these dims");
+    HIP_TRY(hipMemcpyAsync(e->d_field, e->h_field, sizeof(float) * kFieldHdrW, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipEventRecord(e->ev_field, e->stream));
+    e->field_pending = true;
+    return MPPI_OK;
+}
+
+// The field as it stands on the device: the whole buffer into the pinned staging copy (once no upload
+// reads it any more), one synchronise, and the first word of every x-pair handed out.
+mppi_status mppi_get_distance_field(mppi_engine* e, int32_t* is_set, float* origin3, float* d_zyx) {
+    if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
+    if (!e->d_field) return fail(MPPI_ERR_STATE, "engine created without a field (mppi_create_scene_field)");
+    if (use_device(e)) return MPPI_ERR_HIP;
+    if (e->field_pending) {
+        HIP_TRY(hipEventSynchronize(e->ev_field));
+        e->field_pending = false;
+    }
+    const int64_t nvox = field_voxels(e->field);
+    const size_t words = d_zyx ? (size_t)field_words(nvox) : (size_t)kFieldHdrW;
+    HIP_TRY(hipMemcpyAsync(e->h_field, e->d_field, sizeof(float) * words, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (is_set) std::memcpy(is_set, e->h_field + 7, sizeof(*is_set));
+    if (origin3) std::memcpy(origin3, e->h_field, 3 * sizeof(float));
+    const float* const cells = e->h_field + kFieldHdrW;
+    for (int64_t i = 0; d_zyx && i < nvox; ++i) d_zyx[i] = cells[2 * i];
     return MPPI_OK;
 }
 

@@ -135,6 +135,9 @@ struct mppi_engine : mppi_host::EngineLayout {
     float* h_field = nullptr;
     hipEvent_t ev_field = nullptr;
     bool field_pending = false;
+    // mppi_set_occupancy's device scratch (allocated at its first call, for the field's dims: the two
+    // int32 grids of the transform, then the occupancy bytes; mppi_edt.h edt_scratch_bytes)
+    void* d_edt = nullptr;
     float* d_exchange = nullptr;
     // mppi_get_plan's buffers (allocated at its first call): the host's vehicle constants; the
     // planes (V,C,H), cost_t (V,H), pos_err (V,H) and S (V) in one block, and its pinned host copy

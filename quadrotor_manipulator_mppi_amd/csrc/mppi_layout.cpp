@@ -357,6 +357,65 @@ void field_pack(const mppi_field_desc& f, const float* d_zyx, float* cells) {
     }
 }
 
+// ------------------------------------------------------------------ occupancy grids
+mppi_status occupancy_validate(const float* origin3, const uint8_t* occ_zyx, float max_dist) {
+    if (!occ_zyx) return fail(MPPI_ERR_INVALID_ARG, "occupancy: null grid");
+    for (int d = 0; origin3 && d < 3; ++d)
+        if (!std::isfinite(origin3[d])) return fail(MPPI_ERR_INVALID_ARG, "occupancy: non-finite origin");
+    if (std::isnan(max_dist) || (std::isinf(max_dist) && max_dist > 0.0f))
+        return fail(MPPI_ERR_INVALID_ARG, "occupancy: max_dist %g (a finite cap, or <= 0 for none)", max_dist);
+    return MPPI_OK;
+}
+
+// out[i] = min_j (in[j] + (i - j)^2) over one line of n nodes `stride` apart, for both grids at once: j
+// walks outward from i and stops where (i - j)^2 reaches both running minima, as k_edt_axis does.
+static void occupancy_line(int32_t* a, int32_t* b, int n, int64_t stride, int32_t* la, int32_t* lb) {
+    for (int i = 0; i < n; ++i) { la[i] = a[i * stride]; lb[i] = b[i * stride]; }
+    for (int i = 0; i < n; ++i) {
+        int32_t ma = la[i], mb = lb[i];
+        for (int d = 1; d < n; ++d) {
+            const int32_t dd = d * d;
+            if (dd >= ma && dd >= mb) break;
+            if (i - d >= 0) { ma = std::min(ma, la[i - d] + dd); mb = std::min(mb, lb[i - d] + dd); }
+            if (i + d < n) { ma = std::min(ma, la[i + d] + dd); mb = std::min(mb, lb[i + d] + dd); }
+        }
+        a[i * stride] = ma;
+        b[i * stride] = mb;
+    }
+}
+
+void occupancy_field(const mppi_field_desc& f, const uint8_t* occ, float max_dist, float* d_zyx) {
+    const int nx = f.dims[0], ny = f.dims[1], nz = f.dims[2];
+    const int64_t sy = nx, sz = (int64_t)nx * ny, nvox = field_voxels(f);
+    const float cap = edt_cap(f.dims, f.voxel, max_dist);
+    std::vector<int32_t> ga((size_t)nvox), gb((size_t)nvox), la(kEdtMaxLine), lb(kEdtMaxLine);
+    // x: the distance to the nearest seed of each set on either side, one sweep each way
+    for (int64_t r = 0; r < (int64_t)ny * nz; ++r) {
+        const uint8_t* o = occ + r * nx;
+        int32_t* a = ga.data() + r * nx;
+        int32_t* b = gb.data() + r * nx;
+        int lo = -1, lf = -1;
+        for (int x = 0; x < nx; ++x) {
+            if (o[x]) lo = x; else lf = x;
+            a[x] = lo < 0 ? kEdtInf : (x - lo) * (x - lo);
+            b[x] = lf < 0 ? kEdtInf : (x - lf) * (x - lf);
+        }
+        lo = lf = -1;
+        for (int x = nx - 1; x >= 0; --x) {
+            if (o[x]) lo = x; else lf = x;
+            if (lo >= 0) a[x] = std::min(a[x], (lo - x) * (lo - x));
+            if (lf >= 0) b[x] = std::min(b[x], (lf - x) * (lf - x));
+        }
+    }
+    for (int z = 0; z < nz; ++z)
+        for (int x = 0; x < nx; ++x)
+            occupancy_line(ga.data() + z * sz + x, gb.data() + z * sz + x, ny, sy, la.data(), lb.data());
+    for (int y = 0; y < ny; ++y)
+        for (int x = 0; x < nx; ++x)
+            occupancy_line(ga.data() + y * sy + x, gb.data() + y * sy + x, nz, sz, la.data(), lb.data());
+    for (int64_t e = 0; e < nvox; ++e) d_zyx[e] = edt_value(ga[(size_t)e], gb[(size_t)e], f.voxel, cap);
+}
+
 void set_generic(EngineLayout& l, int generic) {
     l.generic = generic;
     l.fp.kern = (generic & 1) ? kFinKernGeneric : 0;
@@ -382,6 +441,17 @@ extern "C" void mppi_scene_default(mppi_scene* s, const mppi_config* cfg) {
     if (cfg->model != MPPI_MODEL_DRONE)
         for (int j = 0; j < cfg->n_joints && j < MPPI_MAX_JOINTS; ++j)
             if (cfg->joints[j].type != MPPI_JOINT_FIXED) add(j, 0.05f);
+}
+
+// The occupancy grid's distance field on the host (include/mppi_hip.h): mppi_set_occupancy's definition
+// without a device.
+extern "C" mppi_status mppi_occupancy_field(const mppi_field_desc* desc, const uint8_t* occ_zyx, float max_dist, float* d_zyx) {
+    mppi_status st = field_validate(desc);
+    if (st != MPPI_OK) return st;
+    if ((st = occupancy_validate(nullptr, occ_zyx, max_dist)) != MPPI_OK) return st;
+    if (!d_zyx) return fail(MPPI_ERR_INVALID_ARG, "mppi_occupancy_field: null output");
+    occupancy_field(*desc, occ_zyx, max_dist, d_zyx);
+    return MPPI_OK;
 }
 
 // Diagnostic (no GPU): validate, scene_validate and the body table of a configuration and a scene.

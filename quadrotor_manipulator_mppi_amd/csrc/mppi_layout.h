@@ -8,6 +8,7 @@
 #include "mppi_dev.h"
 #include "mppi_obstacles.h"
 #include "mppi_field.h"
+#include "mppi_edt.h"
 
 // mppi_engine::generic with every part switched back (MPPI_GENERIC_KERNELS=1)
 constexpr int kGenericAll = 15;
@@ -90,6 +91,13 @@ mppi_status field_engine_validate(const mppi_config& c, const mppi_scene* scene,
 mppi_status field_data_validate(const mppi_field_desc& f, const float* origin3, const float* d_zyx);
 void field_header(const mppi_field_desc& f, const float* origin3, bool set, float* hdr);
 void field_pack(const mppi_field_desc& f, const float* d_zyx, float* cells);
+// ------------------------------------------------- occupancy grids (mppi_layout.cpp; mppi_edt.h)
+// occupancy_validate: the errors of mppi_set_occupancy's arguments (origin3 may be null).
+// occupancy_field: the host twin of the device transform (mppi_edt.hip) -- the same definition and the
+// same inline for the value (mppi_edt.h edt_value), separable, in int32 squared distances: occ (nz, ny, nx)
+// into d (nz, ny, nx) for a descriptor that passed field_validate.
+mppi_status occupancy_validate(const float* origin3, const uint8_t* occ_zyx, float max_dist);
+void occupancy_field(const mppi_field_desc& f, const uint8_t* occ_zyx, float max_dist, float* d_zyx);
 // the MPPI_GENERIC_KERNELS bits (EngineLayout::generic) and what they set in dp and fp
 void set_generic(EngineLayout& l, int generic);
 

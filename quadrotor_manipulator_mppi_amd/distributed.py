@@ -428,6 +428,15 @@ class ShardedEngine:
     def clear_distance_field(self):
         self.engine.clear_distance_field()
 
+    def set_occupancy(self, occ, origin=None, max_dist=None):
+        """This rank's engine's field from an occupancy grid (Engine.set_occupancy).  Every rank is given
+        the same map, as for set_distance_field."""
+        self.engine.set_occupancy(occ, origin, max_dist)
+
+    def get_distance_field(self):
+        """This rank's engine's field (Engine.get_distance_field): the same on every rank."""
+        return self.engine.get_distance_field()
+
     def get_clearances(self):
         """This rank's samples' clearances (Engine.get_clearances)."""
         return self.engine.get_clearances()

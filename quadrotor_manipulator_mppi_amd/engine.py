@@ -170,6 +170,29 @@ class DistanceField:
             return out
         return DistanceField.from_function(sdf, dims, voxel, origin)
 
+    def check_occupancy(self, occ) -> np.ndarray:
+        """An occupancy grid of this field's shape as the uint8 bytes the library takes (nonzero = occupied)."""
+        occ = np.asarray(occ)
+        if occ.dtype != np.bool_ and occ.dtype != np.uint8:
+            raise TypeError(f"occupancy of dtype {occ.dtype}: bool or uint8")
+        if occ.shape != self.shape:
+            raise ValueError(f"occupancy {occ.shape}, expected (nz, ny, nx) = {self.shape}")
+        return np.ascontiguousarray(occ).view(np.uint8)
+
+    @staticmethod
+    def from_occupancy(occ, dims, voxel, origin=(0.0, 0.0, 0.0), max_dist=None) -> "DistanceField":
+        """The field of an occupancy grid (nz, ny, nx), bool or uint8, by the host helper
+        (mppi_occupancy_field): what ``Engine.set_occupancy`` builds on the device, bit for bit, without one."""
+        f = DistanceField(dims, voxel, origin)
+        occ = f.check_occupancy(occ)
+        d = np.empty(f.shape, np.float32)
+        desc = f.to_c()
+        capi.check(capi.lib().mppi_occupancy_field(C.byref(desc), occ.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   0.0 if max_dist is None else float(max_dist), capi.fptr(d)),
+                   "mppi_occupancy_field")
+        f.d = d
+        return f
+
 
 def fill_joints(cfg: capi.Config, chain: Sequence[Dict]) -> None:
     if len(chain) > capi.MAX_JOINTS:
@@ -580,6 +603,31 @@ class Engine:
         if self.field is None:
             raise RuntimeError("engine created without a field (Engine(cfg, field=DistanceField(...)))")
         capi.check(self._L.mppi_set_distance_field(self._h, None, None), "clear_distance_field")
+
+    def set_occupancy(self, occ, origin=None, max_dist=None):
+        """Replaces a field engine's distance field by the one of an occupancy grid: ``occ`` (nz, ny, nx)
+        bool or uint8, nonzero = occupied; the transform runs on the device (mppi_set_occupancy), so only
+        the bytes cross the bus.  ``max_dist`` (m) caps |d| (None: no cap); ``origin`` as in
+        ``set_distance_field``.  Takes effect on the next step."""
+        if self.field is None:
+            raise RuntimeError("engine created without a field (Engine(cfg, field=DistanceField(...)))")
+        occ = self.field.check_occupancy(occ)
+        o = None if origin is None else np.ascontiguousarray(origin, np.float32).reshape(3)
+        capi.check(self._L.mppi_set_occupancy(self._h, capi.fptr(o), occ.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              0.0 if max_dist is None else float(max_dist)), "set_occupancy")
+
+    def get_distance_field(self):
+        """``(d, origin)``: the field as it stands on the device, (nz, ny, nx) float32 and (3,) -- what the
+        controller sees after ``set_distance_field`` or ``set_occupancy``; None while the field is cleared."""
+        if self.field is None:
+            raise RuntimeError("engine created without a field (Engine(cfg, field=DistanceField(...)))")
+        is_set = C.c_int32(0)
+        capi.check(self._L.mppi_get_distance_field(self._h, C.byref(is_set), None, None), "get_distance_field")
+        if not is_set.value:
+            return None
+        d, o = np.empty(self.field.shape, np.float32), np.empty(3, np.float32)
+        capi.check(self._L.mppi_get_distance_field(self._h, None, capi.fptr(o), capi.fptr(d)), "get_distance_field")
+        return d, o
 
     def get_clearances(self) -> np.ndarray:
         """(V, K): every sample's min clearance to the obstacles over the horizon and the body

@@ -221,7 +221,7 @@ class SolverBase:
     # the engine a field engine (with ``scene``, or the placeholder spheres); its data, when it has some,
     # is the field until set_distance_field / clear_distance_field.
     _field = None
-    _field_data = None     # (d, origin or None) of set_distance_field; None: cleared
+    _field_data = None     # (d, origin or None) of set_distance_field, (occ, origin or None, max_dist) of set_occupancy; None: cleared
     _field_sent = None     # (engine, data) last written (_sync_field)
 
     def set_distance_field(self, d, origin=None) -> None:
@@ -231,6 +231,24 @@ class SolverBase:
             raise RuntimeError("set_distance_field needs field=... at construction")
         o = None if origin is None else np.ascontiguousarray(origin, np.float32).reshape(3).copy()
         self._field_data = (self._field.check(d).copy(), o)
+
+    def set_occupancy(self, occ, origin=None, max_dist=None) -> None:
+        """The distance field of an occupancy grid, built on the device (``Engine.set_occupancy``):
+        (nz, ny, nx) bool or uint8, nonzero = occupied.  Used from the next control call on."""
+        if self._field is None:
+            raise RuntimeError("set_occupancy needs field=... at construction")
+        o = None if origin is None else np.ascontiguousarray(origin, np.float32).reshape(3).copy()
+        self._field_data = (self._field.check_occupancy(occ).copy(), o, max_dist)
+
+    def get_distance_field(self):
+        """``(d, origin)`` of the field the engine holds (``Engine.get_distance_field``), or None while it
+        is cleared or before the first control call has made the engine."""
+        if self._field is None:
+            raise RuntimeError("get_distance_field needs field=... at construction")
+        if self._engine is None:
+            return None
+        self._sync_field(self._engine)
+        return self._engine.get_distance_field()
 
     def clear_distance_field(self) -> None:
         if self._field is None:
@@ -248,6 +266,8 @@ class SolverBase:
         if sent is None or sent[0] is not eng or sent[1] is not data:
             if data is None:
                 eng.clear_distance_field()
+            elif len(data) == 3:   # (occ, origin, max_dist) of set_occupancy
+                eng.set_occupancy(*data)
             else:
                 eng.set_distance_field(*data)
             self._field_sent = (eng, data)
