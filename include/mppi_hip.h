@@ -561,6 +561,50 @@ mppi_status mppi_set_occupancy(mppi_engine* e, const float* origin3, const uint8
  * engine not created by mppi_create_scene_field. */
 mppi_status mppi_get_distance_field(mppi_engine* e, int32_t* is_set, float* origin3, float* d_zyx);
 
+/* ---- Self-collision avoidance: pairs of body spheres in the scene rollout cost (the project's own
+ * term; what a MoveIt-style stack keeps as the allowed-collision matrix, turned round: the pairs that
+ * are NOT allowed to touch).  ARM and WHOLEBODY; DRONE (no chain: every pair is rigid) and QUADROTOR
+ * are MPPI_ERR_INVALID_ARG.
+ *
+ * A pair list is up to MPPI_MAX_SELF_PAIRS unordered pairs (a, b) of the scene's body spheres, indexed
+ * as in mppi_scene.body; engine-wide and fixed at creation.  With c_b(k,t) the sphere's world centre
+ * as the obstacle term defines it and g_ab = |c_a - c_b| - r_a - r_b,
+ *   x_self(k,t) = w_self sum_{(a,b)} max(0, margin - g_ab) + penalty [min_{(a,b)} g_ab < 0]
+ *   S_k += sum_{t<H} x_self(k,t)          (no discount; after the obstacle / field term)
+ * and the per-sample self clearance sclr_k = min_{t,(a,b)} g_ab (+inf with no pair).  The weights are
+ * the term's own (self margins are usually tighter than obstacle margins); project constants
+ * (mppi_self_collision_default): w_self = 100, margin = 0.02 m, penalty = 1e4.  The term does not
+ * depend on the base pose, so ARM and WHOLEBODY share the definition.
+ * sep(a, b) is the number of non-fixed chain joints j with f_lo < j <= f_hi (the two spheres' frames):
+ * a pair with sep = 0 is rigid -- its distance can never change -- and is refused as a configuration
+ * error (frames -1 and 0 of the Kinova chain, whose joint 0 is fixed, are such a pair). */
+#define MPPI_MAX_SELF_PAIRS 32
+typedef struct { int32_t n_pairs; int32_t pair[MPPI_MAX_SELF_PAIRS][2];
+                 float w_self, margin, penalty; int32_t reserved; } mppi_self_collision;
+/* Every pair of the scene's spheres (scene NULL: mppi_scene_default) with sep >= 3, in lexicographic
+ * (a, b) order, cut off at MPPI_MAX_SELF_PAIRS, with the default weights: like the default body
+ * spheres a placeholder for the user's collision model. */
+void mppi_self_collision_default(mppi_self_collision* out, const mppi_config* cfg, const mppi_scene* scene);
+/* mppi_create_scene / mppi_create_scene_field with a pair list (scene NULL: mppi_scene_default; field
+ * NULL: no distance field; self NULL: MPPI_ERR_INVALID_ARG).  MPPI_ERR_INVALID_ARG, with the pair
+ * named in mppi_last_error: what those refuse, the DRONE model, n_pairs outside 0..32, an index outside
+ * [0, n_body), a = b, the same unordered pair twice, a rigid pair, a non-finite or negative weight,
+ * margin or penalty; and an explicit block_threads whose block would not hold the kernel's LDS (the
+ * centres of the spheres that appear in a pair ride in a per-lane LDS column: 12 B per such sphere
+ * and thread; a block of 64 threads always fits, and block_threads = 0 picks the largest of 256, 128
+ * and 64 that keeps the block at or below 64 KiB).  The engine is a scene engine (and a field engine
+ * with `field`): mppi_set_obstacles, mppi_get_clearances, mppi_set_distance_field and
+ * mppi_set_occupancy work on it unchanged; mppi_get_plan's cost_t and S include the term.  Runs the
+ * self kernels (k_rollout_sc, with a field k_rollout_sf; no quiet form). */
+mppi_status mppi_create_scene_self(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field,
+                                   const mppi_self_collision* self, mppi_engine** out);
+/* sclr (V,K): the per-sample self clearances of the last rollout, valid as mppi_get_costs is.
+ * MPPI_ERR_STATE on an engine not created by mppi_create_scene_self. */
+mppi_status mppi_get_self_clearances(mppi_engine* e, float* sclr_vk);
+/* sclr (V,H): min_{(a,b)} g_ab at step t of the nominal plan (mppi_get_plan's rollout).
+ * MPPI_ERR_STATE on an engine not created by mppi_create_scene_self. */
+mppi_status mppi_get_plan_self_clearance(mppi_engine* e, float* sclr_vh);
+
 #define MPPI_MAX_ELITES 64
 /* The n lowest-cost samples of the last rollout of every vehicle, best first (synchronous).
  *   idx  (V,n) int32   sample index within this engine's K (a shard: local; global = shard_rank*K + idx)

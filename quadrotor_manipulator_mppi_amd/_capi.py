@@ -76,6 +76,14 @@ class FieldDesc(C.Structure):
     _fields_ = [("dims", C.c_int32 * 3), ("voxel", C.c_float), ("origin", C.c_float * 3), ("reserved", C.c_int32)]
 
 
+MAX_SELF_PAIRS = 32
+
+
+class SelfCollision(C.Structure):
+    _fields_ = [("n_pairs", C.c_int32), ("pair", (C.c_int32 * 2) * MAX_SELF_PAIRS),
+                ("w_self", C.c_float), ("margin", C.c_float), ("penalty", C.c_float), ("reserved", C.c_int32)]
+
+
 class Link(C.Structure):
     _fields_ = [("parent", C.c_int32), ("type", C.c_int32), ("xyz", C.c_double * 3), ("rpy", C.c_double * 3),
                 ("axis", C.c_double * 3), ("mass", C.c_double), ("com", C.c_double * 3),
@@ -159,6 +167,10 @@ PROTOTYPES = {
     "mppi_set_occupancy": (_ST, [_P, _F, C.POINTER(C.c_uint8), C.c_float]),
     "mppi_get_distance_field": (_ST, [_P, _I32, _F, _F]),
     "mppi_occupancy_field": (_ST, [C.POINTER(FieldDesc), C.POINTER(C.c_uint8), C.c_float, _F]),
+    "mppi_self_collision_default": (None, [C.POINTER(SelfCollision), _CFG, C.POINTER(Scene)]),
+    "mppi_create_scene_self": (_ST, [_CFG, C.POINTER(Scene), C.POINTER(FieldDesc), C.POINTER(SelfCollision), C.POINTER(_P)]),
+    "mppi_get_self_clearances": (_ST, [_P, _F]),
+    "mppi_get_plan_self_clearance": (_ST, [_P, _F]),
     "mppi_enable_timing": (_ST, [_P, C.c_int32]),
     "mppi_get_timing": (_ST, [_P, _D, _D, _I64, _I64]),
     "mppi_kernel_timing": (_ST, [_P, C.c_int32, _D, _D]),
@@ -193,6 +205,10 @@ DEBUG_PROTOTYPES = {
     "mppi_debug_field_step_launches": (C.c_int32, [_CFG, C.POINTER(Scene), C.POINTER(FieldDesc), _I32, C.c_char_p,
                                                    C.c_int32, C.POINTER(C.c_uint64)]),
     "mppi_debug_field_rollout_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_char_p, C.c_int32]),
+    "mppi_debug_self_layout": (C.c_int32, [_CFG, C.POINTER(Scene), C.POINTER(SelfCollision), _F, _F, _I32]),
+    "mppi_debug_self_step_launches": (C.c_int32, [_CFG, C.POINTER(Scene), C.POINTER(FieldDesc), C.POINTER(SelfCollision), _I32,
+                                                  C.c_char_p, C.c_int32]),
+    "mppi_debug_self_rollout_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_char_p, C.c_int32]),
     "mppi_debug_edt_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_int32]),
     "mppi_debug_field_words": (C.c_int32, [_P, _F]),
 }

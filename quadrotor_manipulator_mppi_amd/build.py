@@ -35,12 +35,15 @@ _ROLL = ["-fno-slp-vectorize", "-mllvm", "-amdgpu-kernarg-preload-count=11"]
 # both kernels are one wave's dependent chain (profiles/r05/sched_maxilp: C3 -0.28 us, quadrotor
 # K=4096 H=32 -0.25 us, K=65536 -0.8..-1.4 us; on the other units it measured mixed or slower)
 _MAXILP = ["-mllvm", "-amdgpu-sched-strategy=" + os.environ.get("MPPI_C3_SCHED", "max-ilp")]   # (knob: experiments)
+# the self-collision units: the four-chunk bodies' loop over the chunks is larger than the default budget of a
+# "#pragma unroll" (16384); left rolled, its per-chunk arrays were indexed at run time and went to scratch
+_SELF = _ROLL + ["-mllvm", "-pragma-unroll-threshold=131072"]
 _FIN = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 # (experiments: MPPI_MAXILP_UNITS = extra units built with max-ilp, comma-separated)
 _XI = [u for u in os.environ.get("MPPI_MAXILP_UNITS", "").split(",") if u]
 SOURCES = [(u, f + (_MAXILP if u in _XI else [])) for u, f in
            [("mppi_rollout_drone.hip", _ROLL), ("mppi_rollout_arm.hip", _ROLL), ("mppi_rollout_arm32.hip", _ROLL),
-            ("mppi_rollout_wb.hip", _ROLL), ("mppi_finalize.hip", _FIN), ("mppi_plan.hip", ["-fno-slp-vectorize"]),
+            ("mppi_rollout_wb.hip", _ROLL), ("mppi_rollout_sc.hip", _SELF), ("mppi_rollout_sf.hip", _SELF), ("mppi_finalize.hip", _FIN), ("mppi_plan.hip", ["-fno-slp-vectorize"]),
             ("mppi_elites.hip", []), ("mppi_edt.hip", [])]] + \
           [("mppi_rollout_arm_h32.hip", _ROLL + _MAXILP + os.environ.get("MPPI_C3_EXTRA", "").split()), ("mppi_rollout_quad.hip", _ROLL + _MAXILP),
            ("mppi_host_math.cpp", []), ("mppi_layout.cpp", []), ("mppi_engine.cpp", []), ("mppi_launches.cpp", []), ("mppi_step.cpp", []), ("mppi_debug.cpp", []),
@@ -54,6 +57,24 @@ KERNEL_UNITS = [s for s, _ in SOURCES if s.endswith(".hip")]
 
 def code_object_path(lib: str, unit: str) -> str:
     return os.path.splitext(lib)[0] + "." + os.path.splitext(unit)[0] + ".co"
+
+
+def kernel_resources(co: str) -> dict:
+    """kernel symbol -> {vgpr, agpr, sgpr, lds, scratch, vspill, sspill} from a code object's metadata
+    (llvm-readobj --notes): what the dispatch reserves per lane and per block.  tests/test_capi_self_collision_cpu.py
+    holds the self-collision units to a private segment of 0 with it."""
+    import re
+    readobj = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "llvm-readobj")
+    text = subprocess.run([readobj, "--notes", co], capture_output=True, text=True, check=True).stdout
+    keys = {"vgpr": "vgpr_count", "agpr": "agpr_count", "sgpr": "sgpr_count", "lds": "group_segment_fixed_size",
+            "scratch": "private_segment_fixed_size", "vspill": "vgpr_spill_count", "sspill": "sgpr_spill_count"}
+    out = {}
+    for item in re.split(r"\n\s*- \.agpr_count", text)[1:]:
+        item = ".agpr_count" + item.split("\namdhsa.target")[0]
+        name = re.search(r"\.name:\s+(\S+)", item)
+        if name:
+            out[name.group(1)] = {k: int(re.search(r"\." + v + r":\s+(\d+)", item).group(1)) for k, v in keys.items()}
+    return out
 
 
 ARCH = os.environ.get("MPPI_OFFLOAD_ARCH", "gfx950")

@@ -22,9 +22,9 @@ std::string fin_symbol(const FinParams& f, LaunchDesc* desc) {
     if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
-std::string roll_symbol(const DevParams& p, int threads, LaunchDesc* desc, const float* ttab, float* scene, const float* field) {
+std::string roll_symbol(const DevParams& p, int threads, LaunchDesc* desc, const float* ttab, float* scene, const float* field, int self_members) {
     LaunchDesc d{};
-    const int rc = describe(p, threads, &d, ttab, scene, field);
+    const int rc = describe(p, threads, &d, ttab, scene, field, self_members);
     if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
@@ -119,6 +119,7 @@ int32_t mppi_debug_plan_kernel(const int32_t* g, char* sym, int32_t len) {
     p.model = g[0]; p.A = g[1]; p.H = g[2]; p.V = g[3]; p.state_f64 = g[4]; p.q_literal_jinv = g[5];
     PlanParams pp;
     std::memset(&pp, 0, sizeof(pp));
+    pp.self_members = -1;   // (not a self engine: no dynamic LDS)
     LaunchDesc d{};
     {   const mppi_aql::Capture c(&d);
         if (mppi_launch_plan(&p, &pp, nullptr) != 0) return MPPI_ERR_INVALID_ARG; }
@@ -272,14 +273,23 @@ int32_t mppi_debug_queue_ring(mppi_engine* e) {
 // (n > 1) and for the last step.  A path the engine would not take is refused (mppi_last_error says
 // why).  tests/test_capi_step_launches_cpu.py.
 static int32_t step_launches(const mppi_config* cfg, const int32_t* sw, char* buf, int32_t len, const mppi_scene* scene,
-                             const mppi_field_desc* field = nullptr, uint64_t* field_arg = nullptr) {
+                             const mppi_field_desc* field = nullptr, uint64_t* field_arg = nullptr,
+                             const mppi_self_collision* self = nullptr) {
     if (!cfg || !sw || !buf || len <= 0 || sw[0] < 0 || sw[0] > 3 || sw[1] < 1)
         return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_step_launches: bad arguments");
     mppi_status st = validate(*cfg);
     if (st != MPPI_OK) return st;
     const auto eng = std::make_unique<mppi_engine>();
     mppi_engine* e = eng.get();
-    if ((st = layout_of(*cfg, *e)) != MPPI_OK) return st;
+    if (self) {   // a self engine's (mppi_create_scene_self; with a scene): its block and its paired spheres
+        if (!scene) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_self_step_launches: a self engine has a scene");
+        if ((st = scene_validate(*cfg, *scene)) != MPPI_OK || (st = self_validate(*cfg, *scene, self)) != MPPI_OK) return st;
+        if ((st = self_layout(*cfg, self_member_count(*self), *e)) != MPPI_OK) return st;
+        e->has_self = true;
+        e->self_members = self_member_count(*self);
+    } else if ((st = layout_of(*cfg, *e)) != MPPI_OK) {
+        return st;
+    }
     const int path = sw[0], n = path == 1 || path == 3 ? 1 : sw[1];
     const auto stand_in = [](uintptr_t a) { return (void*)a; };
     set_generic(*e, sw[5]);
@@ -348,7 +358,7 @@ static int32_t step_launches(const mppi_config* cfg, const int32_t* sw, char* bu
         const StepPath sp = path < 2 ? StepPath::Hip : path == 2 ? StepPath::Batch : StepPath::Call;
         DevParams p = rollout_params(e, sp, noise, !last);
         if (sp == StepPath::Hip) p.step_ctr = (uint32_t)i;   // (rollout_impl: the launch's own)
-        report(last, "rollout", describe(p, e->threads, &d, e->d_ttab, e->d_scene, e->d_field), d);
+        report(last, "rollout", describe(p, e->threads, &d, e->d_ttab, e->d_scene, e->d_field, e->self_members), d);
         if (field_arg) std::memcpy(field_arg, d.args + kRollFieldOff, sizeof(*field_arg));   // (the last rollout's)
         if (sp == StepPath::Hip && sharded(e)) {
             const FinParams f = finalize_params(e, FinKind::Pack);
@@ -385,7 +395,15 @@ int32_t mppi_debug_field_step_launches(const mppi_config* cfg, const mppi_scene*
     return step_launches(cfg, sw, buf, len, scene, field, field_arg);
 }
 
-static int32_t scene_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len, bool field);
+// Likewise for an engine of mppi_create_scene_self(cfg, scene, field, self) (field may be null).
+// tests/test_capi_self_collision_cpu.py.
+int32_t mppi_debug_self_step_launches(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field,
+                                      const mppi_self_collision* self, const int32_t* sw, char* buf, int32_t len) {
+    if (!scene || !self) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_self_step_launches: bad arguments");
+    return step_launches(cfg, sw, buf, len, scene, field, nullptr, self);
+}
+
+static int32_t scene_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len, bool field, int self_members = -1);
 // mppi_debug_rollout_kernels for a scene engine's launches (same g): the scene kernel into both.
 int32_t mppi_debug_scene_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len) {
     return scene_rollout_kernels(g, full, quiet, len, false);
@@ -394,7 +412,12 @@ int32_t mppi_debug_scene_rollout_kernels(const int32_t* g, char* full, char* qui
 int32_t mppi_debug_field_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len) {
     return scene_rollout_kernels(g, full, quiet, len, true);
 }
-static int32_t scene_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len, bool field) {
+// and for a self engine's (g[15]: with a field; g[16]: the paired spheres): the self kernel into both.
+int32_t mppi_debug_self_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len) {
+    if (!g || g[16] < 0) return MPPI_ERR_INVALID_ARG;
+    return scene_rollout_kernels(g, full, quiet, len, g[15] != 0, g[16]);
+}
+static int32_t scene_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len, bool field, int self_members) {
     if (!g || !full || !quiet || len <= 0) return MPPI_ERR_INVALID_ARG;
     DevParams p;
     std::memset(&p, 0, sizeof(p));
@@ -406,9 +429,9 @@ static int32_t scene_rollout_kernels(const int32_t* g, char* full, char* quiet, 
     p.kern = g[14] ? kRollKernGeneric : 0;
     static float nowhere[4];   // described, not run: any non-null table and scene
     LaunchDesc da{}, db{};
-    const std::string a = roll_symbol(p, g[6], &da, nowhere, nowhere, field ? nowhere : nullptr);
+    const std::string a = roll_symbol(p, g[6], &da, nowhere, nowhere, field ? nowhere : nullptr, self_members);
     p.kern = quiet_roll_kern(p.kern, g[14] ? kGenericAll : 0, false, g[13] != 0, false);
-    const std::string b = roll_symbol(p, g[6], &db, nowhere, nowhere, field ? nowhere : nullptr);
+    const std::string b = roll_symbol(p, g[6], &db, nowhere, nowhere, field ? nowhere : nullptr, self_members);
     snprintf(full, (size_t)len, "%s", a.c_str());
     snprintf(quiet, (size_t)len, "%s", b.c_str());
     note_launches(da, db, g_roll_launch);

@@ -272,6 +272,7 @@ struct PlanParams {
     float* scene;            // a scene engine's buffer (mppi_obstacles.h), else null: the obstacle term in cost_t
                              //   and S, the steps' clearances (V,H) written at its plan offset
     const float* field;      // a field engine's buffer (mppi_field.h; with scene), else null: one more obstacle in that term
+    int32_t self_members;    // a self engine's paired spheres (mppi_self.h; with scene), else -1: the launch's dynamic LDS
 };
 
 // Finalize / pack kernel parameters.
@@ -345,6 +346,10 @@ int mppi_launch_rollout_arm64_df(const mppi::DevParams* p, const float* ttab, fl
 int mppi_launch_rollout_arm64_h32_df(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int block_threads, void* stream);
 int mppi_launch_rollout_arm32_df(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int block_threads, void* stream);
 int mppi_launch_rollout_wb_df(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int block_threads, void* stream);
+// the self rollouts (an engine of mppi_create_scene_self; mppi_self.h): members = the spheres that appear in a
+// pair; field null: k_rollout_sc, else k_rollout_sf (mppi_rollout_sc.hip, mppi_rollout_sf.hip)
+int mppi_launch_rollout_self(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int members, int block_threads, void* stream);
+int mppi_launch_rollout_self_field(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int members, int block_threads, void* stream);
 int mppi_launch_finalize(const mppi::FinParams* p, void* stream);
 int mppi_launch_plan(const mppi::DevParams* p, const mppi::PlanParams* pp, void* stream);
 int mppi_launch_peer_probe(unsigned long long* const* peers, unsigned long long* local, int n, int me,

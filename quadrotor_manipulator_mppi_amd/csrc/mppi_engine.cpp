@@ -257,6 +257,11 @@ mppi_status drain_timing(mppi_engine* e) {
 }
 
 // ---- mppi_create's device stages (a failure leaves a half-built engine for mppi_destroy)
+// a scene engine's buffer: a self engine's carries the pair region behind it (mppi_self.h)
+static int64_t scene_buffer_words(const mppi_engine* e) {
+    return e->has_self ? self_words(e->V, e->K, e->H) : scene_words(e->V, e->K, e->H);
+}
+
 static mppi_status allocate(mppi_engine* e) {
     const mppi_config& c = e->cfg;
     const size_t VHA = (size_t)e->V * e->H * e->A, VK = (size_t)e->V * e->K, nb = e->dp.nb;
@@ -286,7 +291,7 @@ static mppi_status allocate(mppi_engine* e) {
         HIP_TRY(hipEventCreateWithFlags(&e->ev_tt, hipEventDisableTiming));
     }
     if (e->has_scene) {   // the scene buffer, the vehicles' obstacle blocks' pinned staging copy, the uploads' event
-        HIP_TRY(hipMalloc(&e->d_scene, sizeof(float) * (size_t)scene_words(e->V, e->K, e->H)));
+        HIP_TRY(hipMalloc(&e->d_scene, sizeof(float) * (size_t)scene_buffer_words(e)));
         HIP_TRY(hipHostMalloc((void**)&e->h_scene, sizeof(float) * (size_t)e->V * kSceneObsW, hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&e->ev_scene, hipEventDisableTiming));
     }
@@ -351,8 +356,12 @@ static mppi_status upload(mppi_engine* e) {
         e->batch.ttab = e->call.ttab = e->d_ttab;
     }
     if (e->d_scene) {   // the body table; every vehicle without obstacles (zero words: n = 0)
-        HIP_TRY(hipMemset(e->d_scene, 0, sizeof(float) * (size_t)scene_words(e->V, e->K, e->H)));
+        HIP_TRY(hipMemset(e->d_scene, 0, sizeof(float) * (size_t)scene_buffer_words(e)));
         HIP_TRY(hipMemcpy(e->d_scene, e->scene_body.data(), sizeof(float) * kSceneBodyW, hipMemcpyHostToDevice));
+        if (e->has_self) {   // the pair region's header and tables (the body table's word kSelfWord holds its offset)
+            HIP_TRY(hipMemcpy(e->d_scene + self_off(e->V, e->K, e->H), e->self_region.data(), sizeof(float) * kSelfHdrW, hipMemcpyHostToDevice));
+            e->batch.self_members = e->call.self_members = e->self_members;
+        }
         std::memset(e->h_scene, 0, sizeof(float) * (size_t)e->V * kSceneObsW);
         e->batch.scene = e->call.scene = e->d_scene;
     }
@@ -379,7 +388,8 @@ static mppi_status upload(mppi_engine* e) {
 
 using namespace mppi_host;
 
-static mppi_status create_engine(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field, mppi_engine** out);
+static mppi_status create_engine(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field, mppi_engine** out,
+                                 const mppi_self_collision* self = nullptr);
 
 extern "C" {
 
@@ -400,23 +410,46 @@ mppi_status mppi_create_scene_field(const mppi_config* cfg, const mppi_scene* sc
     return create_engine(cfg, &use, field, out);
 }
 
-static mppi_status create_engine(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field, mppi_engine** out) {
+mppi_status mppi_create_scene_self(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field,
+                                   const mppi_self_collision* self, mppi_engine** out) {
+    if (!cfg || !out) return fail(MPPI_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    mppi_status st = validate(*cfg);
+    if (st != MPPI_OK) return st;
+    mppi_scene use;
+    if ((st = self_engine_validate(*cfg, scene, field, self, use)) != MPPI_OK) return st;
+    return create_engine(cfg, &use, field, out, self);
+}
+
+static mppi_status create_engine(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field, mppi_engine** out,
+                                 const mppi_self_collision* self) {
     if (!cfg || !out) return fail(MPPI_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     mppi_status st = validate(*cfg);
     if (st != MPPI_OK) return st;
     if (scene && (st = scene_validate(*cfg, *scene)) != MPPI_OK) return st;
     if (field && (st = field_validate(field)) != MPPI_OK) return st;
+    if (self && !scene) return fail(MPPI_ERR_INVALID_ARG, "self: a self engine has a scene");
+    if (self && (st = self_validate(*cfg, *scene, self)) != MPPI_OK) return st;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (cfg->device < 0 || cfg->device >= ndev)
         return fail(MPPI_ERR_INVALID_ARG, "device %d not present (%d HIP devices)", cfg->device, ndev);
     EngineLayout lay{};
-    if ((st = layout_of(*cfg, lay)) != MPPI_OK) return st;
+    // (a self engine's block is sized by its centre column: self_layout)
+    if ((st = self ? self_layout(*cfg, self_member_count(*self), lay) : layout_of(*cfg, lay)) != MPPI_OK) return st;
     if (scene) {
         lay.has_scene = true;
         lay.scene_body.assign(kSceneBodyW, 0.0f);
-        scene_body_table(lay, *scene, lay.scene_body.data(), nullptr);
+        int order[MPPI_MAX_BODY_SPHERES] = {0};
+        scene_body_table(lay, *scene, lay.scene_body.data(), order);
+        if (self) {
+            lay.has_self = true;
+            lay.self_region.assign(kSelfHdrW, 0.0f);
+            lay.self_members = self_table(lay, *scene, *self, order, lay.self_region.data());
+            const int32_t off = (int32_t)self_off(lay.V, lay.K, lay.H);
+            std::memcpy(lay.scene_body.data() + kSelfWord, &off, sizeof(off));
+        }
     }
     if (field) {
         lay.has_field = true;
@@ -626,14 +659,14 @@ mppi_status mppi_kernel_timing_ex(mppi_engine* e, int32_t n, double* rollout_us,
     for (auto& x : ev) KT_TRY(hipEventCreate(&x));
     KT_TRY(hipMemcpyAsync(saved, e->d_u_prev, ub, hipMemcpyDeviceToDevice, e->stream));
     KT_TRY(hipEventRecord(ev[0], e->stream));
-    for (int i = 0; i < n && rc == 0; ++i) rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field);
+    for (int i = 0; i < n && rc == 0; ++i) rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members);
     KT_TRY(hipEventRecord(ev[1], e->stream));
     for (int i = 0; i < n && rc == 0; ++i) rc = mppi_launch_finalize(&f, e->stream);
     KT_TRY(hipEventRecord(ev[2], e->stream));
     // the kernels as a control step runs them: rollout after finalize (u_prev and the
     // records just written, cold in the other XCDs' L2)
     for (int i = 0; i < n && rc == 0 && pair_us; ++i) {
-        rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field);
+        rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members);
         if (rc == 0) rc = mppi_launch_finalize(&f, e->stream);
     }
     KT_TRY(hipEventRecord(ev[3], e->stream));
@@ -670,9 +703,9 @@ extern "C" mppi_status mppi_probe_sequence(mppi_engine* e, int32_t n, int32_t mo
     (void)hipEventCreate(&a); (void)hipEventCreate(&b);
     (void)hipEventRecord(a, e->stream);
     for (int i = 0; i < n; ++i) {
-        if (mode <= 2 || mode == 5) launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field);
+        if (mode <= 2 || mode == 5) launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members);
         if (mode == 0 || mode == 3) mppi_launch_boundary((float*)e->d_out, fb, e->stream);
-        if (mode == 1 || mode == 4) launch_rollout(p1, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field);
+        if (mode == 1 || mode == 4) launch_rollout(p1, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members);
         if (mode == 2) mppi_launch_finalize(&f, e->stream);
     }
     (void)hipEventRecord(b, e->stream);
@@ -815,6 +848,21 @@ mppi_status mppi_get_plan_clearance(mppi_engine* e, float* clr) {
     return download(e, clr, e->d_scene + scene_plan_off(e->V, e->K), sizeof(float) * e->V * e->H);
 }
 
+mppi_status mppi_get_self_clearances(mppi_engine* e, float* sclr) {
+    if (!e || !sclr) return fail(MPPI_ERR_INVALID_ARG, "null argument");
+    if (!e->has_self) return fail(MPPI_ERR_STATE, "engine created without self-collision pairs (mppi_create_scene_self)");
+    if (use_device(e)) return MPPI_ERR_HIP;
+    return download(e, sclr, e->d_scene + self_clr_off(e->V, e->K, e->H), sizeof(float) * e->V * e->K);
+}
+
+mppi_status mppi_get_plan_self_clearance(mppi_engine* e, float* sclr) {
+    if (!e || !sclr) return fail(MPPI_ERR_INVALID_ARG, "null argument");
+    if (!e->has_self) return fail(MPPI_ERR_STATE, "engine created without self-collision pairs (mppi_create_scene_self)");
+    const mppi_status st = mppi_get_plan(e, nullptr, nullptr, nullptr, nullptr);   // k_plan writes the steps' self clearances
+    if (st != MPPI_OK) return st;
+    return download(e, sclr, e->d_scene + self_plan_off(e->V, e->K, e->H), sizeof(float) * e->V * e->H);
+}
+
 mppi_status mppi_get_weights(mppi_engine* e, float* w) {
     if (!e || !w) return fail(MPPI_ERR_INVALID_ARG, "null argument");
     if (use_device(e)) return MPPI_ERR_HIP;
@@ -888,6 +936,7 @@ mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos
     pp.ttab = e->d_ttab;
     pp.scene = e->d_scene;
     pp.field = e->d_field;
+    pp.self_members = e->self_members;
     pp.traj = e->d_plan; pp.cost_t = pp.traj + n_traj; pp.pos_err = pp.cost_t + n_vh; pp.S = pp.pos_err + n_vh;
     HIP_TRY(hipMemcpyAsync(e->d_plan_vc, e->h_vc, sizeof(VehicleConst) * V, hipMemcpyHostToDevice, e->stream));
     const int rc = mppi_launch_plan(&e->dp, &pp, e->stream);

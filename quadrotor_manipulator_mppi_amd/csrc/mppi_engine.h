@@ -56,6 +56,7 @@ struct DescCache {
     const float* ttab = nullptr;   // a tracking engine's target table (its rollouts' extra argument; fixed per engine)
     float* scene = nullptr;        // a scene engine's buffer (likewise)
     const float* field = nullptr;  // a field engine's field buffer (likewise)
+    int self_members = -1;         // a self engine's paired spheres (likewise; -1: not one)
     // ignore_vc0: the vehicle constants (the state) may differ -- a control call patches them in
     bool matches(const mppi::DevParams& p, const mppi::FinParams& f, int threads, bool ignore_vc0) const;
     // describes (p, f) and, where given, the quiet pair; the launchers' status (0: valid again)
@@ -307,14 +308,16 @@ inline int32_t quiet_roll_kern(int32_t kern, int generic, bool diag, bool peer, 
 // A scene engine's (scene non-null) run the scene kernels, with or without the tracking bit.
 // A field engine's (field non-null, with its scene) run the field kernels.
 inline int launch_rollout(const mppi::DevParams& p, const float* ttab, int threads, void* stream, float* scene = nullptr,
-                          const float* field = nullptr) {
+                          const float* field = nullptr, int self_members = -1) {
+    // a self engine's (self_members >= 0: the spheres that appear in a pair; with its scene) run the self kernels
+    if (self_members >= 0) return mppi_launch_rollout_self(&p, ttab, scene, field, self_members, threads, stream);
     if (field) return mppi_launch_rollout_field(&p, ttab, scene, field, threads, stream);
     if (scene) return mppi_launch_rollout_scene(&p, ttab, scene, threads, stream);
     return (p.cost_terms & MPPI_COST_TARGET_TRACK) ? mppi_launch_rollout_track(&p, ttab, threads, stream)
                                                    : mppi_launch_rollout(&p, threads, stream);
 }
 int describe(const mppi::DevParams& p, int threads, mppi::LaunchDesc* d, const float* ttab = nullptr, float* scene = nullptr,
-             const float* field = nullptr);
+             const float* field = nullptr, int self_members = -1);
 int describe(const mppi::FinParams& f, mppi::LaunchDesc* d);
 // -------------------------------------------------------------- step (mppi_step.cpp)
 // why this engine's steps cannot go native (nullptr: they can).  A batch may carry the stamps /
@@ -326,7 +329,7 @@ const char* aql_ineligible(const mppi_engine* e, bool batch = false);
 // the symbol a launch would run, by the launchers' own description of it ("?": none)
 std::string fin_symbol(const mppi::FinParams& f, mppi::LaunchDesc* desc = nullptr);
 std::string roll_symbol(const mppi::DevParams& p, int threads, mppi::LaunchDesc* desc = nullptr, const float* ttab = nullptr,
-                        float* scene = nullptr, const float* field = nullptr);
+                        float* scene = nullptr, const float* field = nullptr, int self_members = -1);
 
 // ------------------------------------------------------ exchange (mppi_exchange.cpp)
 // RCCL, resolved at the first mppi_comm_* call (dlopen: the library loads and its single-GPU

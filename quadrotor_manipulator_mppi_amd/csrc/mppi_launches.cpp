@@ -73,9 +73,9 @@ FinParams finalize_params(const mppi_engine* e, FinKind kind, StepPath path, boo
     return f;
 }
 
-int describe(const DevParams& p, int threads, LaunchDesc* d, const float* ttab, float* scene, const float* field) {
+int describe(const DevParams& p, int threads, LaunchDesc* d, const float* ttab, float* scene, const float* field, int self_members) {
     const mppi_aql::Capture c(d);
-    return launch_rollout(p, ttab, threads, nullptr, scene, field);
+    return launch_rollout(p, ttab, threads, nullptr, scene, field, self_members);
 }
 int describe(const FinParams& f, LaunchDesc* d) {
     const mppi_aql::Capture c(d);
@@ -98,7 +98,7 @@ int DescCache::refresh(const DevParams& p_, const FinParams& f_, int threads_, c
                        const FinParams* f_quiet) {
     valid = false;
     int rc;
-    if ((rc = describe(p_, threads_, &roll, ttab, scene, field)) != 0 || (p_quiet && (rc = describe(*p_quiet, threads_, &roll_quiet, ttab, scene, field)) != 0) ||
+    if ((rc = describe(p_, threads_, &roll, ttab, scene, field, self_members)) != 0 || (p_quiet && (rc = describe(*p_quiet, threads_, &roll_quiet, ttab, scene, field, self_members)) != 0) ||
         (rc = describe(f_, &fin)) != 0 || (f_quiet && (rc = describe(*f_quiet, &fin_quiet)) != 0))
         return rc;
     p = p_;

@@ -24,7 +24,7 @@ static mppi_status geometry(EngineLayout& l) {
     if (nch != 1 && nch != 2 && nch != 4)
         return fail(MPPI_ERR_INVALID_ARG, "H=%d: supported horizons are <= 128 or 193..256", H);
     const int R = 64 / L;
-    l.threads = c.block_threads ? c.block_threads : 512;
+    l.threads = c.block_threads ? c.block_threads : l.auto_threads;
     const int nw = l.threads / 64;
     const int groups = (l.K + nw * R - 1) / (nw * R);
     int nb = c.blocks_per_vehicle;
@@ -357,6 +357,107 @@ void field_pack(const mppi_field_desc& f, const float* d_zyx, float* cells) {
     }
 }
 
+// ------------------------------------------------------------------ self-collision pairs
+int self_sep(const mppi_config& c, int fa, int fb) {
+    const int lo = std::min(fa, fb), hi = std::max(fa, fb);
+    int n = 0;
+    for (int j = lo + 1; j <= hi && j < c.n_joints; ++j)
+        if (j >= 0 && c.joints[j].type != MPPI_JOINT_FIXED) ++n;
+    return n;
+}
+
+mppi_status self_validate(const mppi_config& c, const mppi_scene& s, const mppi_self_collision* sc) {
+    if (!sc) return fail(MPPI_ERR_INVALID_ARG, "self: null pair list");
+    if (c.model != MPPI_MODEL_ARM && c.model != MPPI_MODEL_WHOLEBODY)
+        return fail(MPPI_ERR_INVALID_ARG, "self: self-collision pairs need the ARM or WHOLEBODY model (no chain: every pair is rigid)");
+    if (sc->n_pairs < 0 || sc->n_pairs > MPPI_MAX_SELF_PAIRS)
+        return fail(MPPI_ERR_INVALID_ARG, "self: n_pairs %d outside 0..%d", sc->n_pairs, MPPI_MAX_SELF_PAIRS);
+    const float w[3] = {sc->w_self, sc->margin, sc->penalty};
+    for (const float x : w)
+        if (!std::isfinite(x) || x < 0.0f) return fail(MPPI_ERR_INVALID_ARG, "self: w_self, margin and penalty are finite and >= 0");
+    for (int i = 0; i < sc->n_pairs; ++i) {
+        const int a = sc->pair[i][0], b = sc->pair[i][1];
+        if (a < 0 || a >= s.n_body || b < 0 || b >= s.n_body)
+            return fail(MPPI_ERR_INVALID_ARG, "self: pair %d (%d, %d) has an index outside [0, %d)", i, a, b, s.n_body);
+        if (a == b) return fail(MPPI_ERR_INVALID_ARG, "self: pair %d (%d, %d) pairs a sphere with itself", i, a, b);
+        for (int k = 0; k < i; ++k)
+            if ((sc->pair[k][0] == a && sc->pair[k][1] == b) || (sc->pair[k][0] == b && sc->pair[k][1] == a))
+                return fail(MPPI_ERR_INVALID_ARG, "self: pair %d (%d, %d) repeats pair %d", i, a, b, k);
+        if (self_sep(c, s.body[a].frame, s.body[b].frame) == 0)
+            return fail(MPPI_ERR_INVALID_ARG, "self: pair %d (%d, %d) is rigid: no moving joint between frames %d and %d", i, a, b,
+                        s.body[a].frame, s.body[b].frame);
+    }
+    return MPPI_OK;
+}
+
+mppi_status self_engine_validate(const mppi_config& c, const mppi_scene* scene, const mppi_field_desc* f,
+                                 const mppi_self_collision* sc, mppi_scene& use) {
+    if (scene) use = *scene;
+    else mppi_scene_default(&use, &c);
+    mppi_status st = scene_validate(c, use);
+    if (st != MPPI_OK) return st;
+    if (f && (st = field_validate(f)) != MPPI_OK) return st;
+    return self_validate(c, use, sc);
+}
+
+int self_member_count(const mppi_self_collision& sc) {
+    bool used[MPPI_MAX_BODY_SPHERES] = {false};
+    for (int i = 0; i < sc.n_pairs; ++i)
+        for (int e = 0; e < 2; ++e) used[sc.pair[i][e]] = true;
+    return (int)std::count(used, used + MPPI_MAX_BODY_SPHERES, true);
+}
+
+int self_table(const EngineLayout& l, const mppi_scene& s, const mppi_self_collision& sc, const int* order, float* region) {
+    std::memset(region, 0, sizeof(float) * kSelfHdrW);
+    const auto put = [&](int i, int32_t x) { std::memcpy(region + i, &x, sizeof(x)); };
+    int pos[MPPI_MAX_BODY_SPHERES] = {0};      // the caller's index -> the sorted position
+    for (int n = 0; n < s.n_body; ++n) pos[order[n]] = n;
+    bool used[MPPI_MAX_BODY_SPHERES] = {false};   // by sorted position
+    for (int i = 0; i < sc.n_pairs; ++i)
+        for (int e = 0; e < 2; ++e) used[pos[sc.pair[i][e]]] = true;
+    int member[MPPI_MAX_BODY_SPHERES], members = 0;
+    for (int n = 0; n < MPPI_MAX_BODY_SPHERES; ++n) {
+        member[n] = (n < s.n_body && used[n]) ? members++ : -1;
+        put(kSelfMem + n, member[n]);
+    }
+    for (int i = 0; i < sc.n_pairs; ++i) {
+        const int a = sc.pair[i][0], b = sc.pair[i][1];
+        put(kSelfPair + 3 * i, member[pos[a]]);
+        put(kSelfPair + 3 * i + 1, member[pos[b]]);
+        region[kSelfPair + 3 * i + 2] = s.body[a].radius + s.body[b].radius;
+    }
+    put(0, sc.n_pairs);
+    region[1] = sc.w_self; region[2] = sc.margin; region[3] = sc.penalty;
+    put(4, members);
+    put(5, (int32_t)self_clr_off(l.V, l.K, l.H));
+    put(6, (int32_t)self_plan_off(l.V, l.K, l.H));
+    return members;
+}
+
+mppi_status self_layout(const mppi_config& c, int members, EngineLayout& l) {
+    const auto bytes = [&]() { return self_dyn_lds(l.A, l.H, l.threads, l.dp.iters, members) + kSelfStaticLds; };
+    mppi_status st;
+    if (c.block_threads) {
+        if ((st = layout_of(c, l)) != MPPI_OK) return st;
+        if (l.threads < 64 || l.threads > 256 || l.threads % 64)
+            return fail(MPPI_ERR_INVALID_ARG, "self: block_threads %d: the self kernels run blocks of 64, 128, 192 or 256 threads", l.threads);
+        if (l.threads > 64 && bytes() > kSelfLdsTarget)
+            return fail(MPPI_ERR_INVALID_ARG, "self: block_threads %d needs %lld B of LDS with %d paired spheres at H = %d, more than the %d B "
+                        "a self block may hold: use a smaller block, or 0 for the largest that fits", l.threads, (long long)bytes(), members,
+                        l.H, kSelfLdsTarget);
+    } else {
+        for (const int t : {256, 128, 64}) {
+            l.auto_threads = t;
+            if ((st = layout_of(c, l)) != MPPI_OK) return st;
+            if (bytes() <= kSelfLdsTarget) break;
+        }
+    }
+    if (bytes() > kSelfLdsMax)
+        return fail(MPPI_ERR_INVALID_ARG, "self: a block of %d threads needs %lld B of LDS at H = %d, more than the CU holds", l.threads,
+                    (long long)bytes(), l.H);
+    return MPPI_OK;
+}
+
 // ------------------------------------------------------------------ occupancy grids
 mppi_status occupancy_validate(const float* origin3, const uint8_t* occ_zyx, float max_dist) {
     if (!occ_zyx) return fail(MPPI_ERR_INVALID_ARG, "occupancy: null grid");
@@ -441,6 +542,58 @@ extern "C" void mppi_scene_default(mppi_scene* s, const mppi_config* cfg) {
     if (cfg->model != MPPI_MODEL_DRONE)
         for (int j = 0; j < cfg->n_joints && j < MPPI_MAX_JOINTS; ++j)
             if (cfg->joints[j].type != MPPI_JOINT_FIXED) add(j, 0.05f);
+}
+
+// The project's default pair list (include/mppi_hip.h; the Python twin's weights: robot/body_spheres.py):
+// every pair of the scene's spheres with at least three moving joints between their frames, in (a, b)
+// order; w_self = 100, margin = 0.02 m, penalty = 1e4.
+extern "C" void mppi_self_collision_default(mppi_self_collision* out, const mppi_config* cfg, const mppi_scene* scene) {
+    if (!out) return;
+    std::memset(out, 0, sizeof(*out));
+    out->w_self = 100.0f; out->margin = 0.02f; out->penalty = 1e4f;
+    if (!cfg || (cfg->model != MPPI_MODEL_ARM && cfg->model != MPPI_MODEL_WHOLEBODY)) return;
+    mppi_scene use;
+    if (scene) use = *scene;
+    else mppi_scene_default(&use, cfg);
+    const int nb = std::min(std::max(use.n_body, 0), MPPI_MAX_BODY_SPHERES);
+    for (int a = 0; a < nb; ++a)
+        for (int b = a + 1; b < nb && out->n_pairs < MPPI_MAX_SELF_PAIRS; ++b)
+            if (self_sep(*cfg, use.body[a].frame, use.body[b].frame) >= 3) {
+                out->pair[out->n_pairs][0] = a;
+                out->pair[out->n_pairs][1] = b;
+                ++out->n_pairs;
+            }
+}
+
+// Diagnostic (no GPU): the argument check of mppi_create_scene_self (scene null: the default one; no
+// field) and the layout it makes.  table: the body table with the region's offset in word kSelfWord
+// (kSceneBodyW words); region: the pair region's header and tables (kSelfHdrW words); out (8 ints): the
+// block's threads, the members, the dynamic LDS bytes of a rollout block, the region's offset, the
+// buffer's words, nb, iters, the static LDS bound.  Any of the three may be null.  Returns the first
+// failing status (the message in mppi_last_error).  tests/test_capi_self_collision_cpu.py.
+extern "C" int32_t mppi_debug_self_layout(const mppi_config* cfg, const mppi_scene* scene, const mppi_self_collision* self,
+                                          float* table, float* region, int32_t* out) {
+    if (!cfg) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_self_layout: bad arguments");
+    mppi_status st = validate(*cfg);
+    if (st != MPPI_OK) return st;
+    mppi_scene use;
+    if ((st = self_engine_validate(*cfg, scene, nullptr, self, use)) != MPPI_OK) return st;
+    EngineLayout l;
+    if ((st = self_layout(*cfg, self_member_count(*self), l)) != MPPI_OK) return st;
+    float t[kSceneBodyW], r[kSelfHdrW];
+    int ord[MPPI_MAX_BODY_SPHERES] = {0};
+    scene_body_table(l, use, t, ord);
+    const int32_t off = (int32_t)self_off(l.V, l.K, l.H);
+    std::memcpy(t + kSelfWord, &off, sizeof(off));
+    const int members = self_table(l, use, *self, ord, r);
+    if (table) std::memcpy(table, t, sizeof(t));
+    if (region) std::memcpy(region, r, sizeof(r));
+    if (out) {
+        const int32_t w[8] = {l.threads, members, (int32_t)self_dyn_lds(l.A, l.H, l.threads, l.dp.iters, members), off,
+                              (int32_t)self_words(l.V, l.K, l.H), l.dp.nb, l.dp.iters, kSelfStaticLds};
+        std::memcpy(out, w, sizeof(w));
+    }
+    return MPPI_OK;
 }
 
 // The occupancy grid's distance field on the host (include/mppi_hip.h): mppi_set_occupancy's definition

@@ -8,6 +8,7 @@
 #include "mppi_dev.h"
 #include "mppi_obstacles.h"
 #include "mppi_field.h"
+#include "mppi_self.h"
 #include "mppi_edt.h"
 
 // mppi_engine::generic with every part switched back (MPPI_GENERIC_KERNELS=1)
@@ -55,6 +56,10 @@ struct EngineLayout {
     std::vector<float> scene_body;
     bool has_field = false;             // mppi_create_scene_field (with has_scene): the field kernels; its descriptor
     mppi_field_desc field{};
+    bool has_self = false;              // mppi_create_scene_self (with has_scene): the self kernels; the pair region's
+    std::vector<float> self_region;     // header and tables (kSelfHdrW words) and the spheres that appear in a pair
+    int self_members = -1;              // (the centre column's rows; -1: not a self engine)
+    int auto_threads = 512;             // the block of a configuration with block_threads = 0 (a self engine: self_layout)
     int fin_ts = 1, fin_tsz = 8;        // finalize t-slices
     int generic = 0;                    // MPPI_GENERIC_KERNELS=1 (tests, A/B): the kernels as before the role and
                                         // fixed-block ones.  Bits: 1 the finalize of every role with run-time
@@ -91,6 +96,24 @@ mppi_status field_engine_validate(const mppi_config& c, const mppi_scene* scene,
 mppi_status field_data_validate(const mppi_field_desc& f, const float* origin3, const float* d_zyx);
 void field_header(const mppi_field_desc& f, const float* origin3, bool set, float* hdr);
 void field_pack(const mppi_field_desc& f, const float* d_zyx, float* cells);
+// ------------------------------------------------- self-collision pairs (mppi_layout.cpp; mppi_self.h)
+// self_validate: the errors of mppi_create_scene_self's pair list, for a configuration and a scene that
+// passed validate() and scene_validate(); every message names the pair.
+// self_sep: the non-fixed chain joints between two frames (0: a rigid pair).
+// self_table: the region's header and tables (kSelfHdrW words) for a layout -- the caller's sphere indices
+// mapped through the body table's sort order (order: sorted position -> the caller's index, as
+// scene_body_table returns it); returns the number of members.
+// self_layout: layout_of for a self engine with that many members -- with block_threads = 0 the largest
+// block of 256, 128, 64 threads whose LDS stays within kSelfLdsTarget (64 where none does); an explicit
+// block the kernels cannot serve is refused with a message.
+// self_engine_validate: the whole of mppi_create_scene_self's argument check after validate().
+mppi_status self_validate(const mppi_config& c, const mppi_scene& s, const mppi_self_collision* sc);
+int self_sep(const mppi_config& c, int frame_a, int frame_b);
+int self_table(const EngineLayout& l, const mppi_scene& s, const mppi_self_collision& sc, const int* order, float* region);
+int self_member_count(const mppi_self_collision& sc);
+mppi_status self_layout(const mppi_config& c, int members, EngineLayout& l);
+mppi_status self_engine_validate(const mppi_config& c, const mppi_scene* scene, const mppi_field_desc* f,
+                                 const mppi_self_collision* sc, mppi_scene& use);
 // ------------------------------------------------- occupancy grids (mppi_layout.cpp; mppi_edt.h)
 // occupancy_validate: the errors of mppi_set_occupancy's arguments (origin3 may be null).
 // occupancy_field: the host twin of the device transform (mppi_edt.hip) -- the same definition and the

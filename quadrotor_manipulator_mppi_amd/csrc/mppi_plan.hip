@@ -18,6 +18,7 @@
 #include "mppi_integrator.h"   // seg_scan_f32_multi
 #include "mppi_obstacles.h"
 #include "mppi_field.h"
+#include "mppi_self.h"
 #include "mppi_quad_step.h"
 
 namespace {
@@ -165,6 +166,12 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     __shared__ float tot1[kMaxWaves][NA], tot2[kMaxWaves][NA];   // the waves' scan totals (the chunk carries)
     __shared__ float wsum[kMaxWaves];
     __shared__ __attribute__((aligned(16))) float scn[kSceneLdsW + kFieldHdrW];   // a scene engine's body table and obstacles, a field engine's field header
+    // a self engine's pair tables and the lanes' centre columns (mppi_self.h; pitch = the block's threads), in
+    // dynamic LDS the launch sizes by the engine's paired spheres: none on every other engine
+    constexpr bool kSelf = MODEL != MPPI_MODEL_DRONE;
+    extern __shared__ __attribute__((aligned(16))) float plan_dyn[];
+    float* const slf = plan_dyn;
+    float* const scolumn = plan_dyn + kSelfHdrW;
     const DevParams& p = pk;
     const int v = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int nthr = blockDim.x, nw = nthr >> 6;
@@ -186,6 +193,10 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     if (pp.scene)
         for (int i = tid; i < kSceneLdsW; i += nthr) scn[i] = pp.scene[i < kSceneBodyW ? i : i + v * kSceneObsW];
     if (pp.field && tid < kFieldHdrW) scn[kSceneLdsW + tid] = pp.field[tid];   // (a field engine has a scene)
+    // the pair region's offset in the scene buffer (the body table's spare word; 0: not a self engine)
+    const int soff = (kSelf && pp.scene && pp.self_members >= 0) ? scene_int(pp.scene + kSelfWord) : 0;
+    if (soff)
+        for (int i = tid; i < kSelfHdrW; i += nthr) slf[i] = pp.scene[(size_t)soff + i];
     const VehicleConst& vc = vcv;
 
     // ---- double integrator (standard_normal_noise.py:41-48), k_rollout's NCH > 1 arithmetic
@@ -249,6 +260,7 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     float cost, perr;
     // a scene engine's term of this step: the hinge sum and the min clearance at row time (t + 1) dt
     float oh = 0.0f, og = INFINITY;
+    float sh = 0.0f, sg = INFINITY;   // a self engine's: the pairs' hinge sum and min clearance
     const float otau = (float)(t + 1) * p.dt;
     if (MODEL == MPPI_MODEL_DRONE) {
         const float dx = posf[0] - tg[0], dy = posf[1] - tg[1], dz = posf[2] - tg[2];
@@ -266,9 +278,13 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     } else {
         Mat34 T;
         plan_fk<MODEL, NA, F64>(T, posf, posd, vc, jnt, p, [&](int slot) {
-            if (pp.field) obs_frame_field(T.m, scn, scn + kSceneBodyW, slot, otau, scn + kSceneLdsW, pp.field + kFieldHdrW, oh, og);
+            if (soff && pp.field) obs_frame_self<true>(T.m, scn, scn + kSceneBodyW, slot, otau, scn + kSceneLdsW, pp.field + kFieldHdrW, slf,
+                                                       scolumn + tid, nthr, oh, og);
+            else if (soff) obs_frame_self<false>(T.m, scn, scn + kSceneBodyW, slot, otau, nullptr, nullptr, slf, scolumn + tid, nthr, oh, og);
+            else if (pp.field) obs_frame_field(T.m, scn, scn + kSceneBodyW, slot, otau, scn + kSceneLdsW, pp.field + kFieldHdrW, oh, og);
             else if (pp.scene) obs_frame(T.m, scn, scn + kSceneBodyW, slot, otau, oh, og);
         });
+        if (soff) self_pairs(slf, scolumn + tid, nthr, sh, sg);   // (each lane reads what it wrote: no barrier)
         cost = pose_cost_row(T, tg, term ? p.w_tp : p.w_sp, term ? p.w_to : p.w_so);
         perr = fabsf(T.m[3] - tg[0]) + fabsf(T.m[7] - tg[1]) + fabsf(T.m[11] - tg[2]);
         if (val) {
@@ -294,6 +310,10 @@ __global__ void __launch_bounds__(256) k_plan(const float* __restrict__ u_prev, 
     if (pp.scene) {   // after the CostManager terms, as the rollout adds it
         cost += obs_step_cost(scn, oh, og);
         if (val) pp.scene[(size_t)scene_int(scn + 5) + (size_t)v * H + t] = og;
+    }
+    if (soff) {   // after the obstacle term, as the rollout adds it
+        cost += self_step_cost(slf, sh, sg);
+        if (val) pp.scene[(size_t)scene_int(slf + 6) + (size_t)v * H + t] = sg;
     }
     if (val) {
         pp.cost_t[(size_t)v * H + t] = cost;
@@ -364,7 +384,10 @@ extern "C" int mppi_launch_plan(const DevParams* p, const PlanParams* pp, void* 
     const hipStream_t s = (hipStream_t)stream;
     if (p->H < 1 || p->H > MPPI_MAX_HORIZON || p->V < 1) return -1;
     const dim3 grid(p->V), block(64 * ((p->H + 63) / 64));   // a block per vehicle, a lane per horizon step
-    const auto chain = [&](auto k) { return go(k, grid, block, 0, s, p->u_prev, p->joints, *pp, *p); };
+    // a self engine's pair tables and centre column (mppi_self.h): at most 120 + 3 * 16 * 256 words
+    if (pp->self_members > kSelfMaxMembers || (pp->self_members >= 0 && !pp->scene)) return -1;
+    const size_t lds = pp->self_members >= 0 ? sizeof(float) * (size_t)(kSelfHdrW + 3 * pp->self_members * (int)block.x) : 0;
+    const auto chain = [&](auto k) { return go(k, grid, block, lds, s, p->u_prev, p->joints, *pp, *p); };
     switch (p->model) {
         case MPPI_MODEL_DRONE:
             if (p->A == 3) return chain(k_plan<MPPI_MODEL_DRONE, 3, false>);

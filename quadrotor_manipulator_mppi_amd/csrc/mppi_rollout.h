@@ -28,6 +28,7 @@
 #include "mppi_integrator.h"
 #include "mppi_obstacles.h"
 #include "mppi_field.h"
+#include "mppi_self.h"
 
 // The leading scalar arguments are preloaded into SGPRs at wave launch on gfx950
 // (-mllvm -amdgpu-kernarg-preload-count, build.py): the first group's Philox
@@ -54,8 +55,23 @@
 // Sigma 72.1 -> 43.6 us, arm 21.8 -> 19.3); XC NCH == 1 keeps 4 (2 and 3 measured slower;
 // profiles/r02/ab_rollout_occupancy_xc.txt)
 // the scene body's accumulators (a hinge or cost sum, a min clearance); nothing in the other bodies
+// A kernel-argument float read where it is used (the self bodies' cost-term weights): the address depends on an
+// opaque zero, so the load is not hoisted to the prologue and merged with its neighbours into one 16 B load.  That
+// load lived to the end of the kernel; the scalar allocator gave it a stack slot, then rematerialised every use,
+// and the unused slot stayed in the kernel's private segment (20 B with the scavenging word, no instruction
+// addressing it) in the one-vehicle forms.
+__device__ __forceinline__ float late_arg(const float& x) {
+    int z = 0;
+    asm volatile("" : "+s"(z));
+    return (&x)[z];
+}
 template <bool OBS> struct ObsAcc {};
 template <> struct ObsAcc<true> { float sum = 0.0f, gmin = INFINITY; };
+// the self body's: those, and the self-collision pairs' hinge or cost sum and min clearance.  One object with the
+// scene's, not a second one: a further (empty) accumulator in the other bodies moved registers in kernels this
+// header also builds for the drone.
+struct SelfAcc : ObsAcc<true> { float ssum = 0.0f, sgmin = INFINITY; };
+template <bool OBS, bool SLF> using RollAcc = std::conditional_t<SLF, SelfAcc, ObsAcc<OBS>>;
 template <int NCH, bool F64, bool XC, bool ONEG>
 constexpr int roll_occ() {
     return (ONEG && !F64) ? 8 : (NCH >= 4 ? 2 : NCH == 2 ? (XC ? 2 : 4) : 4);
@@ -82,8 +98,15 @@ constexpr int roll_occ() {
 // sphere the lane samples the field at the centre it has just formed (four 8 B loads of x-pairs; the
 // lanes of a segment are consecutive t of one sample, so neighbouring centres share lines) and feeds
 // g = d(c) - r_b into the same hinge sum and min.  A field not set is a wave-uniform skip.
+// SLF (k_rollout_sc, with FLD k_rollout_sf; mppi_create_scene_self): a scene body with the self-collision
+// pairs (mppi_self.h).  The pair tables ride in static LDS beside the scene; the chain walk stores the
+// centre of every sphere that appears in a pair into the lane's own LDS column (behind the staged runs:
+// 3 * members words per thread, no barrier), and after the chain of a (k, t) a wave-uniform loop over the
+// pairs forms the step's second hinge sum and min.  That term joins S after the obstacle term, and the
+// per-sample self clearance goes out as the clearance does, a third staged run.  ARM and WHOLEBODY, blocks
+// of at most 256 threads (launch_rollout_self sizes the LDS).
 template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE, bool XC, bool ONEG, bool B512, bool QUIET = false,
-          bool TRK = false, bool OBS = false, bool FLD = false>
+          bool TRK = false, bool OBS = false, bool FLD = false, bool SLF = false>
 __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint32_t seed_hi,
                                              const uint32_t step_arg, const uint32_t k_off,
                                              const int32_t noise_arg, const int32_t H_arg,
@@ -95,6 +118,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                                              const float* __restrict__ field = nullptr) {
     static_assert(!B512 || ONEG, "the fixed-block body is a single-group one");
     static_assert(!FLD || OBS, "the field body is a scene one");
+    static_assert(!SLF || (OBS && MODEL != MPPI_MODEL_DRONE), "the self body is a scene one of a model with a chain");
     static_assert(!OBS || (TRK && !B512), "the scene body is a tracking one of every block size");
     static_assert(!TRK || (XC && !QUIET), "the tracking body is an extended one, and has no quiet form");
     static_assert(!QUIET || (!XC && NCH == 1), "the quiet body exists for the common one-chunk kernels");
@@ -116,6 +140,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     __shared__ JointDev jnt[kMaxJ];
     __shared__ VehicleConst vcv;
     __shared__ __attribute__((aligned(16))) float scn[OBS ? kSceneLdsW + (FLD ? kFieldHdrW : 0) : 4];   // OBS: the body table, then the vehicle's obstacles (FLD: then the field's header)
+    __shared__ __attribute__((aligned(16))) float slf[SLF ? kSelfHdrW : 4];   // SLF: the pair region's header and tables
     const DevParams& p = pk;
     const int v = blockIdx.y;
     // block size and groups per block as one preloaded argument (threads | iters << 16): blockDim
@@ -179,6 +204,9 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     };
     float scr = 0.0f;
     if constexpr (OBS) scr = (tid < kSceneLdsW) ? scene_word(tid) : 0.0f;
+    // SLF: the pair region's offset in the scene buffer (the body table's spare word; uniform)
+    int soff = 0;
+    if constexpr (SLF) soff = scene_int(scene + kSelfWord);
     float fhr = 0.0f;   // FLD: the field header word this thread stages (the block's last wave: nthr >= 64 > kFieldHdrW)
     if constexpr (FLD) fhr = (tid >= nthr - kFieldHdrW) ? field[tid - (nthr - kFieldHdrW)] : 0.0f;
     // touch every kernel-argument line the hot phases read (one s_load per 64 B): they
@@ -300,6 +328,8 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     }
     if constexpr (FLD)
         if (tid >= nthr - kFieldHdrW) scn[kSceneLdsW + tid - (nthr - kFieldHdrW)] = fhr;
+    if constexpr (SLF)
+        for (int i = tid; i < kSelfHdrW; i += nthr) slf[i] = scene[(size_t)soff + i];
     STAMPW(8);
     if (!(MPPI_KO & 256)) lds_barrier();
     const VehicleConst& vc = vcv;
@@ -311,6 +341,9 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
     float* const s_stage = smem + ((HA + 3) & ~3) + 8 * kWs;
     // OBS: the block's clearances, staged the same way behind the costs
     float* const c_stage = OBS ? s_stage + iters * cost_run_stride(nw * R) : nullptr;
+    // SLF: the self clearances behind those, then the centre column (this lane's words: pitch nthr)
+    float* const sc_stage = SLF ? c_stage + iters * cost_run_stride(nw * R) : nullptr;
+    float* const scol = SLF ? sc_stage + iters * cost_run_stride(nw * R) + tid : nullptr;
     STAMP(1);
 
     // trajectory planes of vehicle v (from kernel arguments and blockIdx only, so the
@@ -521,7 +554,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
         // ---- A4-A10: FK + per-step cost, trajectory planes
         float xs[NCH];
         float ecen = 0.0f, ejt = 0.0f, elim = 0.0f;
-        ObsAcc<OBS> oacc;   // OBS: the lane's obstacle term and min clearance over its steps
+        RollAcc<OBS, SLF> oacc;   // OBS: the lane's obstacle term and min clearance over its steps (SLF: and the self-collision term's)
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             const int t = t0 + 64 * c;
@@ -529,7 +562,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             const bool term = (t == H - 1);
             float x;
             // OBS: this step's hinge sum and min clearance (the obstacles at their row time (t + 1) dt)
-            ObsAcc<OBS> ostep;
+            RollAcc<OBS, SLF> ostep;   // (SLF: and the pairs' hinge sum and min clearance of this step)
             const uint32_t toff = ((uint32_t)k * (uint32_t)hp + (uint32_t)t) * 4u;   // byte offset in a plane
             const bool stv = kTraj && HOT(store_traj) && kval && t < hp;   // row incl. its pad (finite values)
             if (MODEL == MPPI_MODEL_DRONE) {
@@ -562,7 +595,9 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 }
                 // OBS: the spheres of a frame slot as soon as T is that frame (slot 0: the folded base)
                 auto obs_at = [&](int slot) __attribute__((always_inline)) {
-                    if constexpr (FLD) obs_frame_field(T.m, scn, scn + kSceneBodyW, slot, (float)(t + 1) * p.dt, scn + kSceneLdsW, field + kFieldHdrW, ostep.sum, ostep.gmin);
+                    if constexpr (SLF) obs_frame_self<FLD>(T.m, scn, scn + kSceneBodyW, slot, (float)(t + 1) * p.dt, FLD ? scn + kSceneLdsW : nullptr,
+                                                           FLD ? field + kFieldHdrW : nullptr, slf, scol, nthr, ostep.sum, ostep.gmin);
+                    else if constexpr (FLD) obs_frame_field(T.m, scn, scn + kSceneBodyW, slot, (float)(t + 1) * p.dt, scn + kSceneLdsW, field + kFieldHdrW, ostep.sum, ostep.gmin);
                     else if constexpr (OBS) obs_frame(T.m, scn, scn + kSceneBodyW, slot, (float)(t + 1) * p.dt, ostep.sum, ostep.gmin);
                 };
                 obs_at(0);
@@ -646,6 +681,7 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                         obs_at(jn - HOT(j0) + 1);
                     }
                 }
+                if constexpr (SLF) self_pairs(slf, scol, nthr, ostep.ssum, ostep.sgmin);   // every member's centre is in the column
                 // the four weights as SGPR values: selecting between two kernel-argument
                 // addresses per lane would otherwise become two vector loads in the FK
                 const float wsp = uniform_f32(HOT(w_sp)), wso = uniform_f32(HOT(w_so)), wtp = uniform_f32(HOT(w_tp)),
@@ -664,6 +700,10 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                 oacc.sum += val ? obs_step_cost(scn, ostep.sum, ostep.gmin) : 0.0f;
                 oacc.gmin = fminf(oacc.gmin, val ? ostep.gmin : INFINITY);
             }
+            if constexpr (SLF) {
+                oacc.ssum += val ? self_step_cost(slf, ostep.ssum, ostep.sgmin) : 0.0f;
+                oacc.sgmin = fminf(oacc.sgmin, val ? ostep.sgmin : INFINITY);
+            }
             // extra joint-space terms (cost_manager.py:84,85,87; joint_space_cost.py)
             if (XC && (p.cost_terms & (MPPI_COST_CENTER | MPPI_COST_JOINT_TRACK | MPPI_COST_JOINT_LIMIT))) {
                 const int tc = (t < H) ? t : H - 1;
@@ -681,9 +721,15 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
                     out |= (qd < (double)vc.qlo[j]) | (qd > (double)vc.qhi[j]);
                 }
                 if (val) {
-                    if (p.cost_terms & MPPI_COST_CENTER) ecen += (p.w_cen * sc) * gts[c];
-                    if (p.cost_terms & MPPI_COST_JOINT_TRACK) ejt += (p.w_jt * sj) * gts[c];
-                    if ((p.cost_terms & MPPI_COST_JOINT_LIMIT) && out) elim += p.lim_pen * gts[c];
+                    if constexpr (SLF) {   // (the weights as late reads: late_arg)
+                        if (p.cost_terms & MPPI_COST_CENTER) ecen += (late_arg(pk.w_cen) * sc) * gts[c];
+                        if (p.cost_terms & MPPI_COST_JOINT_TRACK) ejt += (late_arg(pk.w_jt) * sj) * gts[c];
+                        if ((p.cost_terms & MPPI_COST_JOINT_LIMIT) && out) elim += late_arg(pk.lim_pen) * gts[c];
+                    } else {
+                        if (p.cost_terms & MPPI_COST_CENTER) ecen += (p.w_cen * sc) * gts[c];
+                        if (p.cost_terms & MPPI_COST_JOINT_TRACK) ejt += (p.w_jt * sj) * gts[c];
+                        if ((p.cost_terms & MPPI_COST_JOINT_LIMIT) && out) elim += p.lim_pen * gts[c];
+                    }
                 }
             }
         }
@@ -720,7 +766,10 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
 #pragma unroll
                 for (int s = 0; s < R; ++s) {
                     float add = read_lane_f32(ts, s * LSEG + LSEG - 1);
-                    if (i == 0) add = p.w_cov * add;
+                    if (i == 0) {
+                        if constexpr (SLF) add = late_arg(pk.w_cov) * add;
+                        else add = p.w_cov * add;
+                    }
                     S_seg[s] += add;
                 }
             }
@@ -731,6 +780,13 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             for (int s = 0; s < R; ++s) S_seg[s] += read_lane_f32(ts, s * LSEG + LSEG - 1);
             const float clr = seg_min_f32<LSEG>(oacc.gmin);
             if (kCosts && kval && t0 == 0) c_stage[it * cost_run_stride(nw * R) + wid * R + sub] = clr;
+        }
+        if constexpr (SLF) {   // S += the self-collision term (after the obstacle term); the sample's self clearance
+            const float ts = seg_scan_f32<LSEG>(oacc.ssum);
+#pragma unroll
+            for (int s = 0; s < R; ++s) S_seg[s] += read_lane_f32(ts, s * LSEG + LSEG - 1);
+            const float sclr = seg_min_f32<LSEG>(oacc.sgmin);
+            if (kCosts && kval && t0 == 0) sc_stage[it * cost_run_stride(nw * R) + wid * R + sub] = sclr;
         }
         float S_mine = S_seg[0];
 #pragma unroll
@@ -869,6 +925,13 @@ __device__ __forceinline__ void rollout_body(const uint32_t seed_lo, const uint3
             for (int i = lane; i < iters * q; i += 64) {
                 const int it = i / q, k0 = (blockIdx.x + it * HOT(nb)) * nS;
                 st_dev_run(Cv, (uint32_t)k0, c_stage + it * cost_run_stride(nS), min(nS, K - k0), i - it * q);
+            }
+        }
+        if constexpr (SLF) {   // and the self clearances: (V, K) in the pair region
+            float* const Cs = uniform_ptr(scene + (size_t)scene_int(slf + 5) + (size_t)v * K);
+            for (int i = lane; i < iters * q; i += 64) {
+                const int it = i / q, k0 = (blockIdx.x + it * HOT(nb)) * nS;
+                st_dev_run(Cs, (uint32_t)k0, sc_stage + it * cost_run_stride(nS), min(nS, K - k0), i - it * q);
             }
         }
     }
@@ -1024,4 +1087,34 @@ __global__ void __launch_bounds__(512, (roll_occ<NCH, F64, true, false>())) k_ro
                                                  const float* __restrict__ field, const DevParams pk) {
     rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, true, false, false, false, true, true, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg,
                                                                                                H_arg, geo_arg, u_prev, jtab, pk, ttab, scene, field);
+}
+
+// The self rollouts (rollout_body SLF): the scene kernel (k_rollout_sc) and the field kernel (k_rollout_sf)
+// with the self-collision pairs (mppi_self.h), under symbols of their own and with the arguments of the
+// kernel each extends -- the pair region lies in the scene buffer.  Blocks of at most 256 threads: the
+// centre column bounds a CU to about two waves per SIMD, which is what the registers are budgeted for (the
+// four-chunk kernels: one, so that they too run without scratch).
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE>
+__global__ void __launch_bounds__(256, (NCH >= 4 ? 1 : 2)) k_rollout_sc(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                 const uint32_t step_arg, const uint32_t k_off,
+                                                 const int32_t noise_arg, const int32_t H_arg,
+                                                 const int32_t geo_arg,
+                                                 const float* __restrict__ u_prev,
+                                                 const JointDev* __restrict__ jtab,
+                                                 const float* __restrict__ ttab, float* __restrict__ scene,
+                                                 const DevParams pk) {
+    rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, true, false, false, false, true, true, false, true>(
+        seed_lo, seed_hi, step_arg, k_off, noise_arg, H_arg, geo_arg, u_prev, jtab, pk, ttab, scene);
+}
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool VONE>
+__global__ void __launch_bounds__(256, (NCH >= 4 ? 1 : 2)) k_rollout_sf(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                 const uint32_t step_arg, const uint32_t k_off,
+                                                 const int32_t noise_arg, const int32_t H_arg,
+                                                 const int32_t geo_arg,
+                                                 const float* __restrict__ u_prev,
+                                                 const JointDev* __restrict__ jtab,
+                                                 const float* __restrict__ ttab, float* __restrict__ scene,
+                                                 const float* __restrict__ field, const DevParams pk) {
+    rollout_body<MODEL, NA, NCH, LSEG, F64, VONE, true, false, false, false, true, true, true, true>(
+        seed_lo, seed_hi, step_arg, k_off, noise_arg, H_arg, geo_arg, u_prev, jtab, pk, ttab, scene, field);
 }

@@ -172,3 +172,53 @@ template <int MODEL, int NA, bool F64>
 inline int dispatch_geom_df(const DevParams& p, const float* ttab, float* scene, const float* field, int threads, hipStream_t s) {
     return pick_geom(p, [&](auto nch, auto l) { return launch_rollout_df<MODEL, NA, nch(), l(), F64>(p, ttab, scene, field, threads, s); });
 }
+
+// The self launch (an engine of mppi_create_scene_self: the pair region behind its scene buffer, mppi_self.h):
+// k_rollout_sc, with a field k_rollout_sf, on every step of a batch (no quiet form).  LDS as the scene
+// kernel's plus a third run stage (the self clearances) and the centre column, 3 * members words per
+// thread (self_dyn_lds, the figure the layout chose the block by); blocks of 64..256 threads, and
+// nothing past the CU's LDS with the kernels' static part.
+static_assert(sizeof(JointDev) * kMaxJ + sizeof(VehicleConst) + 4 * (kSceneLdsW + kFieldHdrW + kSelfHdrW) + 64 <= (size_t)kSelfStaticLds,
+              "the self kernels' static LDS: joint table, vehicle constants, scene, field header, pair tables");
+template <int MODEL, int NA, int NCH, int LSEG, bool F64, bool FLD>
+inline int launch_rollout_self(const DevParams& p, const float* ttab, float* scene, const float* field, int members, int threads,
+                               hipStream_t s) {
+    size_t lds;
+    int32_t geo;
+    if (!ttab || !scene || (FLD && !field) || members < 0 || members > kSelfMaxMembers || threads < 64 || threads > 256 ||
+        !rollout_block<NA, NCH, LSEG>(p, threads, p.iters, false, lds, geo))
+        return -1;
+    lds += (size_t)(2 * p.iters * cost_run_stride((threads / 64) * (64 / LSEG)) + 3 * members * threads) * sizeof(float);
+    if ((int64_t)lds != self_dyn_lds(NA, p.H, threads, p.iters, members) || lds + kSelfStaticLds > (size_t)kSelfLdsMax) return -1;
+    return pick<true, false>(p.V == 1, [&](auto vone) {
+        if constexpr (FLD) {
+            const auto k = k_rollout_sf<MODEL, NA, NCH, LSEG, F64, vone()>;
+            static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+            static_assert(arg_offset<11>(decltype(k)()) == kRollFieldOff, "the field pointer follows the scene pointer");
+            return go(k, dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
+                      p.noise_mode, p.H, geo, p.u_prev, p.joints, ttab, scene, field, p);
+        } else {
+            const auto k = k_rollout_sc<MODEL, NA, NCH, LSEG, F64, vone()>;
+            static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+            return go(k, dim3(p.nb, p.V), dim3(threads), lds, s, p.seed_lo, p.seed_hi, p.step_ctr, (uint32_t)p.k_offset,
+                      p.noise_mode, p.H, geo, p.u_prev, p.joints, ttab, scene, p);
+        }
+    });
+}
+
+// every model, state width and geometry of the ladder for one of the two kernels (the self units)
+template <bool FLD>
+inline int dispatch_self(const DevParams& p, const float* ttab, float* scene, const float* field, int members, int threads, hipStream_t s) {
+    const auto geom = [&](auto model, auto na, auto f64) {
+        return pick_geom(p, [&](auto nch, auto l) {
+            return launch_rollout_self<model(), na(), nch(), l(), f64(), FLD>(p, ttab, scene, field, members, threads, s);
+        });
+    };
+    using std::integral_constant;
+    if (p.model == MPPI_MODEL_ARM && p.A == 7)
+        return p.state_f64 ? geom(integral_constant<int, MPPI_MODEL_ARM>{}, integral_constant<int, 7>{}, std::true_type{})
+                           : geom(integral_constant<int, MPPI_MODEL_ARM>{}, integral_constant<int, 7>{}, std::false_type{});
+    if (p.model == MPPI_MODEL_WHOLEBODY && p.A == 10)
+        return geom(integral_constant<int, MPPI_MODEL_WHOLEBODY>{}, integral_constant<int, 10>{}, std::false_type{});
+    return -1;
+}

@@ -69,7 +69,7 @@ static mppi_status rollout_impl(mppi_engine* e, const float* d_noise, bool quiet
     p.step_ctr = e->step_ctr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (e->timing) { e0 = pool_event(e); e1 = pool_event(e); HIP_TRY(hipEventRecord(e0, e->stream)); }
-    int rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field);
+    int rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members);
     if (rc != 0) return fail(MPPI_ERR_HIP, "rollout launch failed (%d: %s)", rc,
                              rc > 0 ? hipGetErrorString((hipError_t)rc) : "no kernel for this model/A/H");
     if (e->timing) {
@@ -333,7 +333,7 @@ mppi_status mppi_step(mppi_engine* e, const double* state, const float* h_noise,
     if (e->comm && (st = mppi_exchange(e)) != MPPI_OK) return st;
     if ((st = mppi_finalize(e)) != MPPI_OK) return st;
     if (!e->kern_call_hip || e->kern_call_peer != e->peer) {   // (mppi_kernel_info; described once)
-        e->kern_call = kernels_text(roll_symbol(rollout_params(e, StepPath::Hip, dn, false), e->threads, nullptr, e->d_ttab, e->d_scene, e->d_field),
+        e->kern_call = kernels_text(roll_symbol(rollout_params(e, StepPath::Hip, dn, false), e->threads, nullptr, e->d_ttab, e->d_scene, e->d_field, e->self_members),
                                     fin_symbol(finalize_params(e, FinKind::Final)), nullptr);
         e->kern_call_hip = true;
         e->kern_call_peer = e->peer;
@@ -498,7 +498,7 @@ mppi_status mppi_run_steps(mppi_engine* e, int32_t n) {
         if ((st = finalize_impl(e, i == n - 1, true)) != MPPI_OK) return st;
     }
     {   // (mppi_kernel_info) the launches above, described
-        const auto roll = [&](bool quiet) { return roll_symbol(rollout_params(e, StepPath::Hip, nullptr, quiet), e->threads, nullptr, e->d_ttab, e->d_scene, e->d_field); };
+        const auto roll = [&](bool quiet) { return roll_symbol(rollout_params(e, StepPath::Hip, nullptr, quiet), e->threads, nullptr, e->d_ttab, e->d_scene, e->d_field, e->self_members); };
         const auto fin = [&](bool quiet) { return fin_symbol(finalize_params(e, FinKind::Final, StepPath::Hip, quiet)); };
         const std::string q = fin(n > 1), rq = roll(n > 1);
         e->kern_batch = kernels_text(roll(false), fin(false), &q, &rq);

@@ -245,7 +245,12 @@ class ShardedEngine:
         scene = engine_kw.pop("scene", None)
         # an engine.DistanceField: every rank's engine holds the whole field
         field = engine_kw.pop("field", None)
-        make_engine = lambda c: Engine(c) if scene is None and field is None else Engine(c, scene=scene, field=field)  # noqa: E731
+        # an engine.SelfCollision: every rank's engine carries the same self-collision pairs
+        self_collision = engine_kw.pop("self_collision", None)
+        if self_collision is not None:
+            make_engine = lambda c: Engine(c, scene=scene, field=field, self_collision=self_collision)  # noqa: E731
+        else:
+            make_engine = lambda c: Engine(c) if scene is None and field is None else Engine(c, scene=scene, field=field)  # noqa: E731
         self.local = int(os.environ.get("LOCAL_RANK", device))
         self.local %= max(1, torch.cuda.device_count())   # more ranks than devices: wrap
         torch.cuda.set_device(self.local)
@@ -436,6 +441,10 @@ class ShardedEngine:
     def get_distance_field(self):
         """This rank's engine's field (Engine.get_distance_field): the same on every rank."""
         return self.engine.get_distance_field()
+
+    def get_self_clearances(self):
+        """This rank's samples' self clearances (Engine.get_self_clearances)."""
+        return self.engine.get_self_clearances()
 
     def get_clearances(self):
         """This rank's samples' clearances (Engine.get_clearances)."""

@@ -42,6 +42,7 @@ class Plan:
     S: np.ndarray         # (V,)
     ee_path: np.ndarray   # (V, H, 3): the EE (arm, whole-body) or vehicle (drone, quadrotor) positions
     clearance: Optional[np.ndarray] = None   # (V, H): min clearance to the obstacles at each step (scene engines)
+    self_clearance: Optional[np.ndarray] = None   # (V, H): min clearance over the self-collision pairs (self engines)
 
     def first_reach(self, tol: float = 0.005):
         """The first t with pos_err < tol (check_reach's measure), -1 if none: per vehicle."""
@@ -51,7 +52,8 @@ class Plan:
 
     def vehicle(self, v: int = 0) -> "Plan":
         return Plan(self.traj[v], self.cost_t[v], self.pos_err[v], self.S[v], self.ee_path[v],
-                    None if self.clearance is None else self.clearance[v])
+                    None if self.clearance is None else self.clearance[v],
+                    None if self.self_clearance is None else self.self_clearance[v])
 
 
 @dataclass(slots=True)
@@ -109,6 +111,48 @@ class Scene:
             c.body[i].frame, c.body[i].radius = f, r
             c.body[i].offset[:] = o
         c.w_obs, c.margin, c.penalty = self.w_obs, self.margin, self.penalty
+        return c
+
+
+class SelfCollision:
+    """The self-collision pairs of a self engine (``Engine(cfg, scene=..., self_collision=...)``,
+    mppi_create_scene_self): up to 32 unordered pairs ``(a, b)`` of the scene's body spheres, indexed as in
+    ``Scene.body``, and the term's own weights (project constants: w_self = 100, margin = 0.02 m,
+    penalty = 1e4).  Fixed at creation; hashable by value, so it can be part of an engine key."""
+
+    def __init__(self, pairs=(), w_self: float = 100.0, margin: float = 0.02, penalty: float = 1e4):
+        self.pairs = tuple((int(a), int(b)) for a, b in pairs)
+        self.w_self, self.margin, self.penalty = float(w_self), float(margin), float(penalty)
+
+    def _key(self):
+        return (self.pairs, self.w_self, self.margin, self.penalty)
+
+    def __eq__(self, other):
+        return isinstance(other, SelfCollision) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"SelfCollision(pairs={self.pairs}, w_self={self.w_self}, margin={self.margin}, penalty={self.penalty})"
+
+    @staticmethod
+    def default(cfg: capi.Config, scene: Optional["Scene"] = None) -> "SelfCollision":
+        """The project's placeholder pairs for a config and a scene (None: ``Scene.default(cfg)``): every
+        pair with at least three moving joints between its frames (mppi_self_collision_default)."""
+        c = capi.SelfCollision()
+        sc = None if scene is None else scene.to_c()
+        capi.lib().mppi_self_collision_default(C.byref(c), C.byref(cfg), None if sc is None else C.byref(sc))
+        return SelfCollision(tuple((c.pair[i][0], c.pair[i][1]) for i in range(c.n_pairs)), c.w_self, c.margin, c.penalty)
+
+    def to_c(self) -> capi.SelfCollision:
+        if len(self.pairs) > capi.MAX_SELF_PAIRS:
+            raise ValueError(f"{len(self.pairs)} self-collision pairs (max {capi.MAX_SELF_PAIRS})")
+        c = capi.SelfCollision()
+        c.n_pairs = len(self.pairs)
+        for i, (a, b) in enumerate(self.pairs):
+            c.pair[i][0], c.pair[i][1] = a, b
+        c.w_self, c.margin, c.penalty = self.w_self, self.margin, self.penalty
         return c
 
 
@@ -310,19 +354,27 @@ class Engine:
     """One MPPI engine on one GPU (V vehicles x K samples x H steps)."""
 
     def __init__(self, cfg: Optional[capi.Config] = None, scene: Optional[Scene] = None,
-                 field: Optional[DistanceField] = None, **kw):
+                 field: Optional[DistanceField] = None, self_collision: Optional[SelfCollision] = None, **kw):
         """``scene``: a ``Scene`` makes this an obstacle-avoiding engine (``set_obstacles``,
         ``get_clearances``, ``Plan.clearance``); None: the engine as before.  ``field``: a
         ``DistanceField`` adds a voxel distance field as one more obstacle (``set_distance_field``,
-        ``clear_distance_field``); without ``scene`` it uses ``Scene.default(cfg)``."""
+        ``clear_distance_field``); without ``scene`` it uses ``Scene.default(cfg)``.
+        ``self_collision``: a ``SelfCollision`` adds the self-collision pairs of the scene's spheres
+        (``get_self_clearances``, ``Plan.self_clearance``; arm and whole-body), likewise with the default scene."""
         self._L = capi.lib()
         self.cfg = cfg if cfg is not None else make_config(**kw)
-        if field is not None and scene is None:
+        if (field is not None or self_collision is not None) and scene is None:
             scene = Scene.default(self.cfg)
         self.scene = scene
         self.field = field
+        self.self_collision = self_collision
         h = C.c_void_p()
-        if field is not None:
+        if self_collision is not None:
+            sc, sf = scene.to_c(), self_collision.to_c()
+            fd = None if field is None else field.to_c()
+            capi.check(self._L.mppi_create_scene_self(C.byref(self.cfg), C.byref(sc), None if fd is None else C.byref(fd),
+                                                      C.byref(sf), C.byref(h)), "mppi_create_scene_self")
+        elif field is not None:
             sc, fd = scene.to_c(), field.to_c()
             capi.check(self._L.mppi_create_scene_field(C.byref(self.cfg), C.byref(sc), C.byref(fd), C.byref(h)),
                        "mppi_create_scene_field")
@@ -636,6 +688,15 @@ class Engine:
         capi.check(self._L.mppi_get_clearances(self._h, capi.fptr(c)), "get_clearances")
         return c
 
+    def get_self_clearances(self) -> np.ndarray:
+        """(V, K): every sample's min clearance over the self-collision pairs and the horizon (+inf with
+        an empty pair list); valid as ``get_costs`` is.  Self engines only."""
+        if self.self_collision is None:
+            raise RuntimeError("engine created without self-collision pairs (Engine(cfg, self_collision=SelfCollision(...)))")
+        c = np.empty((self.V, self.K), np.float32)
+        capi.check(self._L.mppi_get_self_clearances(self._h, capi.fptr(c)), "get_self_clearances")
+        return c
+
     def get_weights(self) -> np.ndarray:
         w = np.empty((self.V, self.K), np.float32)
         capi.check(self._L.mppi_get_weights(self._h, capi.fptr(w)), "get_weights")
@@ -670,7 +731,11 @@ class Engine:
         if self.scene is not None:   # (k_plan wrote them with the plan above; a second, small launch and copy)
             clr = np.empty((self.V, self.H), np.float32)
             capi.check(self._L.mppi_get_plan_clearance(self._h, capi.fptr(clr)), "get_plan_clearance")
-        return Plan(traj, cost_t, pos_err, S, self._ee_path(traj), clr)
+        sclr = None
+        if self.self_collision is not None:
+            sclr = np.empty((self.V, self.H), np.float32)
+            capi.check(self._L.mppi_get_plan_self_clearance(self._h, capi.fptr(sclr)), "get_plan_self_clearance")
+        return Plan(traj, cost_t, pos_err, S, self._ee_path(traj), clr, sclr)
 
     def _ee_path(self, traj: np.ndarray) -> np.ndarray:
         """(..., H, 3) positions out of (..., H, C) rows: the EE matrix's translation column (arm,

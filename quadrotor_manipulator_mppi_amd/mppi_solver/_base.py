@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import _capi as capi
-from ..engine import Engine, Scene, cost_term_bits, make_config
+from ..engine import Engine, Scene, SelfCollision, cost_term_bits, make_config
 
 
 class OutputRing:
@@ -114,6 +114,8 @@ class SolverBase:
         start (and the prewarm window, mppi_set_prewarm: for a loop ticking with idle gaps)."""
         e = self._engine
         full_key = (key, self._scene, self._field)   # (the scene and the field's grid are fixed per engine)
+        if self._self_collision is not None:
+            full_key += (self._self_collision,)       # (and the pair list)
         if e is not None and full_key == self._engine_key:
             return e
         u = self._u_prev_host if e is None else e.get_u_prev()[0]
@@ -121,7 +123,13 @@ class SolverBase:
             e.close()
         cfg = self._config(key)
         scene = Scene.default(cfg) if self._scene is True else self._scene
-        e = self._engine = Engine(cfg) if scene is None and self._field is None else Engine(cfg, scene=scene, field=self._field)
+        if self._self_collision is not None:   # True: the placeholder pairs of the scene (engine.SelfCollision.default)
+            if scene is None:
+                scene = Scene.default(cfg)
+            pairs = SelfCollision.default(cfg, scene) if self._self_collision is True else self._self_collision
+            e = self._engine = Engine(cfg, scene=scene, field=self._field, self_collision=pairs)
+        else:
+            e = self._engine = Engine(cfg) if scene is None and self._field is None else Engine(cfg, scene=scene, field=self._field)
         self._engine_key = full_key
         e.set_u_prev(u)
         if self._prewarm_us:
@@ -216,6 +224,19 @@ class SolverBase:
         if self._scene is None:
             raise RuntimeError("clear_obstacles needs scene=... at construction")
         self._obstacles = None
+
+    # ``self_collision=`` (a constructor keyword of the arm class): an ``engine.SelfCollision``, or True for
+    # the placeholder pairs, makes the engine a self engine (with ``scene``, or the placeholder spheres).
+    _self_collision = None
+
+    def get_self_clearances(self) -> np.ndarray:
+        """(K,): the last control call's samples' min clearances over the self-collision pairs
+        (``Engine.get_self_clearances``)."""
+        if self._self_collision is None:
+            raise RuntimeError("get_self_clearances needs self_collision=... at construction")
+        if self._engine is None:
+            raise RuntimeError("get_self_clearances: no control call yet")
+        return self._engine.get_self_clearances()[0]
 
     # ``field=`` (a constructor keyword of the arm and drone classes): an ``engine.DistanceField`` makes
     # the engine a field engine (with ``scene``, or the placeholder spheres); its data, when it has some,

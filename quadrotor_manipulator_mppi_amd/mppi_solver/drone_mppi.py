@@ -23,12 +23,15 @@ from ._base import VehicleSolver
 class MPPI(VehicleSolver):
     def __init__(self, n_samples: int = 1000, n_timestep: int = 32, device: Optional[int] = None,
                  noise: str = "philox", seed: int = 0x5EED, verbose: bool = False, prewarm_us: int = 0,
-                 track_target: bool = False, scene=None, field=None):
+                 track_target: bool = False, scene=None, field=None, self_collision=None):
         """``track_target``: a target that may move along the horizon (``set_target_trajectory`` with
         (H, 3) positions, ``clear_target_trajectory``); off, the class is as before.  ``scene``: an
         ``engine.Scene`` (True: the placeholder 0.30 m sphere) for obstacle avoidance
         (``set_obstacles``, ``clear_obstacles``).  ``field``: an ``engine.DistanceField``, a voxel
         distance field as one more obstacle (``set_distance_field``, ``clear_distance_field``)."""
+        if self_collision is not None:
+            raise NotImplementedError("self-collision pairs are not available for the drone model (no chain: every pair "
+                                      "of its spheres is rigid); use the arm class")
         super().__init__(3, torch.eye(3) * 30.0, n_samples, n_timestep, device, noise, seed, verbose, prewarm_us,
                          track_target=track_target, scene=scene, field=field)
         self.param_gamma = self.param_lambda * (1.0 - 0.9)

@@ -56,7 +56,7 @@ class MPPI(SolverBase):
                  noise: str = "philox", seed: int = 0x5EED, urdf_path: Optional[str] = None,
                  root_link: str = "base", end_link: str = "j2s7s300_link_7", verbose: bool = True,
                  cost_terms=(), cost_weights=None, prewarm_us: int = 0, track_target: bool = False,
-                 scene=None, field=None):
+                 scene=None, field=None, self_collision=None):
         """``track_target``: a pose target that may move along the horizon
         (``set_target_trajectory`` with (H, 7) rows xyz + xyzw, ``clear_target_trajectory``); while
         no table is set, ``target_pose`` is the target of every step as before.  ``cost_terms``: CostManager terms to switch on beyond the pose cost the
@@ -73,6 +73,9 @@ class MPPI(SolverBase):
         # an engine.DistanceField: a voxel distance field as one more obstacle (set_distance_field /
         # clear_distance_field); without scene= the placeholder spheres
         self._init_field(field)
+        # an engine.SelfCollision (True: the placeholder pairs, engine.SelfCollision.default): self-collision
+        # avoidance between the scene's body spheres (get_self_clearances); without scene= the placeholder spheres
+        self._self_collision = self_collision
         # mppi.py:37-42
         self.n_manipulator_dof = 7
         self.n_mobile_dof = 0

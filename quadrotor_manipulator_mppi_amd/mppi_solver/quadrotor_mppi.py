@@ -26,7 +26,10 @@ class MPPI(VehicleSolver):
     def __init__(self, n_samples: int = 1000, n_timestep: int = 32, device: Optional[int] = None,
                  noise: str = "philox", seed: int = 0x5EED, mass: float = 14.7,
                  inertia=(1.57, 3.93, 2.59), kd: float = 0.0, gravity: float = 9.81, verbose: bool = False, prewarm_us: int = 0,
-                 track_target: bool = False, scene=None, field=None):
+                 track_target: bool = False, scene=None, field=None, self_collision=None):
+        if self_collision is not None:
+            raise NotImplementedError("self-collision pairs are not available for the 6-DoF quadrotor model "
+                                      "(no scene form of its rollout kernel); use the arm class")
         if field is not None:
             raise NotImplementedError("distance fields are not available for the 6-DoF quadrotor model "
                                       "(no scene form of its rollout kernel); use the drone or arm classes")

@@ -7,6 +7,8 @@ frame origin of every actuated chain joint, one on the base frame (-1) of a flyi
 JOINT_SPHERE_RADIUS = 0.05     # m, every actuated joint's frame origin (ARM, WHOLEBODY)
 VEHICLE_SPHERE_RADIUS = 0.30   # m, frame -1 (WHOLEBODY, DRONE)
 W_OBS, MARGIN, PENALTY = 100.0, 0.05, 1e4
+# the self-collision term's own weights (``mppi_self_collision_default``): self margins are tighter
+W_SELF, MARGIN_SELF, PENALTY_SELF = 100.0, 0.02, 1e4
 
 
 def default_body(model: str, chain) -> tuple:
