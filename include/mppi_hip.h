@@ -65,9 +65,21 @@ typedef enum {
     MPPI_MODEL_DRONE = 0,     /* xyz double integrator, squared position cost      (A=3)  drone_mppi.py   */
     MPPI_MODEL_ARM = 1,       /* joint double integrator + FK chain + pose cost    (A=nq) mppi.py         */
     MPPI_MODEL_WHOLEBODY = 2, /* drone xyz + arm joints, mobile-base FK, pose cost (A=3+nq) SURVEY A16    */
-    MPPI_MODEL_QUADROTOR = 3  /* 6-DoF rigid-body quadrotor: thrust + body torques, Euler-angle attitude,
+    MPPI_MODEL_QUADROTOR = 3, /* 6-DoF rigid-body quadrotor: thrust + body torques, Euler-angle attitude,
                                * squared position cost (A=4, H <= 64).  The model the reference ships
                                * commented out (drone_mppi.py:57-83, drone.py:114-154) */
+    MPPI_MODEL_AERIAL = 4     /* aerial manipulator: the QUADROTOR's rigid body carrying the Kinova arm
+                               * (A = 4 + nq = 11, H <= 64).  Action (thrust, tau_xyz, qdd_0..6); the base
+                               * steps by the QUADROTOR recurrence on dims 0..3, the joints by the ARM's
+                               * double integrator on dims 4..10; the pose cost is taken at
+                               *   EE(k,t) = [Rz(yaw) Ry(pitch) Rx(roll) | p](k,t) M_fixed chain(q(k,t))
+                               * with the attitude and position of that row of the rollout.  The coupling is
+                               * kinematic only: quad_mass and quad_inertia are the loaded vehicle's as the
+                               * user sets them, and arm motion does not react on the base.  The chain is the
+                               * Kinova table of the ARM kernels (leading fixed joints, then seven revolute-z
+                               * joints).  Not available on this model (MPPI_ERR_INVALID_ARG, AERIAL named
+                               * in mppi_last_error): scenes, fields and self-collision, every cost_terms
+                               * bit (target tracking included), shard_count > 1 */
 } mppi_model;
 
 typedef enum {
@@ -98,7 +110,7 @@ typedef struct {
     int32_t n_vehicles;       /* V independent controllers batched in one launch (config C5)    */
     int32_t n_samples;        /* K samples owned by THIS engine (one shard)                      */
     int32_t n_horizon;        /* H                                                              */
-    int32_t n_action;         /* A (3 drone, nq arm, 3+nq whole-body)                           */
+    int32_t n_action;         /* A (3 drone, nq arm, 3+nq whole-body, 4 quadrotor, 4+nq aerial) */
     double dt;                /* 0.01 (mppi.py:42, drone_mppi.py:18); a Python float there       */
     double lambda_;           /* 0.1  (mppi.py:75, drone_mppi.py:33)                             */
     float sigma[MPPI_MAX_ACTION * MPPI_MAX_ACTION]; /* Sigma (A x A, row-major), eps = z^T Sigma */
@@ -161,7 +173,7 @@ typedef enum {
     MPPI_COST_ACTION = 8,
     MPPI_COST_JOINT_LIMIT = 16,
     /* Not a CostManager term: the pose target moves along the horizon (mppi_set_target_trajectory).
-     * Accepted on every model; bits 1..16 stay ARM / WHOLEBODY only. */
+     * Accepted on every model but AERIAL (which takes no cost_terms bit); bits 1..16 stay ARM / WHOLEBODY only. */
     MPPI_COST_TARGET_TRACK = 32
 } mppi_cost_term;
 
@@ -235,6 +247,7 @@ mppi_status mppi_get_u_prev(mppi_engine* e, float* u_prev);
  *   WHOLEBODY: base xyz(3) quat xyzw(4) q(nq) base vel(3) qd(nq)
  *   QUADROTOR: xyz(3) rpy(3) (roll, pitch, yaw; R = Rz(yaw) Ry(pitch) Rx(roll), drone.py:126-154)
  *              v world(3) omega body(3)
+ *   AERIAL:    xyz(3) rpy(3) q(nq) | v world(3) omega body(3) qd(nq)   (12 + 2 nq; float32 tensors)
  * Async host->device (pinned staging) on the engine stream. */
 mppi_status mppi_set_state(mppi_engine* e, const double* state);
 
@@ -351,6 +364,8 @@ mppi_status mppi_peer_reset(mppi_engine* e, uint32_t step, uint32_t epoch);
 /* Synchronise and copy the step's outputs: out (V, output_dim) doubles
  *   DRONE: x_des(3) v_des(3);  ARM: qdes(nq) vdes(nq);  WHOLEBODY: x(3) v(3) qdes(nq) vdes(nq)
  *   QUADROTOR: x_des = (xyz, rpy)(6), v_des = (v, omega)(6): the model's first step under u0
+ *   AERIAL:    x_des(6) v_des(6) as QUADROTOR (the base's first step under u0[0..3]), then qdes(nq)
+ *              vdes(nq) as ARM (mppi.py:157-158, qdes from the old u_prev[0])
  * u0 (V, A) floats and stats (V) may be NULL. */
 mppi_status mppi_read_outputs(mppi_engine* e, double* out, float* u0, mppi_stats* stats);
 
@@ -423,6 +438,7 @@ mppi_status mppi_get_prewarm(mppi_engine* e, int32_t* window_us, int64_t* touche
  *   noise    eps (V,K,H,A)                   sampling()            [store_noise]
  *   traj     (V,K,H,C) C = traj_channels    DRONE p(3) / ARM q(nq)+EE(16) / WB p(3)+q(nq)+EE(16)
  *                                            QUADROTOR xyz(3)+rpy(3) (drone_mppi.py:62 trajectory)
+ *                                            AERIAL xyz(3)+rpy(3)+q(nq)+EE(16)
  *            EE as the 4x4 row-major matrix of urdf_fk.py:108       [store_trajectory]
  *   wnoise   w_eps before / after SavGol (V,H,A), recomputed from the records the last
  *            step combined (a k_finalize launch in READBACK mode): the step itself stores
@@ -437,7 +453,7 @@ mppi_status mppi_get_weighted_noise(mppi_engine* e, float* raw, float* smoothed)
  * state (synchronous; any engine: single, fleet, sharded, peer -- u_prev is the same on every rank).
  *   traj    (V,H,C)  C = mppi_traj_channels, the per-(t) layout of mppi_get_trajectory
  *   cost_t  (V,H)    the step's share of S: every enabled term, stage weights for t < H-1, terminal at H-1
- *   pos_err (V,H)    L1 distance of the EE (ARM, WHOLEBODY) or the vehicle (DRONE, QUADROTOR) position to
+ *   pos_err (V,H)    L1 distance of the EE (ARM, WHOLEBODY, AERIAL) or the vehicle (DRONE, QUADROTOR) position to
  *                    the target: check_reach's measure (utils/pose.py:121-123) along the plan
  *   S       (V)      the cost the rollout kernel gives this sample; sum_t cost_t
  * Any pointer may be NULL.  The state and targets are the ones last set (mppi_set_state / mppi_step,
@@ -448,7 +464,7 @@ mppi_status mppi_get_weighted_noise(mppi_engine* e, float* raw, float* smoothed)
 mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos_err, float* S);
 
 /* ---- Obstacle avoidance: sphere scenes in the rollout cost (the project's own term; the reference
- * has no counterpart).  ARM, WHOLEBODY and DRONE; a QUADROTOR config with a scene is
+ * has no counterpart).  ARM, WHOLEBODY and DRONE; a QUADROTOR or AERIAL config with a scene is
  * MPPI_ERR_INVALID_ARG.
  *
  * Body spheres are the robot's geometry, engine-wide and fixed at creation (mppi_scene): sphere b
@@ -475,7 +491,7 @@ typedef struct { int32_t n_body; mppi_body_sphere body[MPPI_MAX_BODY_SPHERES];
                  float w_obs, margin, penalty; } mppi_scene;
 /* The project's default spheres and weights for the config's model and chain. */
 void mppi_scene_default(mppi_scene* scene, const mppi_config* cfg);
-/* mppi_create with a scene (NULL scene: mppi_create).  MPPI_ERR_INVALID_ARG: QUADROTOR, n_body
+/* mppi_create with a scene (NULL scene: mppi_create).  MPPI_ERR_INVALID_ARG: QUADROTOR, AERIAL, n_body
  * outside 0..16, a frame outside [-1, n_joints) (DRONE: other than -1), a non-finite value, a
  * radius <= 0, a negative weight.  Runs the scene kernels (k_rollout_ob; no quiet form). */
 mppi_status mppi_create_scene(const mppi_config* cfg, const mppi_scene* scene, mppi_engine** out);
@@ -494,7 +510,7 @@ mppi_status mppi_get_plan_clearance(mppi_engine* e, float* clr_vh);
 
 /* ---- Distance-field environments: a voxel signed distance field as one more obstacle of a scene
  * engine (walls, shelves, floors: what a planning stack hands over as an ESDF).  ARM, WHOLEBODY and
- * DRONE; QUADROTOR is MPPI_ERR_INVALID_ARG, as for a scene.
+ * DRONE; QUADROTOR and AERIAL are MPPI_ERR_INVALID_ARG, as for a scene.
  *
  * The field is engine-wide: one world, shared by all V vehicles.  It is a nodal grid d[iz][iy][ix]
  * of fp32 signed distances in metres (negative inside), C order (nz, ny, nx); node (ix, iy, iz)
@@ -563,8 +579,8 @@ mppi_status mppi_get_distance_field(mppi_engine* e, int32_t* is_set, float* orig
 
 /* ---- Self-collision avoidance: pairs of body spheres in the scene rollout cost (the project's own
  * term; what a MoveIt-style stack keeps as the allowed-collision matrix, turned round: the pairs that
- * are NOT allowed to touch).  ARM and WHOLEBODY; DRONE (no chain: every pair is rigid) and QUADROTOR
- * are MPPI_ERR_INVALID_ARG.
+ * are NOT allowed to touch).  ARM and WHOLEBODY; DRONE (no chain: every pair is rigid), QUADROTOR and
+ * AERIAL are MPPI_ERR_INVALID_ARG.
  *
  * A pair list is up to MPPI_MAX_SELF_PAIRS unordered pairs (a, b) of the scene's body spheres, indexed
  * as in mppi_scene.body; engine-wide and fixed at creation.  With c_b(k,t) the sphere's world centre
@@ -676,7 +692,7 @@ mppi_status mppi_occupancy_field(const mppi_field_desc* desc, const uint8_t* occ
  * W = mppi_philox_words(A), exactly as the rollout kernel draws them for (seed, step,
  * vehicle, global k0..k0+K): A/8 Philox4x32-10 calls, then the A mod 8 remainder from one
  * Philox2x32-10 call (remainder <= 4) or one more Philox4x32-10 call.
- * A in {2, 3, 4, 7, 8, 10}. */
+ * A in {2, 3, 4, 7, 8, 10, 11}. */
 int32_t mppi_philox_words(int32_t A);
 mppi_status mppi_philox_normals(uint64_t seed, uint32_t step, int32_t vehicle, int64_t k0, int32_t K,
                                 int32_t H, int32_t A, int32_t device, float* z, uint32_t* raw);

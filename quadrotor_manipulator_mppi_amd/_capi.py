@@ -16,7 +16,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPPI_HIP_LIB", os.path.join(PKG, "lib", "libmppi_hip.so"))
 
 MAX_ACTION, MAX_JOINTS, MAX_HORIZON, MAX_SAVGOL = 16, 16, 256, 31
-MODEL_DRONE, MODEL_ARM, MODEL_WHOLEBODY, MODEL_QUADROTOR = 0, 1, 2, 3
+MODEL_DRONE, MODEL_ARM, MODEL_WHOLEBODY, MODEL_QUADROTOR, MODEL_AERIAL = 0, 1, 2, 3, 4
 NOISE_PHILOX, NOISE_INJECTED = 0, 1
 JOINT_FIXED, JOINT_REVOLUTE, JOINT_PRISMATIC, JOINT_FLOATING = 0, 1, 2, 3
 OK, ERR_INVALID_ARG, ERR_HIP, ERR_NONFINITE, ERR_STATE, ERR_COMM, ERR_PEER_TIMEOUT = 0, -1, -2, -3, -4, -5, -6

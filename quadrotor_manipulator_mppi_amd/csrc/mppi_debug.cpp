@@ -379,6 +379,37 @@ static int32_t step_launches(const mppi_config* cfg, const int32_t* sw, char* bu
 int32_t mppi_debug_step_launches(const mppi_config* cfg, const int32_t* sw, char* buf, int32_t len) {
     return step_launches(cfg, sw, buf, len, nullptr);
 }
+// Diagnostic (no GPU): the outputs the host forms for a QUADROTOR or AERIAL configuration -- the base's first step
+// under u0 (quad_outputs; AERIAL: aerial_outputs picks the base rows out of its state) -- into out12, and (vc non-null)
+// the vehicle constants build_vehicle_consts makes of `state` for vehicle 0: pos0f then vel0f (2 x 16 floats), then base
+// (12).  The engine is built on the host from layout_of, as in step_launches.  tests/test_capi_aerial_cpu.py.
+int32_t mppi_debug_base_outputs(const mppi_config* cfg, const double* state, const float* u0, double* out12, float* vc44) {
+    if (!cfg || !state || !u0 || !out12) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_base_outputs: bad arguments");
+    mppi_status st = validate(*cfg);
+    if (st != MPPI_OK) return st;
+    if (cfg->model != MPPI_MODEL_QUADROTOR && cfg->model != MPPI_MODEL_AERIAL)
+        return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_base_outputs: the QUADROTOR and AERIAL models form outputs on the host");
+    const auto eng = std::make_unique<mppi_engine>();
+    mppi_engine* e = eng.get();
+    if ((st = layout_of(*cfg, *e)) != MPPI_OK) return st;
+    std::vector<VehicleConst> vc((size_t)e->V);
+    e->h_vc = vc.data();
+    e->tpos.assign((size_t)3 * e->V, 0.0f);
+    e->tquat.assign((size_t)4 * e->V, 0.0f);
+    e->state.assign((size_t)e->state_dim * e->V, 0.0);
+    std::memcpy(e->state.data(), state, sizeof(double) * (size_t)e->state_dim);
+    for (int v = 0; v < e->V; ++v) e->tquat[4 * v + 3] = 1.0f;
+    build_vehicle_consts(e);
+    if (cfg->model == MPPI_MODEL_AERIAL) aerial_outputs(e, e->state.data(), u0, out12);
+    else quad_outputs(e, e->state.data(), u0, out12);
+    if (vc44) {
+        std::memcpy(vc44, vc[0].pos0f, sizeof(float) * 16);
+        std::memcpy(vc44 + 16, vc[0].vel0f, sizeof(float) * 16);
+        std::memcpy(vc44 + 32, vc[0].base, sizeof(float) * 12);
+    }
+    e->h_vc = nullptr;
+    return MPPI_OK;
+}
 // Likewise for an engine of mppi_create_scene(cfg, scene) (a null scene: mppi_debug_step_launches).
 // tests/test_capi_obstacles_cpu.py.
 int32_t mppi_debug_scene_step_launches(const mppi_config* cfg, const mppi_scene* scene, const int32_t* sw, char* buf,

@@ -36,9 +36,10 @@ struct JointDev {
 struct VehicleConst {
     double pos0[kMaxA];   // initial positions per action dim (drone xyz / joints / both)
     double vel0[kMaxA];   // initial velocities
-    float pos0f[kMaxA];   // fp32 copies (f32 state mode)
-    float vel0f[kMaxA];
-    float base[12];       // ARM: fp32 base transform (urdf_fk.py:30-55) times the leading fixed
+    float pos0f[kMaxA];   // fp32 copies (f32 state mode).  AERIAL: xyz / v in 0..2, q / qd in 4..10 (the joints'
+    float vel0f[kMaxA];   //   action dims, as the finalize indexes them), rpy / omega in 11..13
+    float base[12];       // AERIAL: the leading fixed joints alone (M_fixed)
+                          // ARM: fp32 base transform (urdf_fk.py:30-55) times the leading fixed
                           //      joints of the chain, rows 0..2
                           // WB : R(rpy(quat)) (transformation_matrix.py:148-187) times the leading
                           //      fixed joints; column 3 = R * (their translation), p(k,t) is added
@@ -136,6 +137,17 @@ struct DevParams {
 // handed-over vehicle constants are never read (a batch's step before its last): the records only.
 constexpr int32_t kRollKernGeneric = 1, kRollKernQuiet = 2;
 constexpr int kStamps = 16;
+// k_rollout_aerial (mppi_rollout_aerial.hip; MPPI_MODEL_AERIAL): a block owns 16 rollouts per dynamics wave
+// (nwd = DevParams::iters: 1 or 4).  Its dynamic LDS, in floats: the noise tile [H+1][16 nwd 11 + 1] (odd
+// pitch), u_prev [H+1][11], and the pose tile [16 nwd][H+1][7] the dynamics waves leave (p, rpy) in for the
+// lanes that cost the end effector (a spare row H each: the operands are read a step ahead).  The layout
+// picks the four-wave block only where this stays within kAerialLdsMax of the CU's 160 KiB.
+constexpr int kAerialA = 11, kAerialNq = 7, kAerialR = 16, kAerialPoseW = 7;
+constexpr inline int64_t aerial_lds_floats(int H, int nwd) {
+    return (int64_t)(H + 1) * (kAerialR * nwd * kAerialA + 1) + (int64_t)(H + 1) * kAerialA +
+           (int64_t)kAerialR * nwd * (H + 1) * kAerialPoseW;
+}
+constexpr int64_t kAerialLdsMax = 128 * 1024;
 // noise-mode flag of native dispatch (mppi_aql.cpp): the rollout's step-counter argument is
 // relative to the dispatch id -- step = arg + (dispatch id >> 1) -- so one argument block,
 // written once, serves every (rollout, finalize) pair the engine's queue runs
@@ -327,6 +339,7 @@ int mppi_launch_rollout_arm64_h32(const mppi::DevParams* p, int block_threads, v
 int mppi_launch_rollout_arm32(const mppi::DevParams* p, int block_threads, void* stream);
 int mppi_launch_rollout_wb(const mppi::DevParams* p, int block_threads, void* stream);
 int mppi_launch_rollout_quad(const mppi::DevParams* p, int block_threads, void* stream);
+int mppi_launch_rollout_aerial(const mppi::DevParams* p, int block_threads, void* stream);
 // the tracking rollouts (cost_terms & MPPI_COST_TARGET_TRACK): ttab = the target table (V, H, 12)
 int mppi_launch_rollout_track(const mppi::DevParams* p, const float* ttab, int block_threads, void* stream);
 int mppi_launch_rollout_arm64_tt(const mppi::DevParams* p, const float* ttab, int block_threads, void* stream);

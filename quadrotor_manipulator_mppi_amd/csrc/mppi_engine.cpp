@@ -75,14 +75,21 @@ mppi_status download(mppi_engine* e, void* dst, const void* src, size_t bytes) {
     return MPPI_OK;
 }
 
+// the models whose planes end in the EE's twelve stored entries, and the state channels ahead of them (ARM,
+// WHOLEBODY: the action dims; AERIAL: xyz, rpy, q), else all of the channels
+static bool model_has_ee(const mppi_engine* e) {
+    return e->cfg.model == MPPI_MODEL_ARM || e->cfg.model == MPPI_MODEL_WHOLEBODY || e->cfg.model == MPPI_MODEL_AERIAL;
+}
+static int state_channels(const mppi_engine* e) { return model_has_ee(e) ? e->C - 12 : e->C; }
+
 // n steps out of SoA planes (channel stride `plane` floats; step i at offset at(i) of each) into
-// rows of mppi_traj_channels floats: the state channels, then (ARM, WHOLEBODY) the EE's twelve
+// rows of mppi_traj_channels floats: the state channels, then (ARM, WHOLEBODY, AERIAL) the EE's twelve
 // stored entries with the row 0 0 0 1 appended
 template <class At>
 static void planes_to_rows(const mppi_engine* e, const float* planes, size_t plane, size_t n, At at, float* rows) {
     const int Cr = mppi_traj_channels(&e->cfg);
-    const bool has_ee = e->cfg.model == MPPI_MODEL_ARM || e->cfg.model == MPPI_MODEL_WHOLEBODY;
-    const int nstate = has_ee ? e->A : e->C;
+    const bool has_ee = model_has_ee(e);
+    const int nstate = state_channels(e);
     for (size_t i = 0; i < n; ++i) {
         float* dst = rows + i * Cr;
         const float* src = planes + at(i);
@@ -130,6 +137,18 @@ mppi_status build_vehicle_consts(mppi_engine* e) {
                 vc.pos0f[a] = (float)s[a]; vc.vel0f[a] = (float)s[6 + a];
                 vc.pos0[a] = vc.pos0f[a]; vc.vel0[a] = vc.vel0f[a];
             }
+        } else if (c.model == MPPI_MODEL_AERIAL) {   // xyz rpy q | v omega qd (float32 tensors)
+            // indexed so that the finalize's joint branch reads pos0f[a] / vel0f[a] of action dim a = 4 + j
+            const int nq = e->nq;
+            for (int a = 0; a < 3; ++a) {
+                vc.pos0f[a] = (float)s[a]; vc.vel0f[a] = (float)s[6 + nq + a];
+                vc.pos0f[11 + a] = (float)s[3 + a]; vc.vel0f[11 + a] = (float)s[9 + nq + a];
+            }
+            for (int j = 0; j < nq; ++j) {
+                vc.pos0f[4 + j] = (float)s[6 + j]; vc.vel0f[4 + j] = (float)s[12 + nq + j];
+            }
+            for (int a = 0; a < kMaxA; ++a) { vc.pos0[a] = vc.pos0f[a]; vc.vel0[a] = vc.vel0f[a]; }
+            std::memcpy(vc.base, e->fixedM, sizeof(vc.base));   // M_fixed alone: [R(rpy) | p](k,t) is the rollout's
         } else if (c.model == MPPI_MODEL_ARM) {
             float T16[16];
             base_from_xyzquat(s, c.state_f64 != 0, T16);
@@ -185,6 +204,15 @@ void quad_outputs(const mppi_engine* e, const double* s, const float* u0, double
     out[9] = wx + dt * (p.q_iinv[0] * u0[1]);
     out[10] = wy + dt * (p.q_iinv[1] * u0[2]);
     out[11] = wz + dt * (p.q_iinv[2] * u0[3]);
+}
+
+// AERIAL outputs: the base's twelve as the QUADROTOR's (its state rows xyz rpy | v omega picked out of the
+// aerial state); the joints' qdes, vdes behind them are the finalize's.
+void aerial_outputs(const mppi_engine* e, const double* s, const float* u0, double* out) {
+    const int nq = e->nq;
+    double sq[12];
+    for (int i = 0; i < 6; ++i) { sq[i] = s[i]; sq[6 + i] = s[6 + nq + i]; }
+    quad_outputs(e, sq, u0, out);
 }
 
 mppi_status target_rows_begin(mppi_engine* e) {
@@ -473,7 +501,8 @@ static mppi_status create_engine(const mppi_config* cfg, const mppi_scene* scene
     e->out_dbg = getenv("MPPI_DEBUG_OUT") ? atoi(getenv("MPPI_DEBUG_OUT")) : 0;
     if (const char* d = getenv("MPPI_DISPATCH")) e->aql_mode = !strcmp(d, "hip") ? 0 : !strcmp(d, "aql") ? 1 : 2;
     // experiment (MPPI_OVERLAP=1): overlapped native batches; k_rollout only (k_rollout_quad does not wait)
-    e->overlap = getenv("MPPI_OVERLAP") && atoi(getenv("MPPI_OVERLAP")) != 0 && c.model != MPPI_MODEL_QUADROTOR;
+    e->overlap = getenv("MPPI_OVERLAP") && atoi(getenv("MPPI_OVERLAP")) != 0 && c.model != MPPI_MODEL_QUADROTOR &&
+                 c.model != MPPI_MODEL_AERIAL;
 
     if ((st = allocate(e)) == MPPI_OK) {
         bind(e);
@@ -981,14 +1010,14 @@ mppi_status mppi_get_elites(mppi_engine* e, int32_t n, int32_t* idx, float* S, f
         HIP_TRY(hipHostMalloc((void**)&e->h_elites, sizeof(float) * cap, hipHostMallocDefault));
     }
     const size_t vn = V * (size_t)n;
-    const bool has_ee = e->cfg.model == MPPI_MODEL_ARM || e->cfg.model == MPPI_MODEL_WHOLEBODY;
+    const bool has_ee = model_has_ee(e);
     EliteParams p;
     std::memset(&p, 0, sizeof(p));
     p.S = e->d_S; p.stats = e->fp.stats; p.planes = traj ? e->d_traj : nullptr; p.cand = e->d_elite_cand;
     p.idx = (int32_t*)e->d_elites; p.So = e->d_elites + vn; p.w = e->d_elites + 2 * vn;
     p.rows = traj ? e->d_elites + 3 * vn : nullptr;
     p.V = e->V; p.K = e->K; p.H = e->H; p.n = n;
-    p.C = e->C; p.nstate = has_ee ? e->A : e->C; p.has_ee = has_ee; p.Cr = (int32_t)Cr;
+    p.C = e->C; p.nstate = state_channels(e); p.has_ee = has_ee; p.Cr = (int32_t)Cr;
     p.pitch = traj_pitch(e); p.t_major = e->cfg.model == MPPI_MODEL_QUADROTOR;
     p.coef = e->dp.coef;
     const int rc = mppi_launch_elites(&p, e->stream);

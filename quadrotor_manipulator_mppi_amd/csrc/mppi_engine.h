@@ -247,6 +247,7 @@ mppi_status aql_join(mppi_engine* e);
 mppi_status use_device(mppi_engine* e);
 mppi_status build_vehicle_consts(mppi_engine* e);
 void quad_outputs(const mppi_engine* e, const double* s, const float* u0, double* out);
+void aerial_outputs(const mppi_engine* e, const double* s, const float* u0, double* out);
 mppi_status upload_consts(mppi_engine* e);
 // A tracking engine's table, as upload_consts moves the V > 1 vehicle constants: target_rows_begin
 // waits until the last copy out of the staging rows has run (they may then be rewritten),

@@ -697,9 +697,9 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
         double* out = outp + (size_t)v * odim;
         const bool drone_dim = (model == MPPI_MODEL_DRONE) || (model == MPPI_MODEL_WHOLEBODY && a < 3);
         double o1 = 0.0, o2 = 0.0;   // this dim's two outputs (position, velocity)
-        if (model == MPPI_MODEL_QUADROTOR) {
+        if (model == MPPI_MODEL_QUADROTOR || (model == MPPI_MODEL_AERIAL && a < 4)) {
             // coupled dims (thrust rotated by R(rpy)): the host forms the outputs from u0
-            // (mppi_engine.cpp quad_outputs)
+            // (mppi_engine.cpp quad_outputs; AERIAL's base dims likewise, aerial_outputs)
         } else if (drone_dim) {   // drone_mppi.py:168-169
             const float x0 = x0f, v0 = v0f;
             const float xo = (x0 + v0 * dt) + (0.5f * u0) * dt2;
@@ -712,7 +712,7 @@ __device__ __forceinline__ void fin_body(const float* __restrict__ hdr_base, con
             }
         } else {           // mppi.py:157-158 (qdes uses the OLD u_prev[0])
             const int j = a - qoff;
-            const int base = (model == MPPI_MODEL_WHOLEBODY) ? 6 : 0;
+            const int base = (model == MPPI_MODEL_WHOLEBODY) ? 6 : (model == MPPI_MODEL_AERIAL) ? 12 : 0;
             const float t1 = uold0 * dt;
             const float t2 = ((0.5f * u0) * dt) * dt;
             const float t3 = u0 * dt;

@@ -53,6 +53,7 @@ mppi_status fail(mppi_status st, const char* fmt, ...) {
 int nq_of(const mppi_config& c) {
     if (c.model == MPPI_MODEL_ARM) return c.n_action;
     if (c.model == MPPI_MODEL_WHOLEBODY) return c.n_action - 3;
+    if (c.model == MPPI_MODEL_AERIAL) return c.n_action - 4;
     return 0;
 }
 
@@ -246,7 +247,7 @@ void host_fk(const mppi_joint* joints, int nj, const double* q, const double* xy
 }
 
 mppi_status validate(const mppi_config& c) {
-    if (c.model < 0 || c.model > 3) return fail(MPPI_ERR_INVALID_ARG, "unknown model %d", c.model);
+    if (c.model < 0 || c.model > MPPI_MODEL_AERIAL) return fail(MPPI_ERR_INVALID_ARG, "unknown model %d", c.model);
     if (c.n_vehicles < 1 || c.n_samples < 1 || c.n_horizon < 2 || c.n_horizon > MPPI_MAX_HORIZON)
         return fail(MPPI_ERR_INVALID_ARG, "bad sizes V=%d K=%d H=%d", c.n_vehicles, c.n_samples, c.n_horizon);
     if (c.model == MPPI_MODEL_DRONE && c.n_action != 3)
@@ -264,7 +265,21 @@ mppi_status validate(const mppi_config& c) {
             !(c.quad_inertia[2] > 0.0f))
             return fail(MPPI_ERR_INVALID_ARG, "QUADROTOR needs a positive mass and inertia");
     }
-    if (c.model == MPPI_MODEL_ARM || c.model == MPPI_MODEL_WHOLEBODY) {
+    if (c.model == MPPI_MODEL_AERIAL) {   // (what the model leaves out is refused by name: include/mppi_hip.h)
+        if (c.n_action != 11)
+            return fail(MPPI_ERR_INVALID_ARG, "AERIAL kernels are built for 4 + 7 dims (n_action 11: thrust, 3 torques, the "
+                        "Kinova joints; got %d)", c.n_action);
+        if (c.n_horizon > 64) return fail(MPPI_ERR_INVALID_ARG, "AERIAL supports H <= 64 (got %d)", c.n_horizon);
+        if (!(c.quad_mass > 0.0f) || !(c.quad_inertia[0] > 0.0f) || !(c.quad_inertia[1] > 0.0f) ||
+            !(c.quad_inertia[2] > 0.0f))
+            return fail(MPPI_ERR_INVALID_ARG, "AERIAL needs a positive mass and inertia");
+        if (c.cost_terms)
+            return fail(MPPI_ERR_INVALID_ARG, "AERIAL runs the pose cost alone: cost_terms 0x%x (the CostManager terms and "
+                        "target tracking) are not available on this model", c.cost_terms);
+        if (c.shard_count != 1)
+            return fail(MPPI_ERR_INVALID_ARG, "AERIAL engines are not sharded (shard_count %d)", c.shard_count);
+    }
+    if (c.model == MPPI_MODEL_ARM || c.model == MPPI_MODEL_WHOLEBODY || c.model == MPPI_MODEL_AERIAL) {
         if (c.n_joints < 1 || c.n_joints > MPPI_MAX_JOINTS)
             return fail(MPPI_ERR_INVALID_ARG, "n_joints=%d", c.n_joints);
         const int nq = nq_of(c);
@@ -349,9 +364,13 @@ void mppi_config_default(mppi_config* c, int32_t model) {
         c->savgol_window = 5;
     } else {                                     // mppi.py:37-75; cost_manager.py:25-28
         c->n_samples = 100;
-        c->n_action = (model == MPPI_MODEL_ARM) ? 7 : 10;
+        c->n_action = (model == MPPI_MODEL_ARM) ? 7 : (model == MPPI_MODEL_AERIAL) ? 11 : 10;
         const int A = c->n_action;
         for (int a = 0; a < A; ++a) c->sigma[a * A + a] = 0.1f;
+        if (model == MPPI_MODEL_AERIAL) {        // the QUADROTOR's Sigma on the base dims, the arm's on the joints
+            c->sigma[0] = 30.0f;
+            for (int a = 1; a < 4; ++a) c->sigma[a * A + a] = 1.0f;
+        }
         if (model == MPPI_MODEL_WHOLEBODY) {
             c->n_horizon = 64;
             for (int a = 0; a < 3; ++a) c->sigma[a * A + a] = 30.0f;
@@ -385,6 +404,7 @@ int32_t mppi_state_dim(const mppi_config* c) {
     if (c->model == MPPI_MODEL_DRONE) return 6;
     if (c->model == MPPI_MODEL_QUADROTOR) return 12;
     if (c->model == MPPI_MODEL_ARM) return 7 + 2 * nq;
+    if (c->model == MPPI_MODEL_AERIAL) return 12 + 2 * nq;
     return 7 + nq + 3 + nq;
 }
 
@@ -393,12 +413,14 @@ int32_t mppi_output_dim(const mppi_config* c) {
     if (c->model == MPPI_MODEL_DRONE) return 6;
     if (c->model == MPPI_MODEL_QUADROTOR) return 12;
     if (c->model == MPPI_MODEL_ARM) return 2 * nq;
+    if (c->model == MPPI_MODEL_AERIAL) return 12 + 2 * nq;
     return 6 + 2 * nq;
 }
 
 int32_t mppi_traj_channels(const mppi_config* c) {
     if (c->model == MPPI_MODEL_DRONE) return 3;
     if (c->model == MPPI_MODEL_QUADROTOR) return 6;
+    if (c->model == MPPI_MODEL_AERIAL) return 6 + nq_of(*c) + 16;
     return c->n_action + 16;
 }
 
@@ -406,7 +428,8 @@ int64_t mppi_rollout_bytes(const mppi_config* c) {
     // algorithmic bytes of one rollout launch: trajectory planes written
     // (+ injected eps read, + eps written when stored) + S + partial records
     const int64_t KH = (int64_t)c->n_vehicles * c->n_samples * c->n_horizon;
-    const int64_t C = (c->model == MPPI_MODEL_DRONE) ? 3 : (c->model == MPPI_MODEL_QUADROTOR) ? 6 : c->n_action + 12;
+    const int64_t C = (c->model == MPPI_MODEL_DRONE) ? 3 : (c->model == MPPI_MODEL_QUADROTOR) ? 6
+                      : (c->model == MPPI_MODEL_AERIAL) ? 6 + nq_of(*c) + 12 : c->n_action + 12;
     int64_t b = 0;
     if (c->store_trajectory) b += KH * C * 4;
     if (c->noise_mode == MPPI_NOISE_INJECTED) b += KH * c->n_action * 4;

@@ -49,6 +49,11 @@ static mppi_status geometry(EngineLayout& l) {
         iters = ((l.K + 15) / 16 * l.V <= 1024) ? 1 : 4;   // (carried in DevParams::iters)
         nb = (l.K + 16 * iters - 1) / (16 * iters);
     }
+    if (c.model == MPPI_MODEL_AERIAL) {      // k_rollout_aerial: the quadrotor's blocks; four dynamics waves only
+        l.threads = 256;                      // where the block's tiles fit (mppi_dev.h aerial_lds_floats)
+        iters = ((l.K + 15) / 16 * l.V <= 1024 || aerial_lds_floats(H, 4) * (int64_t)sizeof(float) > kAerialLdsMax) ? 1 : 4;
+        nb = (l.K + 16 * iters - 1) / (16 * iters);
+    }
     if (nb > 4096) return fail(MPPI_ERR_INVALID_ARG, "too many rollout blocks (%d)", nb);
     // the rollout kernels address one vehicle's trajectory planes through a buffer
     // resource (32-bit byte offsets) and the record bodies with 32-bit indices
@@ -132,14 +137,15 @@ static void chain(EngineLayout& l) {
 
 mppi_status layout_of(const mppi_config& cfg, EngineLayout& l) {
     l.cfg = cfg;
-    if (l.cfg.model == MPPI_MODEL_WHOLEBODY) l.cfg.state_f64 = 0;
+    if (l.cfg.model == MPPI_MODEL_WHOLEBODY || l.cfg.model == MPPI_MODEL_AERIAL) l.cfg.state_f64 = 0;
     const mppi_config& c = l.cfg;
     l.K = c.n_samples; l.H = c.n_horizon; l.A = c.n_action; l.V = c.n_vehicles;
     l.nq = nq_of(c);
-    l.qoff = (c.model == MPPI_MODEL_WHOLEBODY) ? 3 : 0;
+    l.qoff = (c.model == MPPI_MODEL_WHOLEBODY) ? 3 : (c.model == MPPI_MODEL_AERIAL) ? 4 : 0;
     l.state_dim = mppi_state_dim(&c);
     l.out_dim = mppi_output_dim(&c);
-    l.C = (c.model == MPPI_MODEL_DRONE) ? 3 : (c.model == MPPI_MODEL_QUADROTOR) ? 6 : l.A + 12;
+    l.C = (c.model == MPPI_MODEL_DRONE) ? 3 : (c.model == MPPI_MODEL_QUADROTOR) ? 6
+          : (c.model == MPPI_MODEL_AERIAL) ? 6 + l.nq + 12 : l.A + 12;
     l.out_bytes = (int64_t)(off_xerr(&l) + 16);
     const int H = l.H, P = (kHdr + l.A * H + 3) & ~3;
 
@@ -154,6 +160,9 @@ mppi_status layout_of(const mppi_config& cfg, EngineLayout& l) {
     // (the extra CostManager terms' tables; the tracking bit alone needs none)
     if ((c.cost_terms & ~MPPI_COST_TARGET_TRACK) && (st = cost_tables(l)) != MPPI_OK) return st;
     chain(l);
+    if (c.model == MPPI_MODEL_AERIAL && l.dp.chain_fast != 2)
+        return fail(MPPI_ERR_INVALID_ARG, "AERIAL kernels are built for the Kinova chain (leading fixed joints, then the "
+                    "seven revolute-z joints of the ARM kernels' origin table)");
 
     p.model = c.model; p.V = l.V; p.K = l.K; p.H = H; p.A = l.A;
     p.nq = l.nq; p.qoff = l.qoff; p.nj = c.n_joints;
@@ -208,6 +217,9 @@ mppi_status layout_of(const mppi_config& cfg, EngineLayout& l) {
 mppi_status scene_validate(const mppi_config& c, const mppi_scene& s) {
     if (c.model == MPPI_MODEL_QUADROTOR)
         return fail(MPPI_ERR_INVALID_ARG, "a scene needs the ARM, WHOLEBODY or DRONE model (no QUADROTOR scene kernel)");
+    if (c.model == MPPI_MODEL_AERIAL)
+        return fail(MPPI_ERR_INVALID_ARG, "a scene needs the ARM, WHOLEBODY or DRONE model (no AERIAL scene, field or "
+                    "self-collision kernel)");
     if (s.n_body < 0 || s.n_body > MPPI_MAX_BODY_SPHERES)
         return fail(MPPI_ERR_INVALID_ARG, "scene: n_body %d outside 0..%d", s.n_body, MPPI_MAX_BODY_SPHERES);
     const float w[3] = {s.w_obs, s.margin, s.penalty};
@@ -534,7 +546,7 @@ extern "C" void mppi_scene_default(mppi_scene* s, const mppi_config* cfg) {
     if (!s) return;
     std::memset(s, 0, sizeof(*s));
     s->w_obs = 100.0f; s->margin = 0.05f; s->penalty = 1e4f;
-    if (!cfg || cfg->model == MPPI_MODEL_QUADROTOR) return;
+    if (!cfg || cfg->model == MPPI_MODEL_QUADROTOR || cfg->model == MPPI_MODEL_AERIAL) return;
     const auto add = [&](int frame, float r) {
         if (s->n_body < MPPI_MAX_BODY_SPHERES) s->body[s->n_body++] = mppi_body_sphere{frame, {0.0f, 0.0f, 0.0f}, r};
     };

@@ -47,6 +47,9 @@ extern "C" int mppi_launch_rollout(const DevParams* p, int threads, void* stream
         case MPPI_MODEL_QUADROTOR:
             if (p->A == 4) return mppi_launch_rollout_quad(p, threads, stream);
             break;
+        case MPPI_MODEL_AERIAL:   // (no tracking, scene, field or self form: those launches refuse the model)
+            if (p->A == 11) return mppi_launch_rollout_aerial(p, threads, stream);
+            break;
     }
     return -1;
 }
@@ -68,6 +71,8 @@ extern "C" int mppi_launch_rollout_track(const DevParams* p, const float* ttab, 
             break;
         case MPPI_MODEL_QUADROTOR:
             if (p->A == 4) return mppi_launch_rollout_quad_tt(p, ttab, threads, stream);
+            break;
+        default:
             break;
     }
     return -1;
@@ -120,13 +125,14 @@ extern "C" int mppi_launch_philox(uint64_t seed, uint32_t step, int vehicle, int
     const int n = K * H;
     const dim3 g((n + 255) / 256), b(256);
     hipStream_t s = (hipStream_t)stream;
-    switch (A) {   // the action dims the models draw (drone 3, quadrotor 4, arm 7, whole-body 10) + 2, 8
+    switch (A) {   // the action dims the models draw (drone 3, quadrotor 4, arm 7, whole-body 10, aerial 11) + 2, 8
         case 2: hipLaunchKernelGGL(k_philox<2>, g, b, 0, s, seed, step, vehicle, k0, K, H, z, raw); break;
         case 3: hipLaunchKernelGGL(k_philox<3>, g, b, 0, s, seed, step, vehicle, k0, K, H, z, raw); break;
         case 4: hipLaunchKernelGGL(k_philox<4>, g, b, 0, s, seed, step, vehicle, k0, K, H, z, raw); break;
         case 7: hipLaunchKernelGGL(k_philox<7>, g, b, 0, s, seed, step, vehicle, k0, K, H, z, raw); break;
         case 8: hipLaunchKernelGGL(k_philox<8>, g, b, 0, s, seed, step, vehicle, k0, K, H, z, raw); break;
         case 10: hipLaunchKernelGGL(k_philox<10>, g, b, 0, s, seed, step, vehicle, k0, K, H, z, raw); break;
+        case 11: hipLaunchKernelGGL(k_philox<11>, g, b, 0, s, seed, step, vehicle, k0, K, H, z, raw); break;
         default: return -1;
     }
     return (int)hipGetLastError();

@@ -217,11 +217,11 @@ static mppi_status assemble_records(mppi_engine* e) {
                 st3 = (a == 0 || nf > st3 || std::isnan(nf)) ? nf : st3;
             }
             double* ov = e->rec_out.data() + (size_t)v * od;
-            if (model == MPPI_MODEL_QUADROTOR) continue;
+            if (model == MPPI_MODEL_QUADROTOR || (model == MPPI_MODEL_AERIAL && a < 4)) continue;   // (host-formed)
             if (model == MPPI_MODEL_DRONE || (model == MPPI_MODEL_WHOLEBODY && a < 3)) {
                 ov[a] = o1; ov[3 + a] = o2;
             } else {
-                const int base = (model == MPPI_MODEL_WHOLEBODY) ? 6 : 0, j = a - qoff;
+                const int base = (model == MPPI_MODEL_WHOLEBODY) ? 6 : (model == MPPI_MODEL_AERIAL) ? 12 : 0, j = a - qoff;
                 ov[base + j] = o1; ov[base + nq + j] = o2;
             }
         }
@@ -260,6 +260,9 @@ mppi_status mppi_read_outputs(mppi_engine* e, double* out, float* u0, mppi_stats
     if (out && e->cfg.model == MPPI_MODEL_QUADROTOR)
         for (int v = 0; v < e->V; ++v)
             quad_outputs(e, e->state.data() + (size_t)v * e->state_dim, uu + (size_t)v * e->A, out + (size_t)v * e->out_dim);
+    if (out && e->cfg.model == MPPI_MODEL_AERIAL)
+        for (int v = 0; v < e->V; ++v)
+            aerial_outputs(e, e->state.data() + (size_t)v * e->state_dim, uu + (size_t)v * e->A, out + (size_t)v * e->out_dim);
     if (u0) std::memcpy(u0, uu, sizeof(float) * e->V * e->A);
     bool nonfinite = false;
     for (int v = 0; v < e->V; ++v) {

@@ -16,7 +16,7 @@ from . import _capi as capi
 from .robot.urdf_chain import load_chain
 
 MODELS = {"drone": capi.MODEL_DRONE, "arm": capi.MODEL_ARM, "wholebody": capi.MODEL_WHOLEBODY,
-          "quadrotor": capi.MODEL_QUADROTOR}
+          "quadrotor": capi.MODEL_QUADROTOR, "aerial": capi.MODEL_AERIAL}
 QUAD_FIELDS = ("quad_mass", "quad_kd", "quad_gravity")
 JOINT_TYPES = {"fixed": capi.JOINT_FIXED, "revolute": capi.JOINT_REVOLUTE,
                "continuous": capi.JOINT_REVOLUTE, "prismatic": capi.JOINT_PRISMATIC}
@@ -271,7 +271,8 @@ def make_config(model: str = "arm", n_samples: Optional[int] = None, n_horizon: 
     model): one pose target per horizon step, ``Engine.set_target_trajectory``.  ``cost_weights`` overrides
     ``w_covar, cost_alpha, cost_gamma, w_center, w_joint_track, w_action,
     joint_limit_penalty``.  ``quad`` overrides the QUADROTOR rigid body: ``quad_mass``,
-    ``quad_inertia`` (3,), ``quad_kd``, ``quad_gravity``, ``quad_literal_jinv``.  ``vehicle_offset``:
+    ``quad_inertia`` (3,), ``quad_kd``, ``quad_gravity``, ``quad_literal_jinv`` (also the base of the
+    ``"aerial"`` model: the quadrotor carrying the Kinova arm, 4 + 7 action dims).  ``vehicle_offset``:
     the fleet-wide index of vehicle 0 (vehicle sharding: the device noise is keyed by it)."""
     L = capi.lib()
     cfg = capi.Config()
@@ -295,7 +296,7 @@ def make_config(model: str = "arm", n_samples: Optional[int] = None, n_horizon: 
             cfg.sigma[i] = float(s.reshape(-1)[i])
     if weights is not None:
         cfg.w_stage_pos, cfg.w_stage_ori, cfg.w_term_pos, cfg.w_term_ori = map(float, weights)
-    if model in ("arm", "wholebody"):
+    if model in ("arm", "wholebody", "aerial"):
         fill_joints(cfg, chain if chain is not None else load_chain())
     for k, val in (quad or {}).items():
         if k == "quad_inertia":
@@ -740,6 +741,8 @@ class Engine:
     def _ee_path(self, traj: np.ndarray) -> np.ndarray:
         """(..., H, 3) positions out of (..., H, C) rows: the EE matrix's translation column (arm,
         whole-body) or the vehicle's position."""
+        if self.cfg.model == capi.MODEL_AERIAL:   # xyz, rpy, q ahead of the EE
+            return traj[..., -16:].reshape(*traj.shape[:-1], 4, 4)[..., :3, 3].copy()
         if self.cfg.model in (capi.MODEL_ARM, capi.MODEL_WHOLEBODY):
             return traj[..., self.A:].reshape(*traj.shape[:-1], 4, 4)[..., :3, 3].copy()
         return traj[..., :3].copy()
