@@ -577,6 +577,72 @@ mppi_status mppi_set_occupancy(mppi_engine* e, const float* origin3, const uint8
  * engine not created by mppi_create_scene_field. */
 mppi_status mppi_get_distance_field(mppi_engine* e, int32_t* is_set, float* origin3, float* d_zyx);
 
+/* Depth images: the occupancy map carved and marked on the device from what a depth camera delivers, so
+ * that only the image and a camera pose cross the bus (sensor -> map -> field -> rollout cost on the GPU).
+ *
+ * The map.  A field engine owns a persistent occupancy map: one byte per node, (nz, ny, nx), 0 = free,
+ * 1 = occupied, all free until first written.  mppi_set_occupancy seeds it (nonzero reads back as 1);
+ * mppi_set_distance_field, with data or NULL, leaves it alone, and the next map call (mppi_integrate_depth,
+ * mppi_shift_map) rebuilds the field from the map.
+ *
+ * The view.  depth_hw is (height, width) float32 metres along the optical axis (sensor_msgs/Image 32FC1).
+ * Rows and columns 0, stride, 2 stride, ... are used.  Per used pixel (column i, row j, value z):
+ *   NaN, -inf, z < z_min     the pixel is skipped
+ *   z_min <= z <= z_max      a return at z
+ *   z > z_max, +inf          a miss: the ray ends at z_max and marks nothing
+ * Arithmetic: fp32 throughout, every product-sum an explicit fmaf, no contraction.  inv_fx = 1 / fx,
+ * inv_fy = 1 / fy, inv_voxel = 1 / voxel and R = mppi_target_rotation(quat_xyzw) are formed once on the host.
+ *   xn = ((float)i - cx) inv_fx, yn = ((float)j - cy) inv_fy, p_cam = (xn z, yn z, z)
+ *   w_d  = fmaf(R[3d], p0, fmaf(R[3d+1], p1, fmaf(R[3d+2], p2, pos_d)))
+ *   ue_d = (w_d - origin_d) inv_voxel (the end point), uo_d = (pos_d - origin_d) inv_voxel (the camera)
+ * A ray with a non-finite ue or uo is skipped.  A point u is in the grid iff -0.5 <= u_d < n_d - 0.5 on all
+ * three axes, tested in float; only then is node_d = (int)floorf(u_d + 0.5f) formed.  The test comes before
+ * the integer conversion, so no input can form an address outside the grid: not NaN, not +-inf, not 3e38
+ * metres, not a camera a light-year away.
+ * March: du = ue - uo, L = max_d |du_d|, n = (int)fminf(fmaxf(ceilf(2 L), 1), MPPI_DEPTH_MAX_SAMPLES),
+ * inv_n = 1.0f / (float)n (a correctly rounded division); sample m, 0 <= m < n, is
+ * u_d(m) = fmaf((float)m inv_n, du_d, uo_d).
+ *   carve set F   the nodes of all in-grid samples of all rays, except a return's samples that fall in
+ *                 that return's own end-point node (carve = 0: F is empty)
+ *   mark set O    the in-grid end-point nodes of the returns
+ * One image turns the map into (map \ F) U O: occupied wins within a frame.  The result is a pure function
+ * of (map, image, view); it does not depend on thread order (both passes store constants).  The kernels
+ * visit only the samples a conservative slab clip leaves (csrc/mppi_depth.h depth_clip); the result is the
+ * set above, bit for bit, and the host twin runs the same inlines.
+ * Out of scope: probabilistic (log-odds) fusion, lens distortion, point-cloud input, filtering the robot's
+ * own arm out of the image (z_min is the only guard), per-vehicle maps. */
+#define MPPI_DEPTH_MAX_PIXELS  (1 << 20)
+#define MPPI_DEPTH_MAX_SAMPLES 16384
+typedef struct {
+    int32_t width, height;      /* columns, rows: >= 1, product <= MPPI_DEPTH_MAX_PIXELS            */
+    int32_t stride;             /* rows and columns 0, stride, 2 stride, ... are used; >= 1          */
+    int32_t carve;              /* 1: clear free space along the rays; 0: mark end points only       */
+    float fx, fy, cx, cy;       /* pinhole, pixels (CameraInfo K[0], K[4], K[2], K[5]); fx, fy > 0   */
+    float z_min, z_max;         /* m, 0 <= z_min < z_max, z_max / voxel <= 4096                      */
+    float pos[3], quat_xyzw[4]; /* the optical frame (z forward, x right, y down) in the world       */
+    int32_t reserved[3];        /* 0 */
+} mppi_depth_view;              /* 80 bytes */
+/* One image into the map (k_depth_carve, k_depth_mark), then the transform of mppi_set_occupancy under
+ * max_dist, and the header's copy with the set flag on: all on the engine's stream, ordered before the next
+ * step on either dispatch path.  The image is copied to pinned staging of its own (the caller's array is
+ * free on return); staging and its device twin hold MPPI_DEPTH_MAX_PIXELS floats, allocated at the first
+ * call and never grown.  If no map call came before, the transform's scratch is allocated and the map
+ * zero-filled.  MPPI_ERR_STATE on an engine without a field; MPPI_ERR_INVALID_ARG for a NULL view or image,
+ * a non-finite view value, fx or fy <= 0, a size, stride or z limit outside the ranges above, a quaternion
+ * whose squared norm is outside [0.5, 2] (others are normalised, as targets are), a nonzero reserved word,
+ * a max_dist that is NaN or +inf. */
+mppi_status mppi_integrate_depth(mppi_engine* e, const mppi_depth_view* view, const float* depth_hw, float max_dist);
+/* Moves the window with the vehicle (k_map_shift): new node (ix, iy, iz) = old node (ix + sx, iy + sy,
+ * iz + sz), free where that falls outside the grid; the origin moves to fmaf((float)s_d, voxel, origin_d).
+ * A zero shift changes nothing, |s_d| >= n_d clears the map.  The copy goes through the transform's int32
+ * scratch (no new allocation); the transform runs and the field flag is set, as above.  MPPI_ERR_STATE
+ * without a field; MPPI_ERR_INVALID_ARG for a NULL shift, a max_dist that is NaN or +inf, a shift that
+ * takes the origin out of the finite range. */
+mppi_status mppi_shift_map(mppi_engine* e, const int32_t shift_xyz[3], float max_dist);
+/* The map as it stands on the device (synchronous), (nz, ny, nx), 0 or 1.  All free, with no allocation,
+ * before the first map call.  MPPI_ERR_STATE without a field. */
+mppi_status mppi_get_occupancy(mppi_engine* e, uint8_t* occ_zyx);
+
 /* ---- Self-collision avoidance: pairs of body spheres in the scene rollout cost (the project's own
  * term; what a MoveIt-style stack keeps as the allowed-collision matrix, turned round: the pairs that
  * are NOT allowed to touch).  ARM and WHOLEBODY; DRONE (no chain: every pair is rigid), QUADROTOR and
@@ -687,6 +753,12 @@ mppi_status mppi_host_fk(const mppi_joint* joints, int32_t n_joints, const doubl
  * O(n) per line per output node.  MPPI_ERR_INVALID_ARG for a NULL pointer, a descriptor
  * mppi_create_scene_field refuses, a max_dist that is NaN or +inf. */
 mppi_status mppi_occupancy_field(const mppi_field_desc* desc, const uint8_t* occ_zyx, float max_dist, float* d_zyx);
+/* mppi_integrate_depth's map update on the host, by the same definition and the same inlines: occ_zyx_inout
+ * (nz,ny,nx) is updated in place (nonzero counts as occupied; on return every node holds 0 or 1) and equals
+ * the device map, as mppi_get_occupancy returns it, bit for bit.  desc as mppi_create_scene_field validates it; the view and the image as
+ * mppi_integrate_depth validates them (MPPI_ERR_INVALID_ARG, also for a NULL map). */
+mppi_status mppi_depth_integrate_host(const mppi_field_desc* desc, const mppi_depth_view* view, const float* depth_hw,
+                                      uint8_t* occ_zyx_inout);
 
 /* Device RNG check: standard normals z (K,H,A) and the raw Philox words (K,H,W),
  * W = mppi_philox_words(A), exactly as the rollout kernel draws them for (seed, step,

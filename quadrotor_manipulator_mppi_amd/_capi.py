@@ -76,6 +76,17 @@ class FieldDesc(C.Structure):
     _fields_ = [("dims", C.c_int32 * 3), ("voxel", C.c_float), ("origin", C.c_float * 3), ("reserved", C.c_int32)]
 
 
+DEPTH_MAX_PIXELS = 1 << 20
+DEPTH_MAX_SAMPLES = 16384
+
+
+class DepthViewC(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("carve", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("z_min", C.c_float), ("z_max", C.c_float), ("pos", C.c_float * 3), ("quat_xyzw", C.c_float * 4),
+                ("reserved", C.c_int32 * 3)]
+
+
 MAX_SELF_PAIRS = 32
 
 
@@ -167,6 +178,10 @@ PROTOTYPES = {
     "mppi_set_occupancy": (_ST, [_P, _F, C.POINTER(C.c_uint8), C.c_float]),
     "mppi_get_distance_field": (_ST, [_P, _I32, _F, _F]),
     "mppi_occupancy_field": (_ST, [C.POINTER(FieldDesc), C.POINTER(C.c_uint8), C.c_float, _F]),
+    "mppi_integrate_depth": (_ST, [_P, C.POINTER(DepthViewC), _F, C.c_float]),
+    "mppi_shift_map": (_ST, [_P, _I32, C.c_float]),
+    "mppi_get_occupancy": (_ST, [_P, C.POINTER(C.c_uint8)]),
+    "mppi_depth_integrate_host": (_ST, [C.POINTER(FieldDesc), C.POINTER(DepthViewC), _F, C.POINTER(C.c_uint8)]),
     "mppi_self_collision_default": (None, [C.POINTER(SelfCollision), _CFG, C.POINTER(Scene)]),
     "mppi_create_scene_self": (_ST, [_CFG, C.POINTER(Scene), C.POINTER(FieldDesc), C.POINTER(SelfCollision), C.POINTER(_P)]),
     "mppi_get_self_clearances": (_ST, [_P, _F]),
@@ -211,6 +226,8 @@ DEBUG_PROTOTYPES = {
     "mppi_debug_self_rollout_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_char_p, C.c_int32]),
     "mppi_debug_edt_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_int32]),
     "mppi_debug_field_words": (C.c_int32, [_P, _F]),
+    "mppi_debug_depth_validate": (C.c_int32, [C.POINTER(FieldDesc), C.POINTER(DepthViewC), C.c_float]),
+    "mppi_debug_map_shift": (C.c_int32, [C.POINTER(FieldDesc), _I32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _F]),
 }
 
 _lib = None

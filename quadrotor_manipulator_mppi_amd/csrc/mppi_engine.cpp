@@ -544,7 +544,7 @@ void mppi_destroy(mppi_engine* e) {
     void* dev[] = {e->d_xregion, e->d_xpeers, e->d_sigma, e->d_joints, e->d_vc, e->d_u_prev, e->d_noise_in, e->d_traj, e->d_noise_out,
                    e->d_S, e->d_hdr, e->d_rdata, e->d_out, e->d_wraw, e->d_wsmooth, e->d_w,
                    e->d_sinv, e->d_gamma, e->d_jtraj, e->d_ttab, e->d_scene, e->d_field, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec,
-                   e->d_plan_vc, e->d_plan, e->d_elite_cand, e->d_elites, e->d_edt};
+                   e->d_plan_vc, e->d_plan, e->d_elite_cand, e->d_elites, e->d_edt, e->d_depth};
     for (void* p : dev) if (p) (void)hipFree(p);
     if (e->h_out) (void)hipHostFree(e->h_out);
     if (e->h_vc) (void)hipHostFree(e->h_vc);
@@ -554,6 +554,7 @@ void mppi_destroy(mppi_engine* e) {
     if (e->h_scene) (void)hipHostFree(e->h_scene);
     if (e->ev_scene) (void)hipEventDestroy(e->ev_scene);
     if (e->h_field) (void)hipHostFree(e->h_field);
+    if (e->h_depth) (void)hipHostFree(e->h_depth);
     if (e->ev_field) (void)hipEventDestroy(e->ev_field);
     if (e->h_elites) (void)hipHostFree(e->h_elites);
     if (e->ev_vc) (void)hipEventDestroy(e->ev_vc);
@@ -838,6 +839,137 @@ mppi_status mppi_set_occupancy(mppi_engine* e, const float* origin3, const uint8
     HIP_TRY(hipMemcpyAsync(e->d_field, e->h_field, sizeof(float) * kFieldHdrW, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipEventRecord(e->ev_field, e->stream));
     e->field_pending = true;
+    return MPPI_OK;
+}
+
+// ---- The persistent occupancy map of a field engine: the bytes behind the transform's two int32 grids in
+// d_edt, where mppi_set_occupancy uploads them.  map_ready allocates the scratch and zero-fills the map when
+// no map call came before (stream-ordered); map_transform queues the transform from the map as it stands
+// and the header's copy with the set flag on, exactly as mppi_set_occupancy does, and records ev_field.
+static uint8_t* map_bytes(mppi_engine* e) { return (uint8_t*)e->d_edt + 2 * sizeof(int32_t) * (size_t)field_voxels(e->field); }
+
+static mppi_status map_ready(mppi_engine* e) {
+    if (e->d_edt) return MPPI_OK;
+    const int64_t nvox = field_voxels(e->field);
+    HIP_TRY(hipMalloc(&e->d_edt, edt_scratch_bytes(nvox)));
+    HIP_TRY(hipMemsetAsync(map_bytes(e), 0, (size_t)nvox, e->stream));
+    return MPPI_OK;
+}
+
+static mppi_status map_transform(mppi_engine* e, float max_dist) {
+    const int64_t nvox = field_voxels(e->field);
+    field_header(e->field, e->field.origin, true, e->h_field);
+    EdtParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.g_occ = (int32_t*)e->d_edt;
+    p.g_free = p.g_occ + nvox;
+    p.occ = map_bytes(e);
+    p.cells = e->d_field + kFieldHdrW;
+    p.nx = e->field.dims[0]; p.ny = e->field.dims[1]; p.nz = e->field.dims[2];
+    p.voxel = e->field.voxel;
+    p.cap = edt_cap(e->field.dims, e->field.voxel, max_dist);
+    p.window = edt_window(p.voxel, p.cap);
+    const int rc = mppi_launch_edt(&p, e->stream);
+    if (rc != 0) return fail(MPPI_ERR_HIP, "occupancy transform launch failed (%d: %s)", rc,
+                             rc > 0 ? hipGetErrorString((hipError_t)rc) : "no kernel for these dims");
+    HIP_TRY(hipMemcpyAsync(e->d_field, e->h_field, sizeof(float) * kFieldHdrW, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipEventRecord(e->ev_field, e->stream));
+    e->field_pending = true;
+    return MPPI_OK;
+}
+
+// what mppi_integrate_depth queues once the image is in its staging buffer
+static mppi_status depth_queue(mppi_engine* e, const mppi_depth_view& view, size_t pixels, float max_dist) {
+    HIP_TRY(hipMemcpyAsync(e->d_depth, e->h_depth, sizeof(float) * pixels, hipMemcpyHostToDevice, e->stream));
+    DepthParams p;
+    depth_params(e->field, view, p);
+    p.depth = e->d_depth;
+    p.occ = map_bytes(e);
+    const int rc = mppi_launch_depth(&p, e->stream);
+    if (rc != 0) return fail(MPPI_ERR_HIP, "depth launch failed (%d: %s)", rc,
+                             rc > 0 ? hipGetErrorString((hipError_t)rc) : "no kernel for this image");
+    return map_transform(e, max_dist);
+}
+
+// One depth image into the map: the image goes to pinned staging of its own and from there to its device
+// twin; k_depth_carve and k_depth_mark (mppi_depth.hip) update the map's bytes, the transform rebuilds the
+// field from them.  Ordered before the next step as mppi_set_occupancy is.
+mppi_status mppi_integrate_depth(mppi_engine* e, const mppi_depth_view* view, const float* depth_hw, float max_dist) {
+    if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
+    if (!e->d_field) return fail(MPPI_ERR_STATE, "engine created without a field (mppi_create_scene_field)");
+    mppi_status st = depth_validate(e->field, view, depth_hw);
+    if (st != MPPI_OK) return st;
+    if (std::isnan(max_dist) || (std::isinf(max_dist) && max_dist > 0.0f))
+        return fail(MPPI_ERR_INVALID_ARG, "depth: max_dist %g (a finite cap, or <= 0 for none)", max_dist);
+    if (use_device(e)) return MPPI_ERR_HIP;
+    if (!e->h_depth) HIP_TRY(hipHostMalloc((void**)&e->h_depth, sizeof(float) * MPPI_DEPTH_MAX_PIXELS, hipHostMallocDefault));
+    if (!e->d_depth) HIP_TRY(hipMalloc((void**)&e->d_depth, sizeof(float) * MPPI_DEPTH_MAX_PIXELS));
+    if (e->field_pending) {   // the previous copies out of the staging buffers must be done
+        HIP_TRY(hipEventSynchronize(e->ev_field));
+        e->field_pending = false;
+    }
+    if ((st = map_ready(e)) != MPPI_OK) return st;
+    const size_t pixels = (size_t)view->width * (size_t)view->height;
+    std::memcpy(e->h_depth, depth_hw, sizeof(float) * pixels);
+    st = depth_queue(e, *view, pixels, max_dist);
+    // a failure behind the image's copy leaves no event to guard the staging buffers: wait for what was queued
+    if (st != MPPI_OK) (void)hipStreamSynchronize(e->stream);
+    return st;
+}
+
+// what mppi_shift_map queues.  The origin moves as soon as the shift is launched, so the bytes and the origin
+// stay one map even where the transform behind them fails.
+static mppi_status shift_queue(mppi_engine* e, ShiftParams& p, const float* origin, float max_dist) {
+    const int64_t nvox = field_voxels(e->field);
+    p.src = (const uint8_t*)e->d_edt;
+    p.occ = map_bytes(e);
+    HIP_TRY(hipMemcpyAsync(e->d_edt, p.occ, (size_t)nvox, hipMemcpyDeviceToDevice, e->stream));
+    const int rc = mppi_launch_map_shift(&p, e->stream);
+    if (rc != 0) return fail(MPPI_ERR_HIP, "map shift launch failed (%d: %s)", rc,
+                             rc > 0 ? hipGetErrorString((hipError_t)rc) : "no kernel for these dims");
+    std::memcpy(e->field.origin, origin, 3 * sizeof(float));
+    return map_transform(e, max_dist);
+}
+
+// The window move: the map is copied into the transform's int32 scratch (which the transform that follows
+// overwrites anyway), k_map_shift writes it back shifted, and the origin moves with it.
+mppi_status mppi_shift_map(mppi_engine* e, const int32_t shift_xyz[3], float max_dist) {
+    if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
+    if (!e->d_field) return fail(MPPI_ERR_STATE, "engine created without a field (mppi_create_scene_field)");
+    ShiftParams p;
+    float origin[3];
+    mppi_status st = shift_validate(e->field, shift_xyz, max_dist, p, origin);
+    if (st != MPPI_OK) return st;
+    if (use_device(e)) return MPPI_ERR_HIP;
+    if (e->field_pending) {
+        HIP_TRY(hipEventSynchronize(e->ev_field));
+        e->field_pending = false;
+    }
+    if ((st = map_ready(e)) != MPPI_OK) return st;
+    st = shift_queue(e, p, origin, max_dist);
+    if (st != MPPI_OK) (void)hipStreamSynchronize(e->stream);   // (as in mppi_integrate_depth)
+    return st;
+}
+
+// The map as it stands on the device: its bytes into the pinned staging copy behind the header (once no
+// upload reads it any more), one synchronise, and 0 or 1 handed out.
+mppi_status mppi_get_occupancy(mppi_engine* e, uint8_t* occ_zyx) {
+    if (!e || !occ_zyx) return fail(MPPI_ERR_INVALID_ARG, "null argument");
+    if (!e->d_field) return fail(MPPI_ERR_STATE, "engine created without a field (mppi_create_scene_field)");
+    const int64_t nvox = field_voxels(e->field);
+    if (!e->d_edt) {   // no map call yet: all free
+        std::memset(occ_zyx, 0, (size_t)nvox);
+        return MPPI_OK;
+    }
+    if (use_device(e)) return MPPI_ERR_HIP;
+    if (e->field_pending) {
+        HIP_TRY(hipEventSynchronize(e->ev_field));
+        e->field_pending = false;
+    }
+    uint8_t* const stage = (uint8_t*)(e->h_field + kFieldHdrW);
+    HIP_TRY(hipMemcpyAsync(stage, map_bytes(e), (size_t)nvox, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int64_t i = 0; i < nvox; ++i) occ_zyx[i] = stage[i] != 0;
     return MPPI_OK;
 }
 

@@ -139,6 +139,10 @@ struct mppi_engine : mppi_host::EngineLayout {
     // mppi_set_occupancy's device scratch (allocated at its first call, for the field's dims: the two
     // int32 grids of the transform, then the occupancy bytes; mppi_edt.h edt_scratch_bytes)
     void* d_edt = nullptr;
+    // mppi_integrate_depth's image: pinned staging and its device twin, MPPI_DEPTH_MAX_PIXELS floats each,
+    // allocated at its first call (ev_field guards the staging copy, as it does h_field)
+    float* h_depth = nullptr;
+    float* d_depth = nullptr;
     float* d_exchange = nullptr;
     // mppi_get_plan's buffers (allocated at its first call): the host's vehicle constants; the
     // planes (V,C,H), cost_t (V,H), pos_err (V,H) and S (V) in one block, and its pinned host copy

@@ -529,6 +529,84 @@ void occupancy_field(const mppi_field_desc& f, const uint8_t* occ, float max_dis
     for (int64_t e = 0; e < nvox; ++e) d_zyx[e] = edt_value(ga[(size_t)e], gb[(size_t)e], f.voxel, cap);
 }
 
+// ------------------------------------------------------------------ depth images
+static_assert(sizeof(mppi_depth_view) == 80, "mppi_depth_view is 80 bytes (include/mppi_hip.h)");
+mppi_status depth_validate(const mppi_field_desc& f, const mppi_depth_view* v, const float* depth_hw) {
+    if (!v) return fail(MPPI_ERR_INVALID_ARG, "depth: null view");
+    if (!depth_hw) return fail(MPPI_ERR_INVALID_ARG, "depth: null image");
+    if (v->width < 1 || v->height < 1 || (int64_t)v->width * v->height > (int64_t)MPPI_DEPTH_MAX_PIXELS)
+        return fail(MPPI_ERR_INVALID_ARG, "depth: image %d x %d (each >= 1, at most MPPI_DEPTH_MAX_PIXELS pixels)", v->width, v->height);
+    if (v->stride < 1) return fail(MPPI_ERR_INVALID_ARG, "depth: stride %d (>= 1)", v->stride);
+    if (v->carve != 0 && v->carve != 1) return fail(MPPI_ERR_INVALID_ARG, "depth: carve %d (0 or 1)", v->carve);
+    const float vals[] = {v->fx, v->fy, v->cx, v->cy, v->z_min, v->z_max, v->pos[0], v->pos[1], v->pos[2],
+                          v->quat_xyzw[0], v->quat_xyzw[1], v->quat_xyzw[2], v->quat_xyzw[3]};
+    for (const float x : vals)
+        if (!std::isfinite(x)) return fail(MPPI_ERR_INVALID_ARG, "depth: non-finite view value");
+    if (!(v->fx > 0.0f) || !(v->fy > 0.0f) || !std::isfinite(1.0f / v->fx) || !std::isfinite(1.0f / v->fy))
+        return fail(MPPI_ERR_INVALID_ARG, "depth: focal lengths %g, %g (> 0)", v->fx, v->fy);
+    if (!(v->z_min >= 0.0f) || !(v->z_min < v->z_max) || !(v->z_max / f.voxel <= 4096.0f))
+        return fail(MPPI_ERR_INVALID_ARG, "depth: z range %g..%g (0 <= z_min < z_max, z_max / voxel <= 4096)", v->z_min, v->z_max);
+    const float* q = v->quat_xyzw;
+    const float n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+    if (!(n2 >= 0.5f && n2 <= 2.0f)) return fail(MPPI_ERR_INVALID_ARG, "depth: quaternion of squared norm %g (0.5..2)", n2);
+    for (const int32_t w : v->reserved)
+        if (w != 0) return fail(MPPI_ERR_INVALID_ARG, "depth: reserved word %d is not 0", w);
+    return MPPI_OK;
+}
+
+void depth_params(const mppi_field_desc& f, const mppi_depth_view& v, DepthParams& p) {
+    std::memset(&p, 0, sizeof(p));
+    p.nx = f.dims[0]; p.ny = f.dims[1]; p.nz = f.dims[2];
+    p.width = v.width; p.height = v.height; p.stride = v.stride;
+    p.cols = depth_used(v.width, v.stride); p.rows = depth_used(v.height, v.stride);
+    p.carve = v.carve;
+    p.inv_fx = 1.0f / v.fx; p.inv_fy = 1.0f / v.fy;
+    p.cx = v.cx; p.cy = v.cy; p.z_min = v.z_min; p.z_max = v.z_max;
+    p.inv_voxel = 1.0f / f.voxel;
+    quat_xyzw_to_R(v.quat_xyzw, p.R);
+    for (int d = 0; d < 3; ++d) { p.pos[d] = v.pos[d]; p.origin[d] = f.origin[d]; }
+}
+
+void depth_integrate(const DepthParams& p) {
+    const int64_t nvox = (int64_t)p.nx * p.ny * p.nz;
+    for (int64_t e = 0; e < nvox; ++e) p.occ[e] = p.occ[e] != 0;
+    for (int pass = p.carve ? 0 : 1; pass < 2; ++pass)   // carve, then mark: occupied wins
+        for (int j = 0; j < p.height; j += p.stride)
+            for (int i = 0; i < p.width; i += p.stride) {
+                DepthRay r;
+                if (!depth_ray(p, i, j, p.depth[(size_t)j * (size_t)p.width + (size_t)i], r)) continue;
+                if (pass == 1) {
+                    if (r.end >= 0) p.occ[r.end] = 1;
+                    continue;
+                }
+                for (int m = r.m_lo; m <= r.m_hi; ++m) {
+                    const int64_t node = depth_sample(p, r, m);
+                    if (node >= 0) p.occ[node] = 0;
+                }
+            }
+}
+
+mppi_status shift_validate(const mppi_field_desc& f, const int32_t* s, float max_dist, ShiftParams& p, float* origin_out) {
+    if (!s) return fail(MPPI_ERR_INVALID_ARG, "shift: null shift");
+    if (std::isnan(max_dist) || (std::isinf(max_dist) && max_dist > 0.0f))
+        return fail(MPPI_ERR_INVALID_ARG, "shift: max_dist %g (a finite cap, or <= 0 for none)", max_dist);
+    std::memset(&p, 0, sizeof(p));
+    p.nx = f.dims[0]; p.ny = f.dims[1]; p.nz = f.dims[2];
+    int32_t c[3];
+    for (int d = 0; d < 3; ++d) {
+        origin_out[d] = fmaf((float)s[d], f.voxel, f.origin[d]);
+        if (!std::isfinite(origin_out[d])) return fail(MPPI_ERR_INVALID_ARG, "shift: %d nodes along axis %d take the origin out of range", s[d], d);
+        c[d] = std::min(std::max(s[d], -f.dims[d]), f.dims[d]);   // (beyond the grid either way: every node is free)
+    }
+    p.sx = c[0]; p.sy = c[1]; p.sz = c[2];
+    return MPPI_OK;
+}
+
+void map_shift(const ShiftParams& p) {
+    const int64_t nvox = (int64_t)p.nx * p.ny * p.nz;
+    for (int64_t e = 0; e < nvox; ++e) p.occ[e] = shift_value(p, e);
+}
+
 void set_generic(EngineLayout& l, int generic) {
     l.generic = generic;
     l.fp.kern = (generic & 1) ? kFinKernGeneric : 0;
@@ -616,6 +694,49 @@ extern "C" mppi_status mppi_occupancy_field(const mppi_field_desc* desc, const u
     if ((st = occupancy_validate(nullptr, occ_zyx, max_dist)) != MPPI_OK) return st;
     if (!d_zyx) return fail(MPPI_ERR_INVALID_ARG, "mppi_occupancy_field: null output");
     occupancy_field(*desc, occ_zyx, max_dist, d_zyx);
+    return MPPI_OK;
+}
+
+// One depth image into an occupancy map on the host (include/mppi_hip.h): mppi_integrate_depth's map update
+// without a device.
+extern "C" mppi_status mppi_depth_integrate_host(const mppi_field_desc* desc, const mppi_depth_view* view, const float* depth_hw,
+                                                 uint8_t* occ_zyx_inout) {
+    mppi_status st = field_validate(desc);
+    if (st != MPPI_OK) return st;
+    if ((st = depth_validate(*desc, view, depth_hw)) != MPPI_OK) return st;
+    if (!occ_zyx_inout) return fail(MPPI_ERR_INVALID_ARG, "mppi_depth_integrate_host: null map");
+    DepthParams p;
+    depth_params(*desc, *view, p);
+    p.depth = depth_hw;
+    p.occ = occ_zyx_inout;
+    depth_integrate(p);
+    return MPPI_OK;
+}
+
+// mppi_integrate_depth's argument check alone (no GPU, no image): what a caller that queues frames for later
+// runs before it queues one (mppi_solver/_base.py).  Returns the first failing status.
+extern "C" int32_t mppi_debug_depth_validate(const mppi_field_desc* desc, const mppi_depth_view* view, float max_dist) {
+    mppi_status st = field_validate(desc);
+    if (st != MPPI_OK) return st;
+    static const float pixel = 0.0f;   // (the image is checked for null only)
+    if ((st = depth_validate(*desc, view, &pixel)) != MPPI_OK) return st;
+    if (std::isnan(max_dist) || (std::isinf(max_dist) && max_dist > 0.0f))
+        return fail(MPPI_ERR_INVALID_ARG, "depth: max_dist %g (a finite cap, or <= 0 for none)", max_dist);
+    return MPPI_OK;
+}
+
+// Diagnostic (no GPU): mppi_shift_map's map and origin on the host through k_map_shift's own inline: occ_zyx
+// (nz,ny,nx) in, out_zyx out (distinct arrays), origin_out the moved origin.  tests/test_capi_depth_cpu.py.
+extern "C" int32_t mppi_debug_map_shift(const mppi_field_desc* desc, const int32_t* shift_xyz, const uint8_t* occ_zyx,
+                                        uint8_t* out_zyx, float* origin_out) {
+    mppi_status st = field_validate(desc);
+    if (st != MPPI_OK) return st;
+    if (!occ_zyx || !out_zyx || !origin_out || occ_zyx == out_zyx) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_map_shift: bad arguments");
+    ShiftParams p;
+    if ((st = shift_validate(*desc, shift_xyz, 0.0f, p, origin_out)) != MPPI_OK) return st;
+    p.src = occ_zyx;
+    p.occ = out_zyx;
+    map_shift(p);
     return MPPI_OK;
 }
 

@@ -10,6 +10,7 @@
 #include "mppi_field.h"
 #include "mppi_self.h"
 #include "mppi_edt.h"
+#include "mppi_depth.h"
 
 // mppi_engine::generic with every part switched back (MPPI_GENERIC_KERNELS=1)
 constexpr int kGenericAll = 15;
@@ -121,6 +122,19 @@ mppi_status self_engine_validate(const mppi_config& c, const mppi_scene* scene, 
 // into d (nz, ny, nx) for a descriptor that passed field_validate.
 mppi_status occupancy_validate(const float* origin3, const uint8_t* occ_zyx, float max_dist);
 void occupancy_field(const mppi_field_desc& f, const uint8_t* occ_zyx, float max_dist, float* d_zyx);
+// ------------------------------------------------- depth images (mppi_layout.cpp; mppi_depth.h)
+// depth_validate: the errors of mppi_integrate_depth's view and image for a field of this descriptor.
+// depth_params: the kernels' parameters of a validated view -- the reciprocals and the rotation, formed
+// once here for both twins; the pointers are the caller's.
+// depth_integrate: the host twin of k_depth_carve and k_depth_mark through the same inlines (p.depth and
+// p.occ are host arrays); every node holds 0 or 1 afterwards.
+// shift_validate: the errors of mppi_shift_map's arguments; the moved origin in origin_out.
+// map_shift: the host twin of k_map_shift (p.src and p.occ host arrays).
+mppi_status depth_validate(const mppi_field_desc& f, const mppi_depth_view* view, const float* depth_hw);
+void depth_params(const mppi_field_desc& f, const mppi_depth_view& view, mppi::DepthParams& p);
+void depth_integrate(const mppi::DepthParams& p);
+mppi_status shift_validate(const mppi_field_desc& f, const int32_t* shift_xyz, float max_dist, mppi::ShiftParams& p, float* origin_out);
+void map_shift(const mppi::ShiftParams& p);
 // the MPPI_GENERIC_KERNELS bits (EngineLayout::generic) and what they set in dp and fp
 void set_generic(EngineLayout& l, int generic);
 

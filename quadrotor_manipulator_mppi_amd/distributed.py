@@ -438,6 +438,19 @@ class ShardedEngine:
         the same map, as for set_distance_field."""
         self.engine.set_occupancy(occ, origin, max_dist)
 
+    def integrate_depth(self, depth, view, max_dist=None):
+        """One depth image into this rank's engine's map (Engine.integrate_depth).  Every rank holds the
+        whole world, so every rank integrates the same image."""
+        self.engine.integrate_depth(depth, view, max_dist)
+
+    def shift_map(self, shift, max_dist=None):
+        """This rank's engine's map window moved (Engine.shift_map): the same shift on every rank."""
+        self.engine.shift_map(shift, max_dist)
+
+    def get_occupancy(self):
+        """This rank's engine's occupancy map (Engine.get_occupancy): the same on every rank."""
+        return self.engine.get_occupancy()
+
     def get_distance_field(self):
         """This rank's engine's field (Engine.get_distance_field): the same on every rank."""
         return self.engine.get_distance_field()

@@ -238,6 +238,78 @@ class DistanceField:
         return f
 
 
+@dataclass
+class DepthView:
+    """One depth image's camera (mppi_depth_view): the pinhole intrinsics in pixels, the range gate, the
+    pose of the optical frame (z forward, x right, y down) in the world, and which pixels are used (rows
+    and columns 0, stride, 2 stride, ...).  ``carve=False`` marks end points only."""
+    width: int
+    height: int
+    fx: float
+    fy: float
+    cx: float
+    cy: float
+    pos: Sequence[float] = (0.0, 0.0, 0.0)
+    quat_xyzw: Sequence[float] = (0.0, 0.0, 0.0, 1.0)
+    z_min: float = 0.1
+    z_max: float = 5.0
+    stride: int = 1
+    carve: bool = True
+
+    def to_c(self) -> capi.DepthViewC:
+        c = capi.DepthViewC()
+        c.width, c.height, c.stride, c.carve = int(self.width), int(self.height), int(self.stride), int(bool(self.carve))
+        c.fx, c.fy, c.cx, c.cy = float(self.fx), float(self.fy), float(self.cx), float(self.cy)
+        c.z_min, c.z_max = float(self.z_min), float(self.z_max)
+        pos, quat = np.asarray(self.pos, np.float64).reshape(3), np.asarray(self.quat_xyzw, np.float64).reshape(4)
+        c.pos[:] = [float(x) for x in pos]
+        c.quat_xyzw[:] = [float(x) for x in quat]
+        return c
+
+    def validate(self, field: "DistanceField", max_dist=None) -> None:
+        """Raises what ``Engine.integrate_depth`` would raise for this view on an engine with ``field``
+        (mppi_integrate_depth's argument check, without a device or an image)."""
+        f = capi.lib().mppi_debug_depth_validate
+        f.restype, f.argtypes = capi.DEBUG_PROTOTYPES["mppi_debug_depth_validate"]
+        desc, v = field.to_c(), self.to_c()
+        capi.check(f(C.byref(desc), C.byref(v), 0.0 if max_dist is None else float(max_dist)), "integrate_depth")
+
+    def check_image(self, depth) -> np.ndarray:
+        """``depth`` as the (height, width) float32 metres the library takes."""
+        d = np.ascontiguousarray(depth, np.float32)
+        if d.shape != (int(self.height), int(self.width)):
+            raise ValueError(f"depth image {d.shape}, expected (height, width) = {(int(self.height), int(self.width))}")
+        return d
+
+    @staticmethod
+    def from_camera_info(K, width, height, pos=(0.0, 0.0, 0.0), quat_xyzw=(0.0, 0.0, 0.0, 1.0), z_min=0.1, z_max=5.0,
+                         stride=1, carve=True) -> "DepthView":
+        """From a ``sensor_msgs/CameraInfo``'s K (9 values, row major): fx = K[0], fy = K[4], cx = K[2], cy = K[5]."""
+        K = np.asarray(K, np.float64).reshape(9)
+        return DepthView(int(width), int(height), float(K[0]), float(K[4]), float(K[2]), float(K[5]), tuple(pos),
+                         tuple(quat_xyzw), float(z_min), float(z_max), int(stride), bool(carve))
+
+
+def check_shift(shift):
+    """``shift`` as three ints that fit mppi_shift_map's int32 (a value outside would wrap to another shift)."""
+    s = [int(x) for x in shift]
+    if len(s) != 3 or any(x < -2 ** 31 or x > 2 ** 31 - 1 for x in s):
+        raise ValueError(f"shift {tuple(s)}: three node counts (sx, sy, sz) within int32")
+    return s
+
+
+def depth_integrate_host(field: "DistanceField", occ, depth, view: DepthView) -> np.ndarray:
+    """One depth image into an occupancy map on the host (mppi_depth_integrate_host): what
+    ``Engine.integrate_depth`` does to the device map, bit for bit, without a device.  ``occ`` (nz, ny, nx)
+    bool or uint8 is not modified; the new map is returned as uint8 0 / 1."""
+    out = field.check_occupancy(occ).copy()
+    d = view.check_image(depth)
+    desc, v = field.to_c(), view.to_c()
+    capi.check(capi.lib().mppi_depth_integrate_host(C.byref(desc), C.byref(v), capi.fptr(d),
+                                                    out.ctypes.data_as(C.POINTER(C.c_uint8))), "mppi_depth_integrate_host")
+    return out
+
+
 def fill_joints(cfg: capi.Config, chain: Sequence[Dict]) -> None:
     if len(chain) > capi.MAX_JOINTS:
         raise ValueError(f"chain has {len(chain)} joints (max {capi.MAX_JOINTS})")
@@ -668,6 +740,34 @@ class Engine:
         o = None if origin is None else np.ascontiguousarray(origin, np.float32).reshape(3)
         capi.check(self._L.mppi_set_occupancy(self._h, capi.fptr(o), occ.ctypes.data_as(C.POINTER(C.c_uint8)),
                                               0.0 if max_dist is None else float(max_dist)), "set_occupancy")
+
+    def integrate_depth(self, depth, view: DepthView, max_dist=None):
+        """One depth image into a field engine's occupancy map, on the device (mppi_integrate_depth):
+        ``depth`` (height, width) float32 metres along the optical axis, ``view`` its camera.  Free space
+        along the rays is carved, the returns' end points are marked, and the field is rebuilt from the map
+        under ``max_dist`` (None: no cap).  Takes effect on the next step."""
+        if self.field is None:
+            raise RuntimeError("engine created without a field (Engine(cfg, field=DistanceField(...)))")
+        d, v = view.check_image(depth), view.to_c()
+        capi.check(self._L.mppi_integrate_depth(self._h, C.byref(v), capi.fptr(d),
+                                                0.0 if max_dist is None else float(max_dist)), "integrate_depth")
+
+    def shift_map(self, shift, max_dist=None):
+        """Moves the map's window by ``shift`` = (sx, sy, sz) nodes (mppi_shift_map): new node (ix, iy, iz) is
+        old node (ix + sx, iy + sy, iz + sz), free where that falls outside; the origin moves by shift * voxel."""
+        if self.field is None:
+            raise RuntimeError("engine created without a field (Engine(cfg, field=DistanceField(...)))")
+        s = (C.c_int32 * 3)(*check_shift(shift))
+        capi.check(self._L.mppi_shift_map(self._h, s, 0.0 if max_dist is None else float(max_dist)), "shift_map")
+
+    def get_occupancy(self) -> np.ndarray:
+        """The occupancy map as it stands on the device, (nz, ny, nx) uint8 0 / 1 (all free before the first
+        ``set_occupancy``, ``integrate_depth`` or ``shift_map``)."""
+        if self.field is None:
+            raise RuntimeError("engine created without a field (Engine(cfg, field=DistanceField(...)))")
+        occ = np.empty(self.field.shape, np.uint8)
+        capi.check(self._L.mppi_get_occupancy(self._h, occ.ctypes.data_as(C.POINTER(C.c_uint8))), "get_occupancy")
+        return occ
 
     def get_distance_field(self):
         """``(d, origin)``: the field as it stands on the device, (nz, ny, nx) float32 and (3,) -- what the

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import _capi as capi
-from ..engine import Engine, Scene, SelfCollision, cost_term_bits, make_config
+from ..engine import Engine, Scene, SelfCollision, check_shift, cost_term_bits, make_config
 
 
 class OutputRing:
@@ -51,6 +51,10 @@ class OutputRing:
         self._events[i].record()
         self._used[i] = True
         return t
+
+
+class _Cleared:
+    """SolverBase._field_data after clear_distance_field: cleared, and distinct from the clear before it."""
 
 
 class SolverBase:
@@ -120,6 +124,11 @@ class SolverBase:
             return e
         u = self._u_prev_host if e is None else e.get_u_prev()[0]
         if e is not None:
+            sent = self._field_sent
+            if self._field is not None and self._map_live and sent is not None and sent[0] is e and sent[1] is self._field_data:
+                # the map built on the device moves to the new engine (nothing newer from the user waits)
+                fd = e.get_distance_field()
+                self._field_data = (e.get_occupancy(), None if fd is None else fd[1], self._map_max_dist)
             e.close()
         cfg = self._config(key)
         scene = Scene.default(cfg) if self._scene is True else self._scene
@@ -261,6 +270,56 @@ class SolverBase:
         o = None if origin is None else np.ascontiguousarray(origin, np.float32).reshape(3).copy()
         self._field_data = (self._field.check_occupancy(occ).copy(), o, max_dist)
 
+    # The engine's occupancy map (Engine.integrate_depth, shift_map, get_occupancy) lives on the device.  Map
+    # calls made before the first control call has made the engine wait in _map_ops and run, in order, right
+    # after the field data is written.  A call is checked before it is queued (the view and max_dist by
+    # mppi_integrate_depth's own argument check, the shift's range here), and an op leaves the queue before
+    # it runs: one the engine still refuses raises once, to whoever synchronises next, and is gone -- the ops
+    # behind it run at the next synchronise, none runs twice.  When a new engine replaces the old one, the
+    # old one's map goes with it as an occupancy grid (_ensure_engine) as long as the map is what the field
+    # was last built from: a set_distance_field, set_occupancy or clear_distance_field made since wins.
+    _map_ops = ()          # pending (name, args) map calls
+    _map_live = False      # the engine's map holds more than _field_data says
+    _map_max_dist = None
+
+    def _map_call(self, name, *args) -> None:
+        with self._lock:
+            self._map_ops = tuple(self._map_ops) + ((name, args),)
+            if self._engine is not None:
+                self._sync_field(self._engine)
+
+    @staticmethod
+    def _check_max_dist(max_dist) -> None:
+        if max_dist is not None and (np.isnan(max_dist) or max_dist == np.inf):
+            raise ValueError(f"max_dist {max_dist}: a finite cap, or None / <= 0 for none")
+
+    def integrate_depth(self, depth, view, max_dist=None) -> None:
+        """One depth image into the occupancy map, on the device (``Engine.integrate_depth``): ``depth``
+        (height, width) float32 metres, ``view`` an ``engine.DepthView``.  Used from the next control call on.
+        A view or ``max_dist`` the engine would refuse raises here and nothing is queued."""
+        if self._field is None:
+            raise RuntimeError("integrate_depth needs field=... at construction")
+        view.validate(self._field, max_dist)
+        self._map_call("integrate_depth", view.check_image(depth).copy(), view, max_dist)
+
+    def shift_map(self, shift, max_dist=None) -> None:
+        """Moves the map's window by ``shift`` nodes (``Engine.shift_map``)."""
+        if self._field is None:
+            raise RuntimeError("shift_map needs field=... at construction")
+        self._check_max_dist(max_dist)
+        self._map_call("shift_map", tuple(check_shift(shift)), max_dist)
+
+    def get_occupancy(self):
+        """The occupancy map the engine holds (``Engine.get_occupancy``), or None before the first control
+        call has made the engine."""
+        if self._field is None:
+            raise RuntimeError("get_occupancy needs field=... at construction")
+        with self._lock:
+            if self._engine is None:
+                return None
+            self._sync_field(self._engine)
+            return self._engine.get_occupancy()
+
     def get_distance_field(self):
         """``(d, origin)`` of the field the engine holds (``Engine.get_distance_field``), or None while it
         is cleared or before the first control call has made the engine."""
@@ -274,7 +333,7 @@ class SolverBase:
     def clear_distance_field(self) -> None:
         if self._field is None:
             raise RuntimeError("clear_distance_field needs field=... at construction")
-        self._field_data = None
+        self._field_data = _Cleared()   # (a fresh object: a clear after map calls built a field is a change too)
 
     def _init_field(self, field) -> None:
         self._field = field
@@ -285,13 +344,18 @@ class SolverBase:
             return
         data, sent = self._field_data, self._field_sent
         if sent is None or sent[0] is not eng or sent[1] is not data:
-            if data is None:
+            if data is None or isinstance(data, _Cleared):
                 eng.clear_distance_field()
             elif len(data) == 3:   # (occ, origin, max_dist) of set_occupancy
                 eng.set_occupancy(*data)
             else:
                 eng.set_distance_field(*data)
             self._field_sent = (eng, data)
+            self._map_live = False
+        while self._map_ops:
+            (name, args), self._map_ops = self._map_ops[0], tuple(self._map_ops[1:])   # (gone before it can raise)
+            getattr(eng, name)(*args)
+            self._map_live, self._map_max_dist = True, args[-1]
 
     def _sync_obstacles(self, eng: Engine) -> None:
         self._sync_field(eng)

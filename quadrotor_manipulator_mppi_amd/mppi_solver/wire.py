@@ -158,6 +158,118 @@ class Float64MultiArray:
         return m
 
 
+def _header(h: Header) -> bytes:
+    return struct.pack("<III", h.seq & 0xFFFFFFFF, h.secs & 0xFFFFFFFF, h.nsecs & 0xFFFFFFFF) + _string(h.frame_id)
+
+
+def _read_header(r: _Reader) -> Header:
+    seq, secs, nsecs = r.u32(), r.u32(), r.u32()
+    return Header(seq, secs, nsecs, r.string())
+
+
+@dataclass
+class Image:
+    """sensor_msgs/Image: Header, uint32 height, width, string encoding, uint8 is_bigendian, uint32 step
+    (bytes per row), uint8[] data.  The depth camera's topic (``depth_from_image``)."""
+    header: Header = field(default_factory=Header)
+    height: int = 0
+    width: int = 0
+    encoding: str = ""
+    is_bigendian: int = 0
+    step: int = 0
+    data: bytes = b""
+
+    def serialize(self) -> bytes:
+        data = bytes(self.data)
+        return (_header(self.header) + struct.pack("<II", self.height, self.width) + _string(self.encoding)
+                + struct.pack("<BI", self.is_bigendian & 0xFF, self.step) + struct.pack("<I", len(data)) + data)
+
+    @classmethod
+    def deserialize(cls, buf: bytes) -> "Image":
+        r = _Reader(buf)
+        hdr = _read_header(r)
+        height, width = r.u32(), r.u32()
+        enc = r.string()
+        big = struct.unpack_from("<B", r.take(1))[0]
+        step = r.u32()
+        m = cls(hdr, height, width, enc, big, step, bytes(r.take(r.u32())))
+        r.done()
+        return m
+
+
+@dataclass
+class CameraInfo:
+    """sensor_msgs/CameraInfo: Header, uint32 height, width, string distortion_model, float64[] D,
+    float64[9] K, float64[9] R, float64[12] P, uint32 binning_x, binning_y, RegionOfInterest roi (uint32
+    x_offset, y_offset, height, width, bool do_rectify).  ``engine.DepthView.from_camera_info`` takes K."""
+    header: Header = field(default_factory=Header)
+    height: int = 0
+    width: int = 0
+    distortion_model: str = ""
+    D: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    K: np.ndarray = field(default_factory=lambda: np.zeros(9))
+    R: np.ndarray = field(default_factory=lambda: np.zeros(9))
+    P: np.ndarray = field(default_factory=lambda: np.zeros(12))
+    binning_x: int = 0
+    binning_y: int = 0
+    roi: Tuple[int, int, int, int, bool] = (0, 0, 0, 0, False)
+
+    @staticmethod
+    def _fixed(x, n: int, name: str) -> bytes:
+        a = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1), dtype="<f8")
+        if a.size != n:
+            raise WireError(f"CameraInfo.{name} has {a.size} values, the message holds {n}")
+        return a.tobytes()
+
+    def serialize(self) -> bytes:
+        x, y, h, w, rect = self.roi
+        return (_header(self.header) + struct.pack("<II", self.height, self.width) + _string(self.distortion_model)
+                + _f64_array(self.D) + self._fixed(self.K, 9, "K") + self._fixed(self.R, 9, "R")
+                + self._fixed(self.P, 12, "P") + struct.pack("<II", self.binning_x, self.binning_y)
+                + struct.pack("<IIIIB", x, y, h, w, 1 if rect else 0))
+
+    @classmethod
+    def deserialize(cls, buf: bytes) -> "CameraInfo":
+        r = _Reader(buf)
+        hdr = _read_header(r)
+        height, width = r.u32(), r.u32()
+        model = r.string()
+        D = r.f64_array()
+        K, R, P = (np.frombuffer(r.take(8 * n), dtype="<f8").astype(np.float64) for n in (9, 9, 12))
+        bx, by = r.u32(), r.u32()
+        x, y, h, w = r.u32(), r.u32(), r.u32(), r.u32()
+        rect = struct.unpack_from("<B", r.take(1))[0] != 0
+        m = cls(hdr, height, width, model, D, K, R, P, bx, by, (x, y, h, w, rect))
+        r.done()
+        return m
+
+
+def depth_from_image(msg: Image) -> np.ndarray:
+    """The (height, width) float32 depth in metres of a depth camera's ``Image``: ``32FC1`` holds metres,
+    ``16UC1`` millimetres with 0 for "no reading" (-> NaN: the pixel is skipped).  Row padding (``step``
+    beyond the row's bytes) is dropped.  Any other encoding, a big-endian image or a buffer shorter than
+    ``height * step`` raises ``WireError``."""
+    sizes = {"32FC1": ("<f4", 4), "16UC1": ("<u2", 2)}
+    if msg.encoding not in sizes:
+        raise WireError(f"depth image encoding {msg.encoding!r}: 32FC1 (metres) or 16UC1 (millimetres)")
+    if msg.is_bigendian:
+        raise WireError("big-endian depth image")
+    dtype, size = sizes[msg.encoding]
+    row = msg.width * size
+    if msg.height < 1 or msg.width < 1 or msg.step < row:
+        raise WireError(f"depth image {msg.height} x {msg.width} with step {msg.step} (a row holds {row} bytes)")
+    data = bytes(msg.data)
+    if len(data) < msg.height * msg.step:
+        raise WireError(f"short depth image: {len(data)} bytes, {msg.height} rows of {msg.step} need {msg.height * msg.step}")
+    rows = np.frombuffer(data, np.uint8, msg.height * msg.step).reshape(msg.height, msg.step)[:, :row]
+    px = np.ascontiguousarray(rows).view(dtype).reshape(msg.height, msg.width)
+    if msg.encoding == "32FC1":
+        return px.astype(np.float32)
+    out = px.astype(np.float32) * np.float32(1e-3)
+    out[px == 0] = np.nan
+    return out
+
+
 # ------------------------------------------------------ plugin-side layouts
 def robot_states(position_xyz, quat_xyzw, lin_vel, ang_rate, robot_q=None, robot_qdot=None,
                  seq: int = 0) -> JointState:
