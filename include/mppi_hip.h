@@ -687,6 +687,51 @@ mppi_status mppi_get_self_clearances(mppi_engine* e, float* sclr_vk);
  * MPPI_ERR_STATE on an engine not created by mppi_create_scene_self. */
 mppi_status mppi_get_plan_self_clearance(mppi_engine* e, float* sclr_vh);
 
+/* ---- Rotor limits: bounds on thrust and body torque in the QUADROTOR and AERIAL rollouts (every MPPI
+ * stack has control bounds; without them the optimum can be a plan the vehicle cannot fly).  DRONE, ARM
+ * and WHOLEBODY are MPPI_ERR_INVALID_ARG: their outputs are formed inside the finalize, which limits
+ * do not touch.
+ *
+ * Bounds lo[a] <= hi[a] on action dims a = 0..3 (thrust, tau_x, tau_y, tau_z), engine-wide.  Whether an
+ * engine has limits is fixed at creation; the values may be replaced at run time (a degraded rotor, a
+ * sagging battery).  -inf for lo and +inf for hi leave a side open; AERIAL's joint dims 4..10 are not
+ * bounded.  For sample k, row t, dim a, with u = u_prev[t][a] and eps as drawn or injected, every
+ * operation one fp32 operation, none fused with a neighbour:
+ *   a0   = fl(u + eps)
+ *   v'   = min(max(a0, lo), hi)
+ *   eps' = (a0 == v') ? eps : fl(v' - u)                        the effective noise
+ *   c    = (a0 == v') ? a0  : min(max(fl(u + eps'), lo), hi)    the control the dynamics integrate
+ * An unsaturated draw is untouched bit for bit; c lies within [lo, hi] always.  eps' replaces eps
+ * everywhere downstream of the draw: in the block records N = sum_k e_k eps'_k, in the stored noise
+ * (store_noise, mppi_get_noise) and in the kernels' noise tile.  So u_prev + sum_k w_k eps'_k =
+ * sum_k w_k v'_k, a convex combination of controls within the bounds, and the finalize is the plain
+ * engine's.  mppi_get_plan integrates c with eps = 0: the clamped warm start.
+ * u_prev itself stays the raw warm start of the reference's law, u_prev + SavGol(w_eps): the filter's
+ * negative taps can carry a row past a bound by a small amount; the next rollout clamps what it
+ * integrates.  The u0 that mppi_read_outputs and mppi_step return is clamped on the host, and the base's
+ * twelve outputs (formed on the host for these two models) are the first step under that clamped u0.
+ * An engine whose four bounds are all infinite equals the plain engine bit for bit: costs,
+ * trajectories, stored noise, u_prev and outputs.
+ * Runs the bounded kernels (k_rollout_quad_b, with MPPI_COST_TARGET_TRACK k_rollout_quad_tt_b,
+ * k_rollout_aerial_b; k_plan_quad_b, k_plan_aerial_b) on every step of a batch (no quiet form). */
+typedef struct { float lo[4], hi[4]; } mppi_limits;             /* thrust, tau_x, tau_y, tau_z */
+/* thrust in [0, 2 m g] from cfg's quad_mass and quad_gravity (fp32 product); the torques unbounded. */
+void mppi_limits_default(mppi_limits* lim, const mppi_config* cfg);
+/* mppi_create with limits (NULL limits: mppi_create).  MPPI_ERR_INVALID_ARG, with the dim or the model
+ * named in mppi_last_error: a NaN bound, lo > hi, the DRONE, ARM or WHOLEBODY model, shard_count > 1. */
+mppi_status mppi_create_limits(const mppi_config* cfg, const mppi_limits* limits, mppi_engine** out);
+/* Replaces the bounds: validated as at creation, copied to the engine's staging memory and uploaded on
+ * the engine's stream, ordered before the next step on either dispatch path.  MPPI_ERR_STATE on an
+ * engine not created with limits. */
+mppi_status mppi_set_limits(mppi_engine* e, const mppi_limits* limits);
+/* has: 1 on an engine created with limits (then *limits: the bounds as last set), else 0.  Either
+ * output may be NULL. */
+mppi_status mppi_get_limits(mppi_engine* e, int32_t* has, mppi_limits* limits);
+/* Host replay of the four lines above (csrc/mppi_limits.h, the kernels' own; no GPU): u (H,4), eps
+ * (K,H,4) into eps' (K,H,4) and c (K,H,4); either output may be NULL. */
+mppi_status mppi_limits_apply(const mppi_limits* limits, const float* u_h4, const float* eps_kh4, int32_t K, int32_t H,
+                              float* eps_eff_kh4, float* ctl_kh4);
+
 #define MPPI_MAX_ELITES 64
 /* The n lowest-cost samples of the last rollout of every vehicle, best first (synchronous).
  *   idx  (V,n) int32   sample index within this engine's K (a shard: local; global = shard_rank*K + idx)

@@ -95,6 +95,10 @@ class SelfCollision(C.Structure):
                 ("w_self", C.c_float), ("margin", C.c_float), ("penalty", C.c_float), ("reserved", C.c_int32)]
 
 
+class Limits(C.Structure):
+    _fields_ = [("lo", C.c_float * 4), ("hi", C.c_float * 4)]   # thrust, tau_x, tau_y, tau_z
+
+
 class Link(C.Structure):
     _fields_ = [("parent", C.c_int32), ("type", C.c_int32), ("xyz", C.c_double * 3), ("rpy", C.c_double * 3),
                 ("axis", C.c_double * 3), ("mass", C.c_double), ("com", C.c_double * 3),
@@ -186,6 +190,11 @@ PROTOTYPES = {
     "mppi_create_scene_self": (_ST, [_CFG, C.POINTER(Scene), C.POINTER(FieldDesc), C.POINTER(SelfCollision), C.POINTER(_P)]),
     "mppi_get_self_clearances": (_ST, [_P, _F]),
     "mppi_get_plan_self_clearance": (_ST, [_P, _F]),
+    "mppi_limits_default": (None, [C.POINTER(Limits), _CFG]),
+    "mppi_create_limits": (_ST, [_CFG, C.POINTER(Limits), C.POINTER(_P)]),
+    "mppi_set_limits": (_ST, [_P, C.POINTER(Limits)]),
+    "mppi_get_limits": (_ST, [_P, _I32, C.POINTER(Limits)]),
+    "mppi_limits_apply": (_ST, [C.POINTER(Limits), _F, _F, C.c_int32, C.c_int32, _F, _F]),
     "mppi_enable_timing": (_ST, [_P, C.c_int32]),
     "mppi_get_timing": (_ST, [_P, _D, _D, _I64, _I64]),
     "mppi_kernel_timing": (_ST, [_P, C.c_int32, _D, _D]),
@@ -224,6 +233,9 @@ DEBUG_PROTOTYPES = {
     "mppi_debug_self_step_launches": (C.c_int32, [_CFG, C.POINTER(Scene), C.POINTER(FieldDesc), C.POINTER(SelfCollision), _I32,
                                                   C.c_char_p, C.c_int32]),
     "mppi_debug_self_rollout_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_char_p, C.c_int32]),
+    "mppi_debug_limits_step_launches": (C.c_int32, [_CFG, C.POINTER(Limits), _I32, C.c_char_p, C.c_int32]),
+    "mppi_debug_limits_plan_kernel": (C.c_int32, [_I32, C.c_char_p, C.c_int32]),
+    "mppi_debug_limits_set": (C.c_int32, [_CFG, C.c_int32, C.POINTER(Limits)]),
     "mppi_debug_edt_kernels": (C.c_int32, [_I32, C.c_char_p, C.c_int32]),
     "mppi_debug_field_words": (C.c_int32, [_P, _F]),
     "mppi_debug_depth_validate": (C.c_int32, [C.POINTER(FieldDesc), C.POINTER(DepthViewC), C.c_float]),

@@ -46,7 +46,7 @@ SOURCES = [(u, f + (_MAXILP if u in _XI else [])) for u, f in
             ("mppi_rollout_wb.hip", _ROLL), ("mppi_rollout_sc.hip", _SELF), ("mppi_rollout_sf.hip", _SELF), ("mppi_finalize.hip", _FIN), ("mppi_plan.hip", ["-fno-slp-vectorize"]),
             ("mppi_elites.hip", []), ("mppi_edt.hip", []), ("mppi_depth.hip", [])]] + \
           [("mppi_rollout_arm_h32.hip", _ROLL + _MAXILP + os.environ.get("MPPI_C3_EXTRA", "").split()), ("mppi_rollout_quad.hip", _ROLL + _MAXILP),
-           ("mppi_rollout_aerial.hip", _ROLL),
+           ("mppi_rollout_aerial.hip", _ROLL), ("mppi_limits.hip", _ROLL),
            ("mppi_host_math.cpp", []), ("mppi_layout.cpp", []), ("mppi_engine.cpp", []), ("mppi_launches.cpp", []), ("mppi_step.cpp", []), ("mppi_debug.cpp", []),
            ("mppi_exchange.cpp", []),
            ("mppi_prewarm.cpp", []), ("mppi_dynamics.cpp", []), ("mppi_aql.cpp", [])]

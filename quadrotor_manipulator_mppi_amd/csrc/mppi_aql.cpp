@@ -97,7 +97,7 @@ std::map<int, Device> g_dev;
 
 const char* const kUnits[] = {"mppi_rollout_drone", "mppi_rollout_arm", "mppi_rollout_arm_h32", "mppi_rollout_arm32",
                               "mppi_rollout_wb", "mppi_rollout_sc", "mppi_rollout_sf",
-                              "mppi_rollout_quad", "mppi_rollout_aerial", "mppi_finalize"};
+                              "mppi_rollout_quad", "mppi_rollout_aerial", "mppi_limits", "mppi_finalize"};
 
 std::string hsa_msg(hsa_status_t s) {
     const char* m = nullptr;

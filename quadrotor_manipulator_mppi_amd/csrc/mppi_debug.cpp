@@ -22,9 +22,10 @@ std::string fin_symbol(const FinParams& f, LaunchDesc* desc) {
     if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
-std::string roll_symbol(const DevParams& p, int threads, LaunchDesc* desc, const float* ttab, float* scene, const float* field, int self_members) {
+std::string roll_symbol(const DevParams& p, int threads, LaunchDesc* desc, const float* ttab, float* scene, const float* field, int self_members,
+                        const float* limits) {
     LaunchDesc d{};
-    const int rc = describe(p, threads, &d, ttab, scene, field, self_members);
+    const int rc = describe(p, threads, &d, ttab, scene, field, self_members, limits);
     if (desc) *desc = d;
     return rc == 0 ? d.symbol : "?";
 }
@@ -274,11 +275,12 @@ int32_t mppi_debug_queue_ring(mppi_engine* e) {
 // why).  tests/test_capi_step_launches_cpu.py.
 static int32_t step_launches(const mppi_config* cfg, const int32_t* sw, char* buf, int32_t len, const mppi_scene* scene,
                              const mppi_field_desc* field = nullptr, uint64_t* field_arg = nullptr,
-                             const mppi_self_collision* self = nullptr) {
+                             const mppi_self_collision* self = nullptr, const mppi_limits* limits = nullptr) {
     if (!cfg || !sw || !buf || len <= 0 || sw[0] < 0 || sw[0] > 3 || sw[1] < 1)
         return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_step_launches: bad arguments");
     mppi_status st = validate(*cfg);
     if (st != MPPI_OK) return st;
+    if (limits && (st = limits_validate(*cfg, limits)) != MPPI_OK) return st;
     const auto eng = std::make_unique<mppi_engine>();
     mppi_engine* e = eng.get();
     if (self) {   // a self engine's (mppi_create_scene_self; with a scene): its block and its paired spheres
@@ -321,6 +323,11 @@ static int32_t step_launches(const mppi_config* cfg, const int32_t* sw, char* bu
         e->field = *field;
         e->d_field = (float*)stand_in(0x8000);
     }
+    if (limits) {   // a bounded engine's (mppi_create_limits): its limits buffer
+        e->has_limits = true;
+        e->limits = *limits;
+        e->d_limits = (float*)stand_in(0x9000);
+    }
     std::vector<VehicleConst> vc((size_t)e->V);
     e->h_vc = vc.data();
     e->tpos.assign((size_t)3 * e->V, 0.0f);
@@ -358,7 +365,7 @@ static int32_t step_launches(const mppi_config* cfg, const int32_t* sw, char* bu
         const StepPath sp = path < 2 ? StepPath::Hip : path == 2 ? StepPath::Batch : StepPath::Call;
         DevParams p = rollout_params(e, sp, noise, !last);
         if (sp == StepPath::Hip) p.step_ctr = (uint32_t)i;   // (rollout_impl: the launch's own)
-        report(last, "rollout", describe(p, e->threads, &d, e->d_ttab, e->d_scene, e->d_field, e->self_members), d);
+        report(last, "rollout", describe(p, e->threads, &d, e->d_ttab, e->d_scene, e->d_field, e->self_members, e->d_limits), d);
         if (field_arg) std::memcpy(field_arg, d.args + kRollFieldOff, sizeof(*field_arg));   // (the last rollout's)
         if (sp == StepPath::Hip && sharded(e)) {
             const FinParams f = finalize_params(e, FinKind::Pack);
@@ -432,6 +439,44 @@ int32_t mppi_debug_self_step_launches(const mppi_config* cfg, const mppi_scene* 
                                       const mppi_self_collision* self, const int32_t* sw, char* buf, int32_t len) {
     if (!scene || !self) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_self_step_launches: bad arguments");
     return step_launches(cfg, sw, buf, len, scene, field, nullptr, self);
+}
+
+// Likewise for an engine of mppi_create_limits(cfg, limits) (null limits: mppi_debug_step_launches); the stand-in
+// limits buffer is at 0x9000.  tests/test_capi_limits_cpu.py.
+int32_t mppi_debug_limits_step_launches(const mppi_config* cfg, const mppi_limits* limits, const int32_t* sw, char* buf,
+                                        int32_t len) {
+    return step_launches(cfg, sw, buf, len, nullptr, nullptr, nullptr, nullptr, limits);
+}
+
+// Diagnostic (no GPU): mppi_set_limits' status on an engine built on the host from layout_of -- a plain one (bounded
+// 0), or one marked bounded: the call's argument and state checks, which come before it touches a device (a
+// bounded engine with valid bounds would go on to the device: MPPI_OK is returned for it here without the call).
+int32_t mppi_debug_limits_set(const mppi_config* cfg, int32_t bounded, const mppi_limits* limits) {
+    if (!cfg) return fail(MPPI_ERR_INVALID_ARG, "mppi_debug_limits_set: bad arguments");
+    mppi_status st = validate(*cfg);
+    if (st != MPPI_OK) return st;
+    const auto eng = std::make_unique<mppi_engine>();
+    if ((st = layout_of(*cfg, *eng)) != MPPI_OK) return st;
+    eng->has_limits = bounded != 0;
+    if (eng->has_limits && limits_values_validate(limits) == MPPI_OK) return MPPI_OK;
+    return mppi_set_limits(eng.get(), limits);
+}
+
+// Likewise the bounded plan kernel (mppi_debug_plan_kernel's g): "<symbol> grid <blocks> block <threads>".
+int32_t mppi_debug_limits_plan_kernel(const int32_t* g, char* sym, int32_t len) {
+    if (!g || !sym || len <= 0) return MPPI_ERR_INVALID_ARG;
+    DevParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.model = g[0]; p.A = g[1]; p.H = g[2]; p.V = g[3]; p.state_f64 = g[4]; p.q_literal_jinv = g[5];
+    PlanParams pp;
+    std::memset(&pp, 0, sizeof(pp));
+    pp.self_members = -1;
+    static const float nowhere[kLimitsW] = {};   // described, not run: any non-null buffer
+    LaunchDesc d{};
+    {   const mppi_aql::Capture c(&d);
+        if (mppi_launch_plan_b(&p, &pp, nowhere, nullptr) != 0) return MPPI_ERR_INVALID_ARG; }
+    snprintf(sym, (size_t)len, "%s grid %u block %u", d.symbol, d.grid[0], d.block[0]);
+    return MPPI_OK;
 }
 
 static int32_t scene_rollout_kernels(const int32_t* g, char* full, char* quiet, int32_t len, bool field, int self_members = -1);

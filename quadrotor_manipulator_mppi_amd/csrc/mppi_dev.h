@@ -363,6 +363,11 @@ int mppi_launch_rollout_wb_df(const mppi::DevParams* p, const float* ttab, float
 // pair; field null: k_rollout_sc, else k_rollout_sf (mppi_rollout_sc.hip, mppi_rollout_sf.hip)
 int mppi_launch_rollout_self(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int members, int block_threads, void* stream);
 int mppi_launch_rollout_self_field(const mppi::DevParams* p, const float* ttab, float* scene, const float* field, int members, int block_threads, void* stream);
+// the bounded rollouts and plans (an engine of mppi_create_limits; mppi_limits.h): lim = the limits buffer, lo[4] then
+// hi[4]; ttab = the target table of a tracking QUADROTOR engine (k_rollout_quad_tt_b), else null (k_rollout_quad_b)
+int mppi_launch_rollout_quad_b(const mppi::DevParams* p, const float* ttab, const float* lim, int block_threads, void* stream);
+int mppi_launch_rollout_aerial_b(const mppi::DevParams* p, const float* lim, int block_threads, void* stream);
+int mppi_launch_plan_b(const mppi::DevParams* p, const mppi::PlanParams* pp, const float* lim, void* stream);
 int mppi_launch_finalize(const mppi::FinParams* p, void* stream);
 int mppi_launch_plan(const mppi::DevParams* p, const mppi::PlanParams* pp, void* stream);
 int mppi_launch_peer_probe(unsigned long long* const* peers, unsigned long long* local, int n, int me,

@@ -329,6 +329,11 @@ static mppi_status allocate(mppi_engine* e) {
         HIP_TRY(hipHostMalloc((void**)&e->h_field, bytes, hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&e->ev_field, hipEventDisableTiming));
     }
+    if (e->has_limits) {   // the limits buffer, its pinned staging copy, the uploads' event
+        HIP_TRY(hipMalloc(&e->d_limits, sizeof(float) * kLimitsW));
+        HIP_TRY(hipHostMalloc((void**)&e->h_limits, sizeof(float) * kLimitsW, hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&e->ev_limits, hipEventDisableTiming));
+    }
     if (c.cost_terms & ~MPPI_COST_TARGET_TRACK) {   // Sigma^-1, gamma^t, tracking target
         HIP_TRY(hipMalloc(&e->d_sinv, sizeof(float) * e->A * e->A));
         HIP_TRY(hipMalloc(&e->d_gamma, sizeof(float) * e->H));
@@ -349,6 +354,12 @@ static mppi_status allocate(mppi_engine* e) {
     if (e->overlap) HIP_TRY(hipMalloc(&e->d_ovl, (size_t)e->V * e->A * e->fin_ts * sizeof(uint32_t)));
     HIP_TRY(hipMalloc(&e->d_tail, sizeof(FinTail) * kTailSlots));
     return MPPI_OK;
+}
+
+// EngineLayout::limits into the pinned staging copy, in the buffer's order (mppi_limits.h: lo[4], hi[4])
+static void limits_stage(mppi_engine* e) {
+    std::memcpy(e->h_limits, e->limits.lo, sizeof(float) * kLimitsN);
+    std::memcpy(e->h_limits + kLimitsN, e->limits.hi, sizeof(float) * kLimitsN);
 }
 
 // the device pointers of dp and fp (layout_of left them null)
@@ -399,6 +410,11 @@ static mppi_status upload(mppi_engine* e) {
         HIP_TRY(hipMemcpy(e->d_field, e->h_field, sizeof(float) * (size_t)field_words(field_voxels(e->field)), hipMemcpyHostToDevice));
         e->batch.field = e->call.field = e->d_field;
     }
+    if (e->d_limits) {   // the bounds given at creation
+        limits_stage(e);
+        HIP_TRY(hipMemcpy(e->d_limits, e->h_limits, sizeof(float) * kLimitsW, hipMemcpyHostToDevice));
+        e->batch.limits = e->call.limits = e->d_limits;
+    }
     if (c.cost_terms & ~MPPI_COST_TARGET_TRACK) {
         HIP_TRY(hipMemcpy(e->d_sinv, e->sinv.data(), sizeof(float) * e->sinv.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(e->d_gamma, e->gamma_t.data(), sizeof(float) * e->gamma_t.size(), hipMemcpyHostToDevice));
@@ -417,7 +433,7 @@ static mppi_status upload(mppi_engine* e) {
 using namespace mppi_host;
 
 static mppi_status create_engine(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field, mppi_engine** out,
-                                 const mppi_self_collision* self = nullptr);
+                                 const mppi_self_collision* self = nullptr, const mppi_limits* limits = nullptr);
 
 extern "C" {
 
@@ -449,12 +465,46 @@ mppi_status mppi_create_scene_self(const mppi_config* cfg, const mppi_scene* sce
     return create_engine(cfg, &use, field, out, self);
 }
 
+// An engine with rotor limits (include/mppi_hip.h; NULL limits: mppi_create): QUADROTOR and AERIAL, the bounded kernels.
+mppi_status mppi_create_limits(const mppi_config* cfg, const mppi_limits* limits, mppi_engine** out) {
+    return create_engine(cfg, nullptr, nullptr, out, nullptr, limits);
+}
+
+// The bounds replaced: validated, staged and uploaded as a scene engine's obstacles are (mppi_set_obstacles:
+// stream-ordered before the next step on both dispatch paths).  The kernels reach the buffer through the
+// pointer fixed at creation, so no resident argument block changes.
+mppi_status mppi_set_limits(mppi_engine* e, const mppi_limits* limits) {
+    if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
+    if (!e->has_limits) return fail(MPPI_ERR_STATE, "engine created without limits (mppi_create_limits)");
+    const mppi_status st = limits_values_validate(limits);
+    if (st != MPPI_OK) return st;
+    if (use_device(e)) return MPPI_ERR_HIP;
+    if (e->limits_pending) {   // the previous copy out of the staging copy must be done
+        HIP_TRY(hipEventSynchronize(e->ev_limits));
+        e->limits_pending = false;
+    }
+    e->limits = *limits;
+    limits_stage(e);
+    HIP_TRY(hipMemcpyAsync(e->d_limits, e->h_limits, sizeof(float) * kLimitsW, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipEventRecord(e->ev_limits, e->stream));
+    e->limits_pending = true;
+    return MPPI_OK;
+}
+
+mppi_status mppi_get_limits(mppi_engine* e, int32_t* has, mppi_limits* limits) {
+    if (!e) return fail(MPPI_ERR_INVALID_ARG, "null engine");
+    if (has) *has = e->has_limits ? 1 : 0;
+    if (limits && e->has_limits) *limits = e->limits;
+    return MPPI_OK;
+}
+
 static mppi_status create_engine(const mppi_config* cfg, const mppi_scene* scene, const mppi_field_desc* field, mppi_engine** out,
-                                 const mppi_self_collision* self) {
+                                 const mppi_self_collision* self, const mppi_limits* limits) {
     if (!cfg || !out) return fail(MPPI_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     mppi_status st = validate(*cfg);
     if (st != MPPI_OK) return st;
+    if (limits && (st = limits_validate(*cfg, limits)) != MPPI_OK) return st;
     if (scene && (st = scene_validate(*cfg, *scene)) != MPPI_OK) return st;
     if (field && (st = field_validate(field)) != MPPI_OK) return st;
     if (self && !scene) return fail(MPPI_ERR_INVALID_ARG, "self: a self engine has a scene");
@@ -482,6 +532,10 @@ static mppi_status create_engine(const mppi_config* cfg, const mppi_scene* scene
     if (field) {
         lay.has_field = true;
         lay.field = *field;
+    }
+    if (limits) {
+        lay.has_limits = true;
+        lay.limits = *limits;
     }
 
     mppi_engine* e = new mppi_engine();
@@ -544,7 +598,7 @@ void mppi_destroy(mppi_engine* e) {
     void* dev[] = {e->d_xregion, e->d_xpeers, e->d_sigma, e->d_joints, e->d_vc, e->d_u_prev, e->d_noise_in, e->d_traj, e->d_noise_out,
                    e->d_S, e->d_hdr, e->d_rdata, e->d_out, e->d_wraw, e->d_wsmooth, e->d_w,
                    e->d_sinv, e->d_gamma, e->d_jtraj, e->d_ttab, e->d_scene, e->d_field, e->d_xown, e->d_tail, e->d_stamps, e->d_fstamps, e->d_xstall, e->d_ovl, e->d_xdec,
-                   e->d_plan_vc, e->d_plan, e->d_elite_cand, e->d_elites, e->d_edt, e->d_depth};
+                   e->d_plan_vc, e->d_plan, e->d_elite_cand, e->d_elites, e->d_edt, e->d_depth, e->d_limits};
     for (void* p : dev) if (p) (void)hipFree(p);
     if (e->h_out) (void)hipHostFree(e->h_out);
     if (e->h_vc) (void)hipHostFree(e->h_vc);
@@ -557,6 +611,8 @@ void mppi_destroy(mppi_engine* e) {
     if (e->h_depth) (void)hipHostFree(e->h_depth);
     if (e->ev_field) (void)hipEventDestroy(e->ev_field);
     if (e->h_elites) (void)hipHostFree(e->h_elites);
+    if (e->h_limits) (void)hipHostFree(e->h_limits);
+    if (e->ev_limits) (void)hipEventDestroy(e->ev_limits);
     if (e->ev_vc) (void)hipEventDestroy(e->ev_vc);
     if (e->ev_out) (void)hipEventDestroy(e->ev_out);
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -689,14 +745,14 @@ mppi_status mppi_kernel_timing_ex(mppi_engine* e, int32_t n, double* rollout_us,
     for (auto& x : ev) KT_TRY(hipEventCreate(&x));
     KT_TRY(hipMemcpyAsync(saved, e->d_u_prev, ub, hipMemcpyDeviceToDevice, e->stream));
     KT_TRY(hipEventRecord(ev[0], e->stream));
-    for (int i = 0; i < n && rc == 0; ++i) rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members);
+    for (int i = 0; i < n && rc == 0; ++i) rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members, e->d_limits);
     KT_TRY(hipEventRecord(ev[1], e->stream));
     for (int i = 0; i < n && rc == 0; ++i) rc = mppi_launch_finalize(&f, e->stream);
     KT_TRY(hipEventRecord(ev[2], e->stream));
     // the kernels as a control step runs them: rollout after finalize (u_prev and the
     // records just written, cold in the other XCDs' L2)
     for (int i = 0; i < n && rc == 0 && pair_us; ++i) {
-        rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members);
+        rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members, e->d_limits);
         if (rc == 0) rc = mppi_launch_finalize(&f, e->stream);
     }
     KT_TRY(hipEventRecord(ev[3], e->stream));
@@ -733,9 +789,9 @@ extern "C" mppi_status mppi_probe_sequence(mppi_engine* e, int32_t n, int32_t mo
     (void)hipEventCreate(&a); (void)hipEventCreate(&b);
     (void)hipEventRecord(a, e->stream);
     for (int i = 0; i < n; ++i) {
-        if (mode <= 2 || mode == 5) launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members);
+        if (mode <= 2 || mode == 5) launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members, e->d_limits);
         if (mode == 0 || mode == 3) mppi_launch_boundary((float*)e->d_out, fb, e->stream);
-        if (mode == 1 || mode == 4) launch_rollout(p1, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members);
+        if (mode == 1 || mode == 4) launch_rollout(p1, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members, e->d_limits);
         if (mode == 2) mppi_launch_finalize(&f, e->stream);
     }
     (void)hipEventRecord(b, e->stream);
@@ -1100,7 +1156,8 @@ mppi_status mppi_get_plan(mppi_engine* e, float* traj, float* cost_t, float* pos
     pp.self_members = e->self_members;
     pp.traj = e->d_plan; pp.cost_t = pp.traj + n_traj; pp.pos_err = pp.cost_t + n_vh; pp.S = pp.pos_err + n_vh;
     HIP_TRY(hipMemcpyAsync(e->d_plan_vc, e->h_vc, sizeof(VehicleConst) * V, hipMemcpyHostToDevice, e->stream));
-    const int rc = mppi_launch_plan(&e->dp, &pp, e->stream);
+    // (a bounded engine: the plan of the clamped warm start, mppi_plan.hip k_plan_quad_b / k_plan_aerial_b)
+    const int rc = e->d_limits ? mppi_launch_plan_b(&e->dp, &pp, e->d_limits, e->stream) : mppi_launch_plan(&e->dp, &pp, e->stream);
     if (rc != 0) return fail(MPPI_ERR_HIP, "plan launch failed (%d: %s)", rc,
                              rc > 0 ? hipGetErrorString((hipError_t)rc) : "no kernel for this model/A/H");
     // ONE copy of the block into pinned memory (each copy into the caller's pageable arrays cost

@@ -57,6 +57,7 @@ struct DescCache {
     float* scene = nullptr;        // a scene engine's buffer (likewise)
     const float* field = nullptr;  // a field engine's field buffer (likewise)
     int self_members = -1;         // a self engine's paired spheres (likewise; -1: not one)
+    const float* limits = nullptr; // a bounded engine's limits buffer (likewise)
     // ignore_vc0: the vehicle constants (the state) may differ -- a control call patches them in
     bool matches(const mppi::DevParams& p, const mppi::FinParams& f, int threads, bool ignore_vc0) const;
     // describes (p, f) and, where given, the quiet pair; the launchers' status (0: valid again)
@@ -136,6 +137,14 @@ struct mppi_engine : mppi_host::EngineLayout {
     float* h_field = nullptr;
     hipEvent_t ev_field = nullptr;
     bool field_pending = false;
+    // the rotor limits of a bounded engine (mppi_create_limits; else none): the device buffer (mppi_limits.h: lo[4],
+    // hi[4]) the bounded kernels reach through a pointer fixed at creation, its pinned staging copy and the event
+    // recorded behind the last upload (EngineLayout::limits: the bounds as last set)
+    float* d_limits = nullptr;
+    float* h_limits = nullptr;
+    hipEvent_t ev_limits = nullptr;
+    bool limits_pending = false;
+    std::vector<float> lim_u0;          // mppi_read_outputs: the step's u0 with its rotor dims clamped
     // mppi_set_occupancy's device scratch (allocated at its first call, for the field's dims: the two
     // int32 grids of the transform, then the occupancy bytes; mppi_edt.h edt_scratch_bytes)
     void* d_edt = nullptr;
@@ -312,8 +321,15 @@ inline int32_t quiet_roll_kern(int32_t kern, int generic, bool diag, bool peer, 
 // target table as an extra argument; every other launch is mppi_launch_rollout's.
 // A scene engine's (scene non-null) run the scene kernels, with or without the tracking bit.
 // A field engine's (field non-null, with its scene) run the field kernels.
+// A bounded engine's (limits non-null: its limits buffer; QUADROTOR and AERIAL, never a scene engine) run the
+// bounded kernels, QUADROTOR's with or without the tracking bit.
 inline int launch_rollout(const mppi::DevParams& p, const float* ttab, int threads, void* stream, float* scene = nullptr,
-                          const float* field = nullptr, int self_members = -1) {
+                          const float* field = nullptr, int self_members = -1, const float* limits = nullptr) {
+    if (limits) {
+        if (p.model == MPPI_MODEL_QUADROTOR)
+            return mppi_launch_rollout_quad_b(&p, (p.cost_terms & MPPI_COST_TARGET_TRACK) ? ttab : nullptr, limits, threads, stream);
+        return p.model == MPPI_MODEL_AERIAL ? mppi_launch_rollout_aerial_b(&p, limits, threads, stream) : -1;
+    }
     // a self engine's (self_members >= 0: the spheres that appear in a pair; with its scene) run the self kernels
     if (self_members >= 0) return mppi_launch_rollout_self(&p, ttab, scene, field, self_members, threads, stream);
     if (field) return mppi_launch_rollout_field(&p, ttab, scene, field, threads, stream);
@@ -322,7 +338,7 @@ inline int launch_rollout(const mppi::DevParams& p, const float* ttab, int threa
                                                    : mppi_launch_rollout(&p, threads, stream);
 }
 int describe(const mppi::DevParams& p, int threads, mppi::LaunchDesc* d, const float* ttab = nullptr, float* scene = nullptr,
-             const float* field = nullptr, int self_members = -1);
+             const float* field = nullptr, int self_members = -1, const float* limits = nullptr);
 int describe(const mppi::FinParams& f, mppi::LaunchDesc* d);
 // -------------------------------------------------------------- step (mppi_step.cpp)
 // why this engine's steps cannot go native (nullptr: they can).  A batch may carry the stamps /
@@ -334,7 +350,7 @@ const char* aql_ineligible(const mppi_engine* e, bool batch = false);
 // the symbol a launch would run, by the launchers' own description of it ("?": none)
 std::string fin_symbol(const mppi::FinParams& f, mppi::LaunchDesc* desc = nullptr);
 std::string roll_symbol(const mppi::DevParams& p, int threads, mppi::LaunchDesc* desc = nullptr, const float* ttab = nullptr,
-                        float* scene = nullptr, const float* field = nullptr, int self_members = -1);
+                        float* scene = nullptr, const float* field = nullptr, int self_members = -1, const float* limits = nullptr);
 
 // ------------------------------------------------------ exchange (mppi_exchange.cpp)
 // RCCL, resolved at the first mppi_comm_* call (dlopen: the library loads and its single-GPU

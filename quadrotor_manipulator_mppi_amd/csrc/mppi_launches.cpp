@@ -73,9 +73,10 @@ FinParams finalize_params(const mppi_engine* e, FinKind kind, StepPath path, boo
     return f;
 }
 
-int describe(const DevParams& p, int threads, LaunchDesc* d, const float* ttab, float* scene, const float* field, int self_members) {
+int describe(const DevParams& p, int threads, LaunchDesc* d, const float* ttab, float* scene, const float* field, int self_members,
+             const float* limits) {
     const mppi_aql::Capture c(d);
-    return launch_rollout(p, ttab, threads, nullptr, scene, field, self_members);
+    return launch_rollout(p, ttab, threads, nullptr, scene, field, self_members, limits);
 }
 int describe(const FinParams& f, LaunchDesc* d) {
     const mppi_aql::Capture c(d);
@@ -98,7 +99,8 @@ int DescCache::refresh(const DevParams& p_, const FinParams& f_, int threads_, c
                        const FinParams* f_quiet) {
     valid = false;
     int rc;
-    if ((rc = describe(p_, threads_, &roll, ttab, scene, field, self_members)) != 0 || (p_quiet && (rc = describe(*p_quiet, threads_, &roll_quiet, ttab, scene, field, self_members)) != 0) ||
+    if ((rc = describe(p_, threads_, &roll, ttab, scene, field, self_members, limits)) != 0 ||
+        (p_quiet && (rc = describe(*p_quiet, threads_, &roll_quiet, ttab, scene, field, self_members, limits)) != 0) ||
         (rc = describe(f_, &fin)) != 0 || (f_quiet && (rc = describe(*f_quiet, &fin_quiet)) != 0))
         return rc;
     p = p_;

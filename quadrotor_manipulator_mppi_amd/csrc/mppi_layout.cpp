@@ -607,6 +607,30 @@ void map_shift(const ShiftParams& p) {
     for (int64_t e = 0; e < nvox; ++e) p.occ[e] = shift_value(p, e);
 }
 
+// ------------------------------------------------------------------ rotor limits
+static const char* const kLimitDims[kLimitsN] = {"thrust", "tau_x", "tau_y", "tau_z"};
+static const char* const kModelNames[] = {"DRONE", "ARM", "WHOLEBODY", "QUADROTOR", "AERIAL"};
+
+mppi_status limits_values_validate(const mppi_limits* lim) {
+    if (!lim) return fail(MPPI_ERR_INVALID_ARG, "limits: null argument");
+    for (int a = 0; a < kLimitsN; ++a) {
+        if (std::isnan(lim->lo[a]) || std::isnan(lim->hi[a]))
+            return fail(MPPI_ERR_INVALID_ARG, "limits: dim %d (%s) has a NaN bound", a, kLimitDims[a]);
+        if (lim->lo[a] > lim->hi[a])
+            return fail(MPPI_ERR_INVALID_ARG, "limits: dim %d (%s) has lo %g > hi %g", a, kLimitDims[a], lim->lo[a], lim->hi[a]);
+    }
+    return MPPI_OK;
+}
+
+mppi_status limits_validate(const mppi_config& c, const mppi_limits* lim) {
+    if (c.model != MPPI_MODEL_QUADROTOR && c.model != MPPI_MODEL_AERIAL)
+        return fail(MPPI_ERR_INVALID_ARG, "limits need the QUADROTOR or AERIAL model (the %s model's outputs are formed in "
+                    "the finalize, which limits do not touch)", kModelNames[c.model]);
+    if (c.shard_count > 1)
+        return fail(MPPI_ERR_INVALID_ARG, "limits: bounded engines are not sharded (shard_count %d)", c.shard_count);
+    return limits_values_validate(lim);
+}
+
 void set_generic(EngineLayout& l, int generic) {
     l.generic = generic;
     l.fp.kern = (generic & 1) ? kFinKernGeneric : 0;
@@ -632,6 +656,34 @@ extern "C" void mppi_scene_default(mppi_scene* s, const mppi_config* cfg) {
     if (cfg->model != MPPI_MODEL_DRONE)
         for (int j = 0; j < cfg->n_joints && j < MPPI_MAX_JOINTS; ++j)
             if (cfg->joints[j].type != MPPI_JOINT_FIXED) add(j, 0.05f);
+}
+
+// The default rotor limits (include/mppi_hip.h): thrust within [0, 2 m g] (the fp32 product of quad_mass and
+// quad_gravity, doubled), the torques unbounded.
+extern "C" void mppi_limits_default(mppi_limits* lim, const mppi_config* cfg) {
+    if (!lim) return;
+    for (int a = 0; a < kLimitsN; ++a) { lim->lo[a] = -INFINITY; lim->hi[a] = INFINITY; }
+    if (!cfg) return;
+    lim->lo[0] = 0.0f;
+    lim->hi[0] = 2.0f * (cfg->quad_mass * cfg->quad_gravity);
+}
+
+// Host replay of the limits' arithmetic (include/mppi_hip.h): the kernels' own inline over u (H,4), eps (K,H,4).
+extern "C" mppi_status mppi_limits_apply(const mppi_limits* lim, const float* u_h4, const float* eps_kh4, int32_t K, int32_t H,
+                                         float* eps_eff_kh4, float* ctl_kh4) {
+    const mppi_status st = limits_values_validate(lim);
+    if (st != MPPI_OK) return st;
+    if (!u_h4 || !eps_kh4 || K < 0 || H < 0) return fail(MPPI_ERR_INVALID_ARG, "mppi_limits_apply: bad arguments");
+    for (int64_t k = 0; k < K; ++k)
+        for (int64_t t = 0; t < H; ++t)
+            for (int a = 0; a < kLimitsN; ++a) {
+                const int64_t i = (k * H + t) * kLimitsN + a;
+                float e, c;
+                mppi::limits_apply(u_h4[t * kLimitsN + a], eps_kh4[i], lim->lo[a], lim->hi[a], e, c);
+                if (eps_eff_kh4) eps_eff_kh4[i] = e;
+                if (ctl_kh4) ctl_kh4[i] = c;
+            }
+    return MPPI_OK;
 }
 
 // The project's default pair list (include/mppi_hip.h; the Python twin's weights: robot/body_spheres.py):

@@ -8,6 +8,7 @@
 #include "mppi_dev.h"
 #include "mppi_obstacles.h"
 #include "mppi_field.h"
+#include "mppi_limits.h"
 #include "mppi_self.h"
 #include "mppi_edt.h"
 #include "mppi_depth.h"
@@ -60,6 +61,8 @@ struct EngineLayout {
     bool has_self = false;              // mppi_create_scene_self (with has_scene): the self kernels; the pair region's
     std::vector<float> self_region;     // header and tables (kSelfHdrW words) and the spheres that appear in a pair
     int self_members = -1;              // (the centre column's rows; -1: not a self engine)
+    bool has_limits = false;            // mppi_create_limits: the bounded kernels; the bounds as last set (mppi_limits.h)
+    mppi_limits limits{};
     int auto_threads = 512;             // the block of a configuration with block_threads = 0 (a self engine: self_layout)
     int fin_ts = 1, fin_tsz = 8;        // finalize t-slices
     int generic = 0;                    // MPPI_GENERIC_KERNELS=1 (tests, A/B): the kernels as before the role and
@@ -84,6 +87,12 @@ mppi_status scene_validate(const mppi_config& c, const mppi_scene& s);
 void scene_body_table(const EngineLayout& l, const mppi_scene& s, float* table, int* order);
 mppi_status obstacles_validate(int n_vehicles, int vehicle, int n, const float* center, const float* radius, const float* vel);
 void obstacles_fill(float* block, int n, const float* center, const float* radius, const float* vel);
+// ------------------------------------------------- rotor limits (mppi_layout.cpp; mppi_limits.h)
+// limits_values_validate: the errors of mppi_set_limits' bounds (a NaN, lo > hi; the message names the dim).
+// limits_validate: those of mppi_create_limits, for a configuration that passed validate(): the models whose
+// outputs the finalize forms (named), a shard, then the bounds.
+mppi_status limits_values_validate(const mppi_limits* lim);
+mppi_status limits_validate(const mppi_config& c, const mppi_limits* lim);
 // ------------------------------------------------- the distance field (mppi_layout.cpp; mppi_field.h)
 // field_validate: the descriptor's errors of mppi_create_scene_field (the model's are scene_validate's).
 // field_data_validate: those of mppi_set_distance_field's arrays (either may be null).

@@ -41,6 +41,7 @@
 #include <type_traits>
 
 #include "mppi_diag.h"
+#include "mppi_limits.h"
 #include "mppi_noise.h"
 #include "mppi_quad_step.h"
 #include "mppi_stores.h"
@@ -77,14 +78,20 @@ __device__ __forceinline__ float qsum(float x) {
 // (H, 3) position rows of the vehicle's target table go into LDS with the noise tile in phase 1
 // ([H+1][4] floats after u_prev), and the dynamics wave reads its axis' target one step ahead, as it
 // reads u_t and the eps row, so the LDS latency stays off the serial chain.
-template <bool VONE, bool LIT, int NWD, int NT, bool QUIET, bool TRK = false>
+// LIM (k_rollout_quad_b, k_rollout_quad_tt_b; mppi_create_limits): the rotor limits (mppi_limits.h).  Phase 1 reads
+// u_prev[t] beside each draw and leaves the effective noise eps' in the tile and in the stored noise, so the
+// record is formed from eps' with no further work; the dynamics wave clamps the sum of its two LDS operands once
+// more (one v_med3_f32 per control: the identity on an unsaturated draw).  The thrust bounds stay in SGPRs.
+template <bool VONE, bool LIT, int NWD, int NT, bool QUIET, bool TRK = false, bool LIM = false>
 __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const uint32_t seed_hi,
                                                   const uint32_t step_arg, const uint32_t k_off,
                                                   const int32_t noise_arg, const int32_t H,
                                                   const float* __restrict__ u_prev, const DevParams& pk,
-                                                  const float* __restrict__ ttab = nullptr) {
+                                                  const float* __restrict__ ttab = nullptr,
+                                                  const float* __restrict__ lim = nullptr) {
     static_assert(NWD == 1 || NWD == kQWaves, "dynamics waves per block");
     static_assert(!TRK || !QUIET, "the tracking body has no quiet form");
+    static_assert(!LIM || !QUIET, "the bounded body has no quiet form");
     constexpr bool kTraj = !QUIET && !(MPPI_KO & 16), kCosts = !QUIET && !(MPPI_KO & 1024),
                    kHand = !QUIET && !(MPPI_KO & 2048);
     static_assert(NT == kQThreads || (NWD == 1 && NT == kQThreadsWide), "block size");
@@ -132,6 +139,11 @@ __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const 
                       "+s"(v6[0]), "+s"(v6[1]), "+s"(v6[2]), "+s"(v6[3]), "+s"(v6[4]), "+s"(v6[5]),
                       "+s"(tg3[0]), "+s"(tg3[1]), "+s"(tg3[2]), "+s"(ii3[0]), "+s"(ii3[1]), "+s"(ii3[2]),
                       "+s"(sdt), "+s"(sim), "+s"(skd), "+s"(sg), "+s"(swsp), "+s"(swtp), "+s"(scoef));
+    float llo[kQA] = {0.0f, 0.0f, 0.0f, 0.0f}, lhi[kQA] = {0.0f, 0.0f, 0.0f, 0.0f};   // LIM: the bounds (wave-uniform)
+    if constexpr (LIM) {
+#pragma unroll
+        for (int a = 0; a < kQA; ++a) { llo[a] = uniform_f32(lim[a]); lhi[a] = uniform_f32(lim[kLimitsN + a]); }
+    }
     for (int i = tid; i < QR * H; i += NT) {
         // rollouts past K replicate sample K-1 (noise and all): their lanes then compute and
         // store exactly K-1's values, so the dynamics need no store masks; weight 0 below
@@ -156,6 +168,16 @@ __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const 
                     for (int a = 0; a < kQA; ++a) e += z[a] * p.sigma[a * kQA + c];
                     eps[c] = e;
                 }
+            }
+        }
+        if constexpr (LIM) {   // eps -> eps' against row t of the warm start (the previous finalize's; device scope)
+            float ur[kQA];
+#pragma unroll
+            for (int a = 0; a < kQA; ++a) ur[a] = ld_dev(up + t * kQA + a);
+#pragma unroll
+            for (int a = 0; a < kQA; ++a) {
+                float c;
+                limits_apply(ur[a], eps[a], llo[a], lhi[a], eps[a], c);
             }
         }
         float* dst = eps_t + t * kQPitch + r * kQA;
@@ -213,9 +235,12 @@ __device__ __forceinline__ void rollout_quad_body(const uint32_t seed_lo, const 
     float pu0 = urp[0], pe0 = rowp[0], pu1 = urp[1 + jj], pe1 = rowp[1 + jj];
     const float* tgp = tg_t + jj;
     float ptg = TRK ? tgp[0] : tg;
+    // LIM: this lane's torque bounds (the thrust's are llo[0], lhi[0] in every lane)
+    const float tlo = LIM ? axis(llo + 1) : 0.0f, thi = LIM ? axis(lhi + 1) : 0.0f;
     auto step = [&](const int t, auto first_c, auto last_c) {
         constexpr bool FIRST = decltype(first_c)::value, LAST = decltype(last_c)::value;
-        const float thr = pu0 + pe0, tau = pu1 + pe1;
+        float thr = pu0 + pe0, tau = pu1 + pe1;
+        if constexpr (LIM) { thr = limits_clamp(thr, llo[0], lhi[0]); tau = limits_clamp(tau, tlo, thi); }
         const float tgc = ptg;   // this step's target (TRK: row t, loaded a step ahead)
         rowp += kQPitch;
         urp += kQA;
@@ -329,6 +354,27 @@ __global__ void __launch_bounds__(NT) k_rollout_quad_tt(const uint32_t seed_lo, 
     rollout_quad_body<VONE, LIT, NWD, NT, false, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg, H, u_prev, pk, ttab);
 }
 
+// the bounded forms (new symbols): the limits buffer as an extra pointer before the trailing DevParams
+template <bool VONE, bool LIT, int NWD, int NT>
+__global__ void __launch_bounds__(NT) k_rollout_quad_b(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                              const uint32_t step_arg, const uint32_t k_off,
+                                                              const int32_t noise_arg, const int32_t H,
+                                                              const float* __restrict__ u_prev,
+                                                              const float* __restrict__ lim, const DevParams pk) {
+    rollout_quad_body<VONE, LIT, NWD, NT, false, false, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg, H, u_prev, pk,
+                                                              nullptr, lim);
+}
+template <bool VONE, bool LIT, int NWD, int NT>
+__global__ void __launch_bounds__(NT) k_rollout_quad_tt_b(const uint32_t seed_lo, const uint32_t seed_hi,
+                                                                 const uint32_t step_arg, const uint32_t k_off,
+                                                                 const int32_t noise_arg, const int32_t H,
+                                                                 const float* __restrict__ u_prev,
+                                                                 const float* __restrict__ ttab,
+                                                                 const float* __restrict__ lim, const DevParams pk) {
+    rollout_quad_body<VONE, LIT, NWD, NT, false, true, true>(seed_lo, seed_hi, step_arg, k_off, noise_arg, H, u_prev, pk,
+                                                             ttab, lim);
+}
+
 template <bool VONE, bool LIT, int NWD, int NT, bool QUIET>
 constexpr auto quad_kernel() {
     if constexpr (QUIET) return k_rollout_quad_q<VONE, LIT, NWD, NT>;
@@ -378,5 +424,25 @@ extern "C" int mppi_launch_rollout_quad_tt(const DevParams* p, const float* ttab
         static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
         return go(k, dim3(p->nb, p->V), dim3(nt()), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,
                   (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, ttab, *p);
+    });
+}
+
+// The bounded launch (an engine of mppi_create_limits): the same block shapes, the full kernel on every step;
+// with a target table the tracking form (LDS + the target rows).
+extern "C" int mppi_launch_rollout_quad_b(const DevParams* p, const float* ttab, const float* lim, int threads, void* stream) {
+    (void)threads;
+    hipStream_t s = (hipStream_t)stream;
+    if (!lim) return -1;
+    return launch_quad(p, ttab ? (p->H + 1) * 4 : 0, [&](auto vone, auto lit, auto nw, auto nt, size_t lds) {
+        if (ttab) {
+            const auto k = k_rollout_quad_tt_b<vone(), lit(), nw(), nt()>;
+            static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+            return go(k, dim3(p->nb, p->V), dim3(nt()), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,
+                      (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, ttab, lim, *p);
+        }
+        const auto k = k_rollout_quad_b<vone(), lit(), nw(), nt()>;
+        static_assert(arg_offset<2>(decltype(k)()) == kRollStepOff, "the step counter is the third argument");
+        return go(k, dim3(p->nb, p->V), dim3(nt()), lds, s, p->seed_lo, p->seed_hi, p->step_ctr,
+                  (uint32_t)p->k_offset, p->noise_mode, p->H, p->u_prev, lim, *p);
     });
 }

@@ -69,7 +69,7 @@ static mppi_status rollout_impl(mppi_engine* e, const float* d_noise, bool quiet
     p.step_ctr = e->step_ctr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (e->timing) { e0 = pool_event(e); e1 = pool_event(e); HIP_TRY(hipEventRecord(e0, e->stream)); }
-    int rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members);
+    int rc = launch_rollout(p, e->d_ttab, e->threads, e->stream, e->d_scene, e->d_field, e->self_members, e->d_limits);
     if (rc != 0) return fail(MPPI_ERR_HIP, "rollout launch failed (%d: %s)", rc,
                              rc > 0 ? hipGetErrorString((hipError_t)rc) : "no kernel for this model/A/H");
     if (e->timing) {
@@ -256,14 +256,27 @@ mppi_status mppi_read_outputs(mppi_engine* e, double* out, float* u0, mppi_stats
         uu = e->rec_u0.data();
         st = e->rec_stats.data();
     }
+    // A bounded engine hands out u0 clamped on its rotor dims (u_prev stays the raw warm start: SavGol's negative
+    // taps can carry row 0 past a bound), and the base's outputs below are formed from that clamped u0.  The
+    // stats' finiteness check further down reads the raw row.
+    const float* uo = uu;
+    if (e->has_limits) {
+        e->lim_u0.assign(uu, uu + (size_t)e->V * e->A);
+        for (int v = 0; v < e->V; ++v)
+            for (int a = 0; a < kLimitsN; ++a) {
+                float& x = e->lim_u0[(size_t)v * e->A + a];
+                x = x < e->limits.lo[a] ? e->limits.lo[a] : x > e->limits.hi[a] ? e->limits.hi[a] : x;   // (a NaN stays)
+            }
+        uo = e->lim_u0.data();
+    }
     if (out) std::memcpy(out, o, sizeof(double) * e->V * e->out_dim);
     if (out && e->cfg.model == MPPI_MODEL_QUADROTOR)
         for (int v = 0; v < e->V; ++v)
-            quad_outputs(e, e->state.data() + (size_t)v * e->state_dim, uu + (size_t)v * e->A, out + (size_t)v * e->out_dim);
+            quad_outputs(e, e->state.data() + (size_t)v * e->state_dim, uo + (size_t)v * e->A, out + (size_t)v * e->out_dim);
     if (out && e->cfg.model == MPPI_MODEL_AERIAL)
         for (int v = 0; v < e->V; ++v)
-            aerial_outputs(e, e->state.data() + (size_t)v * e->state_dim, uu + (size_t)v * e->A, out + (size_t)v * e->out_dim);
-    if (u0) std::memcpy(u0, uu, sizeof(float) * e->V * e->A);
+            aerial_outputs(e, e->state.data() + (size_t)v * e->state_dim, uo + (size_t)v * e->A, out + (size_t)v * e->out_dim);
+    if (u0) std::memcpy(u0, uo, sizeof(float) * e->V * e->A);
     bool nonfinite = false;
     for (int v = 0; v < e->V; ++v) {
         int reach = 0;
@@ -336,7 +349,7 @@ mppi_status mppi_step(mppi_engine* e, const double* state, const float* h_noise,
     if (e->comm && (st = mppi_exchange(e)) != MPPI_OK) return st;
     if ((st = mppi_finalize(e)) != MPPI_OK) return st;
     if (!e->kern_call_hip || e->kern_call_peer != e->peer) {   // (mppi_kernel_info; described once)
-        e->kern_call = kernels_text(roll_symbol(rollout_params(e, StepPath::Hip, dn, false), e->threads, nullptr, e->d_ttab, e->d_scene, e->d_field, e->self_members),
+        e->kern_call = kernels_text(roll_symbol(rollout_params(e, StepPath::Hip, dn, false), e->threads, nullptr, e->d_ttab, e->d_scene, e->d_field, e->self_members, e->d_limits),
                                     fin_symbol(finalize_params(e, FinKind::Final)), nullptr);
         e->kern_call_hip = true;
         e->kern_call_peer = e->peer;
@@ -501,7 +514,7 @@ mppi_status mppi_run_steps(mppi_engine* e, int32_t n) {
         if ((st = finalize_impl(e, i == n - 1, true)) != MPPI_OK) return st;
     }
     {   // (mppi_kernel_info) the launches above, described
-        const auto roll = [&](bool quiet) { return roll_symbol(rollout_params(e, StepPath::Hip, nullptr, quiet), e->threads, nullptr, e->d_ttab, e->d_scene, e->d_field, e->self_members); };
+        const auto roll = [&](bool quiet) { return roll_symbol(rollout_params(e, StepPath::Hip, nullptr, quiet), e->threads, nullptr, e->d_ttab, e->d_scene, e->d_field, e->self_members, e->d_limits); };
         const auto fin = [&](bool quiet) { return fin_symbol(finalize_params(e, FinKind::Final, StepPath::Hip, quiet)); };
         const std::string q = fin(n > 1), rq = roll(n > 1);
         e->kern_batch = kernels_text(roll(false), fin(false), &q, &rq);

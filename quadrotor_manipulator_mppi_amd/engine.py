@@ -114,6 +114,73 @@ class Scene:
         return c
 
 
+class Limits:
+    """The rotor limits of a bounded engine (``Engine(cfg, limits=...)``, mppi_create_limits; quadrotor and
+    aerial): ``thrust=(lo, hi)`` [N] and ``torque=((lo, hi),) * 3`` [N m] about x, y, z -- action dims 0..3.
+    ``-inf`` / ``+inf`` leave a side open.  Whether an engine has limits is fixed at creation; the values can
+    be replaced with ``Engine.set_limits``.  Hashable by value."""
+
+    def __init__(self, thrust=(-np.inf, np.inf), torque=((-np.inf, np.inf),) * 3):
+        t = tuple(torque)
+        if len(t) != 3 or len(tuple(thrust)) != 2 or any(len(tuple(x)) != 2 for x in t):
+            raise ValueError("limits: thrust=(lo, hi) and torque=((lo, hi),) * 3")
+        self.thrust = tuple(float(x) for x in thrust)
+        self.torque = tuple(tuple(float(x) for x in pair) for pair in t)
+
+    @property
+    def lo(self) -> np.ndarray:
+        return np.float32([self.thrust[0]] + [p[0] for p in self.torque])
+
+    @property
+    def hi(self) -> np.ndarray:
+        return np.float32([self.thrust[1]] + [p[1] for p in self.torque])
+
+    def _key(self):
+        return (self.thrust, self.torque)
+
+    def __eq__(self, other):
+        return isinstance(other, Limits) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"Limits(thrust={self.thrust}, torque={self.torque})"
+
+    @staticmethod
+    def default(cfg: capi.Config) -> "Limits":
+        """Thrust within [0, 2 m g] of the config's quad_mass and quad_gravity, the torques unbounded
+        (mppi_limits_default)."""
+        c = capi.Limits()
+        capi.lib().mppi_limits_default(C.byref(c), C.byref(cfg))
+        return Limits.from_c(c)
+
+    @staticmethod
+    def from_c(c: capi.Limits) -> "Limits":
+        return Limits((c.lo[0], c.hi[0]), tuple((c.lo[a], c.hi[a]) for a in (1, 2, 3)))
+
+    def to_c(self) -> capi.Limits:
+        c = capi.Limits()
+        c.lo[:] = [float(x) for x in self.lo]
+        c.hi[:] = [float(x) for x in self.hi]
+        return c
+
+
+def limits_apply(limits: "Limits", u, eps):
+    """The limits' arithmetic on the host (mppi_limits_apply: the kernels' own inline, no GPU): ``u`` (H, 4)
+    and ``eps`` (K, H, 4) float32 into ``(eps_eff, ctl)``, each (K, H, 4)."""
+    u = np.ascontiguousarray(u, np.float32)
+    eps = np.ascontiguousarray(eps, np.float32)
+    K, H = eps.shape[0], eps.shape[1]
+    if u.shape != (H, 4) or eps.shape != (K, H, 4):
+        raise ValueError(f"limits_apply: u {u.shape} and eps {eps.shape}, expected (H, 4) and (K, H, 4)")
+    e, c = np.empty_like(eps), np.empty_like(eps)
+    lc = limits.to_c()
+    capi.check(capi.lib().mppi_limits_apply(C.byref(lc), capi.fptr(u), capi.fptr(eps), K, H, capi.fptr(e), capi.fptr(c)),
+               "mppi_limits_apply")
+    return e, c
+
+
 class SelfCollision:
     """The self-collision pairs of a self engine (``Engine(cfg, scene=..., self_collision=...)``,
     mppi_create_scene_self): up to 32 unordered pairs ``(a, b)`` of the scene's body spheres, indexed as in
@@ -427,22 +494,31 @@ class Engine:
     """One MPPI engine on one GPU (V vehicles x K samples x H steps)."""
 
     def __init__(self, cfg: Optional[capi.Config] = None, scene: Optional[Scene] = None,
-                 field: Optional[DistanceField] = None, self_collision: Optional[SelfCollision] = None, **kw):
+                 field: Optional[DistanceField] = None, self_collision: Optional[SelfCollision] = None,
+                 limits: Optional[Limits] = None, **kw):
         """``scene``: a ``Scene`` makes this an obstacle-avoiding engine (``set_obstacles``,
         ``get_clearances``, ``Plan.clearance``); None: the engine as before.  ``field``: a
         ``DistanceField`` adds a voxel distance field as one more obstacle (``set_distance_field``,
         ``clear_distance_field``); without ``scene`` it uses ``Scene.default(cfg)``.
         ``self_collision``: a ``SelfCollision`` adds the self-collision pairs of the scene's spheres
-        (``get_self_clearances``, ``Plan.self_clearance``; arm and whole-body), likewise with the default scene."""
+        (``get_self_clearances``, ``Plan.self_clearance``; arm and whole-body), likewise with the default scene.
+        ``limits``: a ``Limits`` makes this a bounded engine (quadrotor and aerial; ``set_limits``,
+        ``get_limits``): thrust and body torques are clamped in the rollouts, the plan and the returned u0."""
         self._L = capi.lib()
         self.cfg = cfg if cfg is not None else make_config(**kw)
         if (field is not None or self_collision is not None) and scene is None:
             scene = Scene.default(self.cfg)
+        if limits is not None and scene is not None:
+            raise ValueError("limits are for the quadrotor and aerial models, which have no scene engines")
         self.scene = scene
         self.field = field
         self.self_collision = self_collision
+        self.has_limits = limits is not None
         h = C.c_void_p()
-        if self_collision is not None:
+        if limits is not None:
+            lc = limits.to_c()
+            capi.check(self._L.mppi_create_limits(C.byref(self.cfg), C.byref(lc), C.byref(h)), "mppi_create_limits")
+        elif self_collision is not None:
             sc, sf = scene.to_c(), self_collision.to_c()
             fd = None if field is None else field.to_c()
             capi.check(self._L.mppi_create_scene_self(C.byref(self.cfg), C.byref(sc), None if fd is None else C.byref(fd),
@@ -713,6 +789,19 @@ class Engine:
         w = None if velocities is None else np.ascontiguousarray(velocities, np.float32).reshape(n, 3)
         capi.check(self._L.mppi_set_obstacles(self._h, vehicle, n, capi.fptr(c), capi.fptr(r), capi.fptr(w)),
                    "set_obstacles")
+
+    def set_limits(self, limits: Limits):
+        """Replaces a bounded engine's rotor limits (mppi_set_limits).  Takes effect on the next step."""
+        if not self.has_limits:
+            raise RuntimeError("engine created without limits (Engine(cfg, limits=Limits(...)))")
+        lc = limits.to_c()
+        capi.check(self._L.mppi_set_limits(self._h, C.byref(lc)), "set_limits")
+
+    def get_limits(self) -> Optional[Limits]:
+        """The bounds as last set, or None on an engine created without limits."""
+        has, lc = C.c_int32(0), capi.Limits()
+        capi.check(self._L.mppi_get_limits(self._h, C.byref(has), C.byref(lc)), "get_limits")
+        return Limits.from_c(lc) if has.value else None
 
     def set_distance_field(self, d, origin=None):
         """Replaces a field engine's distance field: ``d`` (nz, ny, nx) metres, negative inside;

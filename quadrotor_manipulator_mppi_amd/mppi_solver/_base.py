@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import _capi as capi
-from ..engine import Engine, Scene, SelfCollision, check_shift, cost_term_bits, make_config
+from ..engine import Engine, Limits, Scene, SelfCollision, check_shift, cost_term_bits, make_config
 
 
 class OutputRing:
@@ -120,6 +120,8 @@ class SolverBase:
         full_key = (key, self._scene, self._field)   # (the scene and the field's grid are fixed per engine)
         if self._self_collision is not None:
             full_key += (self._self_collision,)       # (and the pair list)
+        if self._limits is not None:
+            full_key += ("limits",)                   # (that an engine is bounded; the values are replaceable)
         if e is not None and full_key == self._engine_key:
             return e
         u = self._u_prev_host if e is None else e.get_u_prev()[0]
@@ -137,6 +139,11 @@ class SolverBase:
                 scene = Scene.default(cfg)
             pairs = SelfCollision.default(cfg, scene) if self._self_collision is True else self._self_collision
             e = self._engine = Engine(cfg, scene=scene, field=self._field, self_collision=pairs)
+        elif self._limits is not None:   # True: the default bounds of the config (engine.Limits.default)
+            if self._limits is True:
+                self._limits = Limits.default(cfg)
+            e = self._engine = Engine(cfg, limits=self._limits)
+            self._limits_sent = (e, self._limits)
         else:
             e = self._engine = Engine(cfg) if scene is None and self._field is None else Engine(cfg, scene=scene, field=self._field)
         self._engine_key = full_key
@@ -233,6 +240,31 @@ class SolverBase:
         if self._scene is None:
             raise RuntimeError("clear_obstacles needs scene=... at construction")
         self._obstacles = None
+
+    # ``limits=`` (a constructor keyword of the quadrotor and aerial classes): an ``engine.Limits``, or True for the
+    # default bounds (thrust within [0, 2 m g]), makes the engine a bounded one.  That is fixed at construction;
+    # the values are not.
+    _limits = None
+    _limits_sent = None    # (engine, limits) last written (_sync_limits)
+
+    def set_limits(self, limits) -> None:
+        """The rotor limits (``Engine.set_limits``): an ``engine.Limits``.  Used from the next control call on."""
+        if self._limits is None:
+            raise RuntimeError("set_limits needs limits=... at construction")
+        if not isinstance(limits, Limits):
+            raise TypeError("set_limits takes an engine.Limits")
+        self._limits = limits
+
+    def get_limits(self):
+        """The rotor limits in use (True until the first control call has made the engine, when they were left to
+        the default), or None without ``limits=``."""
+        return self._limits
+
+    def _sync_limits(self, eng: Engine) -> None:
+        lim, sent = self._limits, self._limits_sent
+        if lim is not None and (sent is None or sent[0] is not eng or sent[1] is not lim):
+            eng.set_limits(lim)
+            self._limits_sent = (eng, lim)
 
     # ``self_collision=`` (a constructor keyword of the arm class): an ``engine.SelfCollision``, or True for
     # the placeholder pairs, makes the engine a self engine (with ``scene``, or the placeholder spheres).
@@ -403,10 +435,11 @@ class VehicleSolver(SolverBase):
     _horizon_attr = "n_timestep"
 
     def __init__(self, width: int, sigma: torch.Tensor, n_samples: int, n_timestep: int, *base_args,
-                 track_target: bool = False, scene=None, field=None):
+                 track_target: bool = False, scene=None, field=None, limits=None):
         super().__init__(sigma.shape[0], n_timestep, *base_args)
         self._track_target = bool(track_target)
         self._scene = scene
+        self._limits = limits
         self._init_field(field)
         self.n_samples = n_samples
         self.n_timestep = n_timestep
@@ -442,6 +475,7 @@ class VehicleSolver(SolverBase):
         self._sync_target(eng, np.asarray(self.target, np.float32))
         self._sync_target_rows(eng)
         self._sync_obstacles(eng)
+        self._sync_limits(eng)
         out, u0, stats = eng.step(row, noise)
         st = self._after_step(u0, stats)   # (u: the tensor is made on first read)
         if self.verbose:

@@ -36,13 +36,16 @@ class MPPI(SolverBase):
                  noise: str = "philox", seed: int = 0x5EED, mass: float = 14.7, inertia=(1.57, 3.93, 2.59),
                  kd: float = 0.0, gravity: float = 9.81, urdf_path: Optional[str] = None, root_link: str = "base",
                  end_link: str = "j2s7s300_link_7", verbose: bool = False, prewarm_us: int = 0,
-                 track_target: bool = False, scene=None, field=None, self_collision=None):
+                 track_target: bool = False, scene=None, field=None, self_collision=None, limits=None):
+        """``limits``: an ``engine.Limits`` (or True: thrust within [0, 2 m g], torques unbounded) bounds thrust and
+        body torques in the rollouts, the plan and the returned u; ``set_limits`` replaces the values."""
         for what, given in (("self-collision pairs", self_collision is not None), ("distance fields", field is not None),
                             ("obstacle scenes", scene is not None), ("target trajectories", bool(track_target))):
             if given:
                 raise NotImplementedError(f"{what} are not available for the aerial manipulator model (its rollout "
                                           "kernel runs the pose cost alone); use the arm class")
         super().__init__(11, n_horizon, device, noise, seed, verbose, prewarm_us)
+        self._limits = limits
         self.n_manipulator_dof = 7
         self.n_samples = n_samples
         self.n_horizon = n_horizon
@@ -91,6 +94,7 @@ class MPPI(SolverBase):
             row[19:26] = self._qdot
         eng = self._ensure_engine((noise is not None or self._noise == "injected", self.n_samples, self.n_horizon))
         self._sync_target(eng, self.target_pose.pose.numpy(), self.target_pose.orientation.numpy())
+        self._sync_limits(eng)
         out, u0, stats = eng.step(row, noise)
         st = self._after_step(u0, stats)
         if self.verbose:

@@ -26,7 +26,9 @@ class MPPI(VehicleSolver):
     def __init__(self, n_samples: int = 1000, n_timestep: int = 32, device: Optional[int] = None,
                  noise: str = "philox", seed: int = 0x5EED, mass: float = 14.7,
                  inertia=(1.57, 3.93, 2.59), kd: float = 0.0, gravity: float = 9.81, verbose: bool = False, prewarm_us: int = 0,
-                 track_target: bool = False, scene=None, field=None, self_collision=None):
+                 track_target: bool = False, scene=None, field=None, self_collision=None, limits=None):
+        """``limits``: an ``engine.Limits`` (or True: thrust within [0, 2 m g], torques unbounded) bounds thrust and
+        body torques in the rollouts, the plan and the returned u; ``set_limits`` replaces the values."""
         if self_collision is not None:
             raise NotImplementedError("self-collision pairs are not available for the 6-DoF quadrotor model "
                                       "(no scene form of its rollout kernel); use the arm class")
@@ -37,7 +39,7 @@ class MPPI(VehicleSolver):
             raise NotImplementedError("obstacle scenes are not available for the 6-DoF quadrotor model "
                                       "(no scene form of its rollout kernel); use the drone or arm classes")
         super().__init__(6, torch.diag(torch.tensor([30.0, 1.0, 1.0, 1.0])), n_samples, n_timestep,
-                         device, noise, seed, verbose, prewarm_us, track_target=track_target)
+                         device, noise, seed, verbose, prewarm_us, track_target=track_target, limits=limits)
         self.params = dict(quad_mass=mass, quad_inertia=tuple(inertia), quad_kd=kd, quad_gravity=gravity)
         self._u_prev_host[:, 0] = np.float32(mass * gravity)   # hover thrust
 
